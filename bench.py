@@ -6,7 +6,13 @@ reduce -> finish for every env of this rank) + rewards.sum().backward() (action 
 single RCCL all-gather of rollout records.  value = (envs of all ranks x steps) / max-over-ranks wall time.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--img S]
-                  [--workload shapenet5k|mixed|teapot|ppo_rollout]
+                  [--workload shapenet5k|mixed|teapot|ppo_rollout] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the one JSON line (value, ms_per_step, ...).  ``--full``
+measures everything else as well: the raster kernel's own time and the roofline figures (events around every raster
+launch of the timed region), the fresh_outputs leg and the CPU baselines.  ``--dump-outputs DIR`` writes what the
+last timed step computed to DIR/<name>.npy (dump_outputs()); the inputs are seeded, so runs with the same arguments
+can be compared output for output.
 
 ``--gpus N`` with N > 1 from a plain shell: this process starts
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...``
@@ -67,7 +73,15 @@ def parse_args(argv=None):
                          "released output sets; the 'fresh_outputs' leg of the JSON line measures this mode as well")
     ap.add_argument("--fresh-steps", type=int, default=40, help="steps of the fresh_outputs leg (N = 1 only; 0 = skip)")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (0 = pick a free one)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: raster kernel time + roofline (events in the timed region), the fresh_outputs "
+                         "leg (--fresh-steps) and the CPU baselines (--no-cpu-baseline / --cpu-sample)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (rank 0's envs) as DIR/<name>.npy, float32; "
+                         "images for a fixed, seeded sample of the envs (env_index.npy), at most 64 MB in all")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.envs is None:
         args.envs = 256 if args.workload == "ppo_rollout" else 1024
     if args.img is None:
@@ -145,7 +159,7 @@ def build_env(workload: str, n_env: int, img: int, seed: int, pool_models: int =
         ds = None
     else:
         # pool of 1 024 procedural ShapeNet-size meshes, seed 1234 (94 MB on the device: beyond L2)
-        # (cached under the temp dir: eight ranks of a node start together, and ~26 s of mesh generation per rank and run
+        # (cached under the temp dir: eight ranks of a node start together, and ~5-9 s of mesh generation per rank and run
         # is start-up nobody needs twice)
         import tempfile
 
@@ -287,6 +301,99 @@ def committed_profile(args, raster_short):
     return None, None
 
 
+DUMP_BYTES = 48 << 20    # data of one --dump-outputs set (+ the .npy headers: well under 64 MB)
+DUMP_SAMPLED = 16 << 10  # arrays with more bytes per env than this (the images) are written for a sample of the envs
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES, seed=0):
+    """Write ``arrays`` (name -> array or tensor, axis 0 = env) as out_dir/<name>.npy: float64 stays float64, every other
+    dtype becomes float32.  Arrays of more than DUMP_SAMPLED bytes per env keep the rows of a fixed sample of the envs -
+    drawn from ``seed``, the same rows for all of them, listed in env_index.npy - sized so that the whole set stays
+    within ``budget`` bytes; the others are written whole.  Tensors are cut where they live, before the copy to the
+    host.  Returns {name: shape written}."""
+    import numpy as np
+    import torch
+
+    def f64(a):
+        return str(a.dtype).endswith("float64")
+
+    n_env = {int(a.shape[0]) for a in arrays.values()}
+    if len(n_env) != 1:
+        raise ValueError(f"dump_outputs: arrays disagree on the number of envs: {sorted(n_env)}")
+    n_env = n_env.pop()
+    row = {k: (8 if f64(a) else 4) * int(np.prod(a.shape[1:])) for k, a in arrays.items()}
+    big = [k for k in arrays if row[k] > DUMP_SAMPLED]
+    rest = budget - sum(row[k] * n_env for k in arrays if k not in big) - 8 * n_env
+    keep = n_env if not big else max(1, min(n_env, rest // sum(row[k] for k in big)))
+    idx = np.arange(n_env) if keep == n_env else np.sort(np.random.default_rng(seed).choice(n_env, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for k, a in list(arrays.items()) + [("env_index", idx.astype(np.float64))]:
+        if hasattr(a, "detach"):
+            a = a.detach()
+            a = (a[torch.as_tensor(idx, device=a.device)] if k in big and keep < n_env else a).cpu().numpy()
+        else:
+            a = np.asarray(a)
+            a = a[idx] if k in big else a
+        a = np.ascontiguousarray(a, dtype=np.float64 if f64(a) else np.float32)
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        shapes[k] = a.shape
+    return shapes
+
+
+def roofline(args, venv, dt, ms_sum, launches):
+    """--full: the dominant kernel's achieved bandwidth against the HBM peak, from the events around every raster launch
+    of the timed region (occ_profile_read: ``ms_sum`` over ``launches`` full-batch launches), and the committed PMC
+    figures of this command line where profiles/ holds them."""
+    eng = venv.engine
+    raster_short = "occ_raster2_kernel"
+    raster_name = raster_short + "<soft,hard,grad>"
+    # algorithmic bytes of one launch of the dominant kernel (= one batched step of this rank)
+    vf = 0.0
+    for e in venv.envs:
+        for m in e._scene[0]:
+            v, f = eng.pool.get(m)
+            vf += v.shape[0] + f.shape[0]
+    b_launch = b_alg_bytes(vf / args.envs, args.img) * args.envs
+    # mean over the full-batch launches of the timed region (auto-resets render tiny batches of their own)
+    avg_ms = ms_sum.value / max(launches.value, 1)
+    achieved = b_launch / (avg_ms * 1e-3) / 1e9 if launches.value else None
+    pj, prof = committed_profile(args, raster_short)
+    traffic = traffic_src = valu = None
+    if pj is not None:
+        traffic = pj.get("hbm_bytes_per_launch")
+        traffic_src = "profiles/%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, " \
+                      "2*FETCH + WRITE; not collected in this run)" % prof
+        nv = pj.get("counters", {}).get("SQ_INSTS_VALU")
+        if nv and launches.value:
+            issue_ms = nv * VALU_CYCLES / (SIMDS * CLOCK_HZ) * 1e3
+            valu = {"insts_per_launch": nv, "issue_ms": issue_ms, "frac_of_launch": issue_ms / avg_ms,
+                    "model": f"SQ_INSTS_VALU x {VALU_CYCLES} cycles / ({SIMDS} SIMDs x {CLOCK_HZ / 1e9:.1f} GHz)",
+                    "source": "profiles/%s (not collected in this run)" % prof}
+    # SURVEY 8d "secondary accounting" (reported, not canonical): the fragments PyTorch3D's design materialises per
+    # env-step - 28 B x K x S^2 per soft render x 3 + 28 B x S^2 hard forward, 12 B x K x S^2 x 3 re-read backward
+    frag_step = (28.0 * 100 * 3 + 28.0 + 12.0 * 100 * 3) * args.img * args.img
+    ms_step = dt / args.steps * 1e3
+    step_frac = b_launch / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS
+    return {"bound": "hbm", "kernel": raster_name, "achieved": achieved,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+            # the same algorithmic bytes over the WHOLE step (all launches, host gaps) / peak
+            "step_frac": step_frac,
+            # what the counters say the dominant kernel really moves (2 FETCH + WRITE) / its duration / peak
+            "counter_frac": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and launches.value) else None,
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": b_launch, "avg_launch_ms": avg_ms,
+            "launches": launches.value, "valu": valu,
+            "secondary": {"label": "materialised-fragments accounting of SURVEY 8d (what PyTorch3D's design moves; "
+                                   "NOT canonical, the fused path never materialises them)",
+                          "bytes_per_env_step": frag_step, "bytes_per_launch": frag_step * args.envs,
+                          "achieved": (frag_step * args.envs / (avg_ms * 1e-3) / 1e9) if launches.value else None,
+                          "unit": "GB/s", "frac": (frag_step * args.envs / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if launches.value else None},
+            "note": "VALU/latency-bound rasterisation; compulsory bytes are ~1.47 MB/env-step (SURVEY 8d)"}
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
@@ -341,8 +448,9 @@ def main(argv=None):
     # pooling + a latency-bound collective next to a VALU-bound raster kernel).  rollout.RecordExchange.
     xch = rollout.RecordExchange(args.envs, dev, world) if (world > 1 and not ppo_mode) else None
     zeros_lp = torch.zeros(args.envs, device=dev)
+    last = {}  # what the last timed step handed its caller (--dump-outputs); filled by that step only
 
-    def one_step():
+    def one_step(keep=False):
         actions = torch.randn(args.envs, 2, device=dev, generator=gen, requires_grad=True)
         obs, rewards, dones, infos = venv.step(actions)
         rewards.sum().backward()
@@ -351,6 +459,8 @@ def main(argv=None):
             # the env's synchronous reset fallback writes reset observations into ``obs`` in place at the start of
             # the next step: it must not overtake the side stream's read of it
             venv.obs_consumer_event = xch.ready
+        if keep:
+            last.update(actions=actions, obs=obs, rewards=rewards, dones=dones, infos=infos)
         return actions.grad
 
     ppo_state = {}
@@ -366,10 +476,13 @@ def main(argv=None):
         # the per-step record exchange on its own stream: the record of step t is stored while step t + 1 renders
         pxch = rollout.RecordExchange(args.envs, dev, world, keep=True)
 
-        def one_step():  # noqa: F811 - trainRL.py:196-216, batched
+        def one_step(keep=False):  # noqa: F811 - trainRL.py:196-216, batched
             feats, action, logprob = agent.select_action(ppo_state["obs"], gen)
             action = action.detach().requires_grad_(True)
             obs, rewards, dones, _infos = venv.step(action)
+            if keep:
+                last.update(actions=action, logprob=logprob, features=feats, obs=obs, rewards=rewards, dones=dones,
+                            infos=_infos)
             rewards.sum().backward()  # differentiable-reward backward to the action (train_predict.py:52)
             if ppo_state["pending"]:
                 agent.store(pxch.wait())
@@ -405,13 +518,15 @@ def main(argv=None):
         del warm
         agent.records = []  # the timed region starts a fresh rollout
         ppo_state["pending"], ppo_state["t"] = False, 0
-    nat.check(lib.occ_profile_enable(1), "occ_profile_enable")
+    if args.full:  # the raster kernel's own time (roofline): events around every raster launch of the timed region
+        nat.check(lib.occ_profile_enable(1), "occ_profile_enable")
     barrier()
     trace = os.environ.get("OCC_BENCH_TRACE")
     stamps = []
+    dump = args.dump_outputs is not None and rank == 0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        g = one_step()
+    for i in range(args.steps):
+        g = one_step(keep=dump and i == args.steps - 1)
         if trace:
             stamps.append(time.perf_counter())
     barrier()
@@ -422,14 +537,29 @@ def main(argv=None):
     import ctypes as C
 
     ms_sum, launches = C.c_double(0.0), C.c_int(0)
-    nat.check(lib.occ_profile_read(C.byref(ms_sum), C.byref(launches)), "occ_profile_read")
-    lib.occ_profile_enable(0)
+    if args.full:
+        nat.check(lib.occ_profile_read(C.byref(ms_sum), C.byref(launches)), "occ_profile_read")
+        lib.occ_profile_enable(0)
     eng.check_status()
     assert torch.isfinite(g).all()
+    if dump:
+        # copies first: reading infos runs the deferred auto-reset bookkeeping, whose synchronous fallback (reserve ran
+        # dry) would write reset observations into rows of obs
+        arrays = {k: last[k].detach().clone() for k in ("obs", "rewards", "dones", "actions", "logprob", "features") if k in last}
+        arrays["action_grad"] = g
+        infos = last.pop("infos")
+        arrays["full_state"] = torch.cat([infos[i]["full_state"] for i in range(args.envs)])
+        arrays["position"] = torch.stack([infos[i]["position"] for i in range(args.envs)])
+        arrays["full_reward"] = torch.stack([infos[i]["full_reward"] for i in range(args.envs)])
+        shapes = dump_outputs(args.dump_outputs, arrays)
+        print(f"[bench] outputs of the last timed step in {args.dump_outputs}: "
+              + ", ".join(f"{k}{list(s)}" for k, s in shapes.items()), file=sys.stderr)
+        del arrays, infos
+        last.clear()
     # fresh_outputs leg (N = 1): the same step with every output tensor allocated anew and written in full - what the
     # reference's allocator does - timed after the main region on the same env, for the reader who wants that number
     fresh = None
-    if world == 1 and args.fresh_steps > 0 and not ppo_mode and eng.R and (not args.no_recycle or args.output_ring):
+    if args.full and world == 1 and args.fresh_steps > 0 and not ppo_mode and eng.R and (not args.no_recycle or args.output_ring):
         del g
         venv.use_output_ring(0)
         venv.use_recycled_outputs(0)
@@ -449,48 +579,19 @@ def main(argv=None):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    raster_short = "occ_raster2_kernel"
-    raster_name = raster_short + "<soft,hard,grad>"
     if rank == 0:
         total_envs = args.envs * world
         value = total_envs * args.steps / dt
-        # algorithmic bytes of one launch of the dominant kernel (= one batched step of this rank)
-        vf = 0.0
-        for e in venv.envs:
-            for m in e._scene[0]:
-                v, f = eng.pool.get(m)
-                vf += v.shape[0] + f.shape[0]
-        b_launch = b_alg_bytes(vf / args.envs, args.img) * args.envs
-        # mean over the full-batch launches of the timed region (auto-resets render tiny batches of their own)
-        avg_ms = ms_sum.value / max(launches.value, 1)
-        achieved = b_launch / (avg_ms * 1e-3) / 1e9 if launches.value else None
-        pj, prof = committed_profile(args, raster_short)
-        traffic = traffic_src = valu = None
-        if pj is not None:
-            traffic = pj.get("hbm_bytes_per_launch")
-            traffic_src = "profiles/%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, " \
-                          "2*FETCH + WRITE; not collected in this run)" % prof
-            nv = pj.get("counters", {}).get("SQ_INSTS_VALU")
-            if nv and launches.value:
-                issue_ms = nv * VALU_CYCLES / (SIMDS * CLOCK_HZ) * 1e3
-                valu = {"insts_per_launch": nv, "issue_ms": issue_ms, "frac_of_launch": issue_ms / avg_ms,
-                        "model": f"SQ_INSTS_VALU x {VALU_CYCLES} cycles / ({SIMDS} SIMDs x {CLOCK_HZ / 1e9:.1f} GHz)",
-                        "source": "profiles/%s (not collected in this run)" % prof}
         what = (f"PPO rollout (T={args.rollout_T}, heads-only update of {args.ppo_epochs} epochs inside the timed region"
                 + (f", episode time limit {args.max_ep_len} steps" if args.max_ep_len else "") + "), " if ppo_mode else "")
         meshes = {"teapot": "3 x data/teapot.obj (2 464 faces) per env", "mixed": "3 meshes per env from a mixed 1 280 / 5 120 / 20 480-face pool",
                   "shapenet5k": "3 ShapeNet-size (~5k-face) meshes per env"}[scene_workload]
         collective = {"nccl": "RCCL", "gloo": "gloo (rehearsal: the ranks share devices, no RCCL)"}[args.dist_backend]
-        # SURVEY 8d "secondary accounting" (reported, not canonical): the fragments PyTorch3D's design materialises per
-        # env-step - 28 B x K x S^2 per soft render x 3 + 28 B x S^2 hard forward, 12 B x K x S^2 x 3 re-read backward
-        frag_step = (28.0 * 100 * 3 + 28.0 + 12.0 * 100 * 3) * args.img * args.img
         ring_on = bool(args.output_ring and eng.R)
         recycle_on = bool(eng.R and not args.no_recycle and not ring_on)
         out_mode = (f"outputs in a ring of {args.output_ring} persistent sets (overwritten {args.output_ring} steps later)" if ring_on else
                     "recycled outputs (a released output set is reused; nothing a caller holds is ever overwritten)" if recycle_on else
                     "fresh output tensors every step")
-        ms_step = dt / args.steps * 1e3
-        step_frac = b_launch / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS
         out = {
             # BASELINE.json's metric is quoted at 128x128 (the default --img); other sizes say so
             "metric": f"env steps/sec (batched renders) @{args.img}x{args.img}, {meshes}"
@@ -514,30 +615,15 @@ def main(argv=None):
                        "envs_per_gpu": args.envs, "img": args.img, "faces_per_pixel": 100, "pool_models": args.pool_models,
                        "output_ring": args.output_ring if ring_on else 0, "recycled_outputs": recycle_on, "collective_backend": args.dist_backend if world > 1 else None,
                        "sharding": f"env-sharded x{world}, no data-path collective"},
-            "roofline": {"bound": "hbm", "kernel": raster_name, "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                         # the same algorithmic bytes over the WHOLE step (all launches, host gaps) / peak
-                         "step_frac": step_frac,
-                         # what the counters say the dominant kernel really moves (2 FETCH + WRITE) / its duration / peak
-                         "counter_frac": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and launches.value) else None,
-                         "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": b_launch, "avg_launch_ms": avg_ms,
-                         "launches": launches.value, "valu": valu,
-                         "secondary": {"label": "materialised-fragments accounting of SURVEY 8d (what PyTorch3D's design moves; "
-                                                "NOT canonical, the fused path never materialises them)",
-                                       "bytes_per_env_step": frag_step, "bytes_per_launch": frag_step * args.envs,
-                                       "achieved": (frag_step * args.envs / (avg_ms * 1e-3) / 1e9) if launches.value else None,
-                                       "unit": "GB/s", "frac": (frag_step * args.envs / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if launches.value else None},
-                         "note": "VALU/latency-bound rasterisation; compulsory bytes are ~1.47 MB/env-step (SURVEY 8d)"},
         }
+        if args.full:
+            out["roofline"] = roofline(args, venv, dt, ms_sum, launches)
         if fresh is not None:
             out["fresh_outputs"] = fresh
         if ppo_mode:
             out["ppo"] = {"updates": ppo_state["updates"], "T": args.rollout_T, "epochs": args.ppo_epochs,
                           "last_update": ppo_state["stats"]}
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
             one, par = cpu_baseline(venv, args.cpu_sample, args.img)
             out["cpu_baseline"] = {"value": one["value"], "unit": "env-steps/s", "cores": 1, "kind": "port",
                                    "sample": f"{one['n']} env-steps (step + backward) of the same scenes, oracle/ C naive "

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 run() {
   name=$1; shift
-  env "$@" timeout -k 10 100 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --pool-models 64 2>/dev/null | python -c "
+  env "$@" timeout -k 10 100 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --pool-models 64 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

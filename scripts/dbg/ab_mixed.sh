@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 run() {
   name=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --workload mixed --envs 1024 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" timeout -k 10 200 python bench.py --workload mixed --envs 1024 --steps 20 --warmup 3 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 for v in "" NO_ATOM NO_SEL NO_EVAL; do
   if [ -n "$v" ]; then export OCC_HIP_LIB=$PWD/build/dbg2/libocc_$v.so; else unset OCC_HIP_LIB; fi
-  timeout -k 10 200 python bench.py --steps 20 --warmup 4 --no-cpu-baseline --pool-models 64 2>/dev/null | python -c "
+  timeout -k 10 200 python bench.py --steps 20 --warmup 4 --full --no-cpu-baseline --pool-models 64 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -14,7 +14,9 @@ What is recorded is what the reference computed, nothing restated here:
   * for K = 80 the same ``update()`` once more with the two heads, the buffer and the action variance converted to
     float64 (``.double()``; every line executed is still the reference's): the DOUBLE-PRECISION trajectory's heads,
     ``<scen>_final64_<head>_K80`` - the arbiter of how far an f32 implementation may drift over 80 epochs through the
-    clip boundary of PPO.py:207 (tests/test_ppo_golden.py).
+    clip boundary of PPO.py:207 (tests/test_ppo_golden.py) - and, before that update, ``evaluate()`` on those float64
+    heads, ``<scen>_eval64_{logprobs,values,entropy}`` - the arbiter of an f32 evaluate() on another CPU, whose GEMM
+    rounds differently.
 The reference never travels to the GPU box; only the .npz does.
 """
 import os
@@ -133,6 +135,11 @@ def _run(out, scen, K, make, obs, direct, rewards, terminals, f64=False):
         agent.buffer.actions = [x.double() for x in agent.buffer.actions]
         agent.buffer.logprobs = [x.double() for x in agent.buffer.logprobs]
         agent.buffer.rewards = [x.double() for x in agent.buffer.rewards]
+        with torch.no_grad():  # evaluate() before the update, on the float64 heads: the arbiter of the f32 evaluate()
+            ev_lp, ev_val, ev_ent = agent.policy.evaluate(states.double(), actions.double())
+        out[f"{scen}_eval64_logprobs"] = ev_lp.numpy()
+        out[f"{scen}_eval64_values"] = ev_val.squeeze(-1).numpy()
+        out[f"{scen}_eval64_entropy"] = ev_ent.numpy()
 
         class _Mse64(torch.nn.Module):  # update() builds its returns as float32 (PPO.py:187): MSELoss wants one dtype
             def forward(self, values, returns):
