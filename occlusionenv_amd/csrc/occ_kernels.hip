@@ -283,12 +283,7 @@ extern "C" int occ_step(const OccScene* scene, const OccCameraArgs* camera, floa
         const int fit = (lds_room / 12) & ~63;
         if (vcap > fit) vcap = fit;  // (0: gather from global memory, same results)
     }
-#ifdef OCC_EXP_SETUP_DUMMY_LDS  // occupancy experiment only: the LDS is reserved but the vertices are still gathered from memory
-    size_t vlds = (size_t)vcap * 3 * sizeof(float);
-    vcap = 0;
-#else
     const size_t vlds = (size_t)vcap * 3 * sizeof(float);
-#endif
     if (grad)
         hipLaunchKernelGGL((occ_setup_kernel<true, kSetupTB>), dim3(N * 3), dim3(kSetupTB), vlds, st, *scene, cam, wsv, vcap);
     else

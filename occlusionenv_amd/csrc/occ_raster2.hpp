@@ -2,8 +2,7 @@
 // pixel rows in a small launch - taken heaviest first from the XCD's queue (occ_order_kernel).
 // Part of the single translation unit occ_kernels.hip (included inside namespace occ; not a stand-alone header).
 //
-// How it works (round 2; the round-1 kernel - 4x4-pixel block x 4 face slots, every staged face evaluated at all 16
-// pixels, one lane-strided 16-byte K-buffer store per candidate into per-lane lists - was retired in round 3):
+// How it works:
 //
 //   * LANE = (face, pixel) PAIR.  For every staged face the wave enumerates exactly the pixels of the face's pixel
 //     bbox (setup kernel, +-sqrt(blur)) that fall into the tile - about 10 per ShapeNet-size face and tile, of which
@@ -80,11 +79,10 @@ constexpr int kSweepU = OCC_SWEEP_U;     // 64-entry rows of the log per sweep g
 #ifndef OCC_SWEEP_RING
 #define OCC_SWEEP_RING 2
 #endif
-// Round 5: the final sweep issues the payload loads of a group's kept entries right after the group's decisions and applies
-// them one group later (1.947 -> 1.899 ms).  The sweeps keep kRingGroups groups of kSweepU rows of (key, tag) in flight;
-// more than two buys nothing (three: 1.902 ms, four: 1.939 ms - the registers cost more than the latency hidden), and rows
-// are still handled kSweepU at a time: the window look-ups of a group are independent LDS reads - one row at a time,
-// twelve rows deep in flight, was measured 9 % SLOWER (2.13 - 2.19 ms): the LDS round trips then lie end to end.
+// The final sweep issues the payload loads of a group's kept entries right after the group's decisions and applies them
+// one group later.  The sweeps keep kRingGroups groups of kSweepU rows of (key, tag) in flight, and rows are handled
+// kSweepU at a time: the window look-ups of a group are independent LDS reads; one row at a time would put the LDS round
+// trips end to end.  (Deeper rings and one-row sweeps were measured slower: DESIGN_HISTORY.md H4.)
 constexpr int kRingGroups = OCC_SWEEP_RING;  // groups of kSweepU rows of (key, tag) in flight per sweep
 constexpr int kListCap = 8;    // boundary-bucket entries per pixel that the owner lane resolves itself
 #ifndef OCC_ACC_COPY_BITS
@@ -92,12 +90,7 @@ constexpr int kListCap = 8;    // boundary-bucket entries per pixel that the own
 #endif
 constexpr int kCopyBits = OCC_ACC_COPY_BITS;  // accumulator copies = 1 << kCopyBits, chosen by (face sequence number & (kCopies - 1))
 constexpr int kCopies = 1 << kCopyBits;
-// (Round 5, measured: SIX copies of 12 bytes - product and tangent sums in arrays of their own, candidate count and key bound
-// as one word per pixel bumped by non-returning LDS atomics, the same 12.7 KB - bring a round from 2.21 to 1.54 sub-passes and
-// the kernel from 1.896 to 1.867 ms against FOUR copies in that format; this format, with its single 16-byte access per
-// sub-pass and the count riding along, runs at 1.869: nothing gained, not kept.  The lanes of a round crowd on about ten
-// pixels - seven tiny faces covering the same ones - so even an exact conflict schedule needs 1.9 sub-passes with four copies.
-// Final sweep: sub-passes over a whole group of four rows at once (four reads in flight per sub-pass): 1.930 vs 1.887, worse.)
+// (Six copies in another format, and final-sweep sub-passes over whole groups of rows: not kept, DESIGN_HISTORY.md H4.)
 constexpr int kAccStride = 65; // accumulator slots per copy: one per pixel, +1 so that the copies of a pixel differ mod 16 (acc_slot)
 
 constexpr uint32_t kNoEntry = 0xFFFFFFFFu;  // tag of a slot past the end of the log (a tag is pixel | face sequence number << 6)
@@ -107,13 +100,11 @@ struct LogPay {  // 12 bytes, moved with one dwordx3 access
 struct WaveLog {
     LogPay* __restrict__ pay;
     uint2* __restrict__ kt;    // (order-preserving depth key, pixel of the tile 0..63 | face sequence number << 6)
-    // Round 5: what the selection's LATER sweeps read.  Its first sweep (the first histogram pass) copies the entries of
+    // What the selection's LATER sweeps read.  Its first sweep (the first histogram pass) copies the entries of
     // the pixels that hold more than K candidates - 63 % of the log of a tile that needs selection on the bench - into
     // this region, in log order and unchanged, with every entry's index in the log (where its payload is) beside it in
     // ix2.  The other histogram passes and the final sweep then visit those rows only.
-    // (A first version packed the index and twelve bits of the face sequence number into the tag: a dense object's
-    // pruned log can be so sparse that a 64-entry row of the copy spans thousands of faces - test_sorted_scan_order_build
-    // caught two pixels - and guarding the packing with a span check in the copying loop cost 8 % of the kernel.)
+    // (Index and face number packed into the tag instead: wrong for dense objects, DESIGN_HISTORY.md H4.)
     uint2* __restrict__ kt2;
     uint16_t* __restrict__ ix2;
 };
@@ -182,9 +173,7 @@ __device__ unsigned long long g_dbg_ends[4 * 4096];
 #define OCC_RASTER2_WAVES_PER_SIMD 3
 #endif
 
-// (Launch parameters behind a constant-address-space pointer instead of by value - so that they are s_load-ed where
-// they are used rather than kept or spilled - were measured in round 4: SGPR spills 83 -> 58, kernel 1.949 -> 1.941 ms,
-// inside the noise; none of the spill code sits in the round loop.  Not kept.)
+// (Launch parameters behind a constant pointer instead of by value: fewer SGPR spills, no faster - DESIGN_HISTORY.md H2.)
 template <bool SOFT, bool HARD, bool GRAD>
 __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_kernel(RasterParams P) {
     const int lane = threadIdx.x;
@@ -235,13 +224,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
     const int myslot = acc_slot(0, lane);  // accumulator slot (copy 0) of the pixel this lane owns
     OCC_T_DECL;
 
-    // (Round 5, -DOCC_DBG_ENDS: the waves' last items end within 2.7 % of the launch; then every wave walks the eight heads with
-    // a device-scope RMW each, 35-40 us from its last item to its exit.  A line of "exhausted" flags - byte stores, one load -
-    // brings that to 12 us and the launch not forward: the last items just end later.  Not kept.  The heads 128 bytes apart
-    // instead of 64 - one L2 line each - is what did count: 1.894 -> 1.873 ms.)
-    // (Claiming the NEXT item when an item starts, so that the queue head's atomic round trip flies during the item's work:
-    // measured in round 4, 1.944 -> 1.995 ms.  A wave that holds two items at a time undoes the point of the cost-ordered
-    // queues near the end of the launch.  Not kept.)
+    // (Claiming the next item ahead, and "exhausted" flags for the queues: measured, not kept - DESIGN_HISTORY.md H2, H4.)
     for (;;) {
         OCC_T(9);  // previous item's result stores
         int item = -1, sub = 0;
@@ -433,20 +416,11 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         bool ov = false;
                         if (kt[u].y != kNoEntry) {
                             const uint32_t px = kt[u].y & 63u;
-#ifdef OCC_EXP_NO_P1S  // A/B build: the window looked up in LDS as in the later passes
-                            const uint2 w = s_sel[px];
-                            ov = w.y < 32u;
-                            if (ov) {
-                                const uint32_t d = (kt[u].x - w.x) >> w.y;
-                                if (kt[u].x >= w.x && d < (1u << kSelBits)) atomicAdd(&hist[px * kSelStride + (d >> 1)], 1u << (16 * (d & 1u)));
-                            }
-#else
                             ov = (((px & 32u) ? ovf_hi : ovf_lo) >> (px & 31u)) & 1u;
                             if (ov) {
                                 const uint32_t d = (kt[u].x - L0) >> sh0;
                                 if (kt[u].x >= L0 && d < (1u << kSelBits)) atomicAdd(&hist[px * kSelStride + (d >> 1)], 1u << (16 * (d & 1u)));
                             }
-#endif
                         }
                         const unsigned long long m = __ballot(ov);
                         if (ov) {
@@ -465,17 +439,12 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                     for (int e0 = 0; e0 < nsrc; e0 += kRingG * kGroup) {
 #pragma unroll
                         for (int gi = 0; gi < kRingG; ++gi) {
-#ifdef OCC_EXP_NO_CLOG  // A/B build: no compacted copy, every sweep reads the log itself
-                            bump(ring[gi]);
-#else
                             if (!compact && pass == 0) bump_copy(e0 + gi * kGroup, ring[gi]);
                             else bump(ring[gi]);
-#endif
                             load_group(e0 + (kRingG + gi) * kGroup, ring[gi]);
                         }
                     }
                 }
-#ifndef OCC_EXP_NO_CLOG
                 if (!compact && pass == 0) {
                     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the copy is in memory before it is swept
                     src = lg.kt2;
@@ -483,7 +452,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                     fmt_b = true;
                     OCC_STAT(13, n2);  // entries in the compacted copy
                 }
-#endif
                 pass += 1;
                 wave_lds_sync();
                 OCC_T(11);  // selection: histogram sweeps
@@ -513,10 +481,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                     } else {
                         sh = max(0, sh - kSelBits);
                     }
-#ifdef OCC_EXP_HIST_ONCE  // timing experiment only (results void): what the histogram passes after the first cost
-                    done = true;
-                    mode = kAll;
-#endif
                     s_sel[lane] = make_uint2(L, done ? 255u : (uint32_t)sh);
                 }
                 wave_lds_sync();
@@ -570,11 +534,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
 #pragma unroll
                 for (int u = 0; u < kU; ++u) {
                     const int e = e0 + u * 64 + lane;
-#ifdef OCC_EXP_FS_NO_PAY  // timing experiment only (results void): what the final sweep's dependent payload loads cost
-                    pv[u] = LogPay{__uint_as_float(0x3f800000u | ((readdm >> u) & 1u)), 0.f, (float)e};
-#else
                     pv[u] = (((readdm | (compact ? keepm : 0u)) >> u) & 1u) ? lg.pay[e] : LogPay{1.f, 0.f, 0.f};
-#endif
                 }
 #pragma unroll
                 for (int u = 0; u < kU; ++u) {
@@ -591,18 +551,10 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         const int slot = acc_slot((int)((tag >> 6) & (uint32_t)(kCopies - 1)), (int)(tag & 63u));
                         unsigned long long rem = __ballot(act);
                         OCC_STAT(11, __popcll(rem));  // entries re-accumulated
-#ifdef OCC_EXP_FS_NO_RMW  // timing experiment only (results void): what the final sweep's RMW sub-passes cost
-                        asm volatile("" ::"v"(pv[u].q), "v"(pv[u].ge), "v"(pv[u].ga), "v"(slot), "v"(grp));
-                        rem = 0ull;
-#endif
                         while (rem) {
                             OCC_STAT(12, 1);          // RMW sub-passes of the final sweep
                             const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane((int)grp, __ffsll(rem) - 1);
-#ifdef OCC_EXP_ONE_SUBPASS
-                            const bool mine = act;
-#else
                             const bool mine = act && grp == g0;
-#endif
                             if (mine) {
                                 float4 a = s_acc[slot];
                                 a.x *= pv[u].q;
@@ -670,18 +622,10 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         const int slot = acc_slot((int)((tag >> 6) & (uint32_t)(kCopies - 1)), (int)(tag & 63u));
                         unsigned long long rem = __ballot(act);
                         OCC_STAT(11, __popcll(rem));  // entries re-accumulated
-#ifdef OCC_EXP_FS_NO_RMW  // timing experiment only (results void): what the final sweep's RMW sub-passes cost
-                        asm volatile("" ::"v"(ppay[u].q), "v"(ppay[u].ge), "v"(ppay[u].ga), "v"(slot), "v"(grp));
-                        rem = 0ull;
-#endif
                         while (rem) {
                             OCC_STAT(12, 1);  // RMW sub-passes of the final sweep
                             const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane((int)grp, __ffsll(rem) - 1);
-#ifdef OCC_EXP_ONE_SUBPASS
-                            const bool mine = act;
-#else
                             const bool mine = act && grp == g0;
-#endif
                             if (mine) {
                                 float4 a = s_acc[slot];
                                 a.x *= ppay[u].q;
@@ -720,7 +664,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                                 }
                                 if (r) {
                                     readdm |= 1u << u;
-#ifndef OCC_EXP_FS_SEQ_COPIES
                                     // Which copy takes the entry and in which sub-pass: by the pixel's ARRIVAL INDEX i among its
                                     // kept entries (one counter per pixel; entries of one pixel in one row get consecutive
                                     // indices, in lane = log order - the rule the tie counters above already rest on).  Copy
@@ -733,9 +676,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                                     const uint32_t base = s_arrive[px];                 // (before any lane's add of this row)
                                     const uint32_t i = atomicAdd(&s_arrive[px], 1u);
                                     rtag[u] = px | ((i & 3u) << 6) | (((i - base) >> 2) << 8);
-#else
-                                    rtag[u] = kt[u].y;
-#endif
                                 }
                             }
                         }
@@ -745,11 +685,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         const bool r = (readdm >> u) & 1u;
                         const uint32_t e = ix[u];  // index of the entry in the log itself: where its payload is
                         ptag[u] = r ? (rtag[u] | 0x80000000u) : 0u;
-#ifdef OCC_EXP_FS_NO_PAY  // timing experiment only (results void): what the final sweep's dependent payload loads cost
-                        ppay[u] = LogPay{__uint_as_float(0x3f800000u | (r ? 1u : 0u)), 0.f, (float)e};
-#else
                         ppay[u] = r ? lg.pay[e] : LogPay{1.f, 0.f, 0.f};
-#endif
                     }
                 };
                 for (int e0 = 0; e0 < nsrc; e0 += kRingG * kGroup) {
@@ -992,7 +928,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
             if (nst_next) stage_issue(rstage, boff ^ kStg2, nst_next);
             OCC_T(2);
             {
-#ifndef OCC_DBG2_NO_COMPACT  // register-pressure experiment only (scripts/dbg)
                 if (SOFT && nlog + ptot > OCC_LOG_CAP) {
                     // rare: the log could fill up inside this batch -> keep every overflowing pixel's K nearest,
                     // compact the log, go on with tighter bounds
@@ -1007,14 +942,8 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                     wave_lds_sync();
                     OCC_T(7);  // in-loop compaction
                 }
-#endif
                 int fbase = 0;  // face of the pair just before this round
-#ifdef OCC_DBG2_NO_EVAL  // timing experiment only
-                if (ptot > 0) fbase = -1;
-#endif
-                // pair -> (staged slot, pixel, pixel centre) of one round.  (Issuing the decode of round r + 1 at the top of
-                // round r, so that its three dependent LDS round trips overlap the arithmetic: +1.5 % - the loop is bound by
-                // its VALU work, and carrying the decoded values costs five instructions; reading only the next round's mark bytes ahead: no change.)
+                // pair -> (staged slot, pixel, pixel centre) of one round.  (Decoding the next round ahead: slower, DESIGN_HISTORY.md Appendix A.)
                 struct Dec {
                     bool live;
                     int f, pix, nlive;
@@ -1046,6 +975,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                     dc.yf = __shfl(own_yf, (int)(d & 56u), 64);
                     return dc;
                 };
+                // (fbase >= 0 always holds; without the test hipcc emits a different loop, so it stays until that is measured)
                 for (int p0 = 0; p0 < ptot && fbase >= 0; p0 += 64) {
                     const Dec cur = decode(p0);
                     const bool live = cur.live;
@@ -1063,11 +993,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                     // lanes look at both halves; the SECOND half's lane emits the winner when both are candidates,
                     // a half whose partner is no candidate at this pixel emits itself.  (A partner that the pruning
                     // bounds kept out of the batch has no lane: it lies beyond every pixel's K nearest anyway.)
-#ifdef OCC_DBG2_NO_PAIR  // static instruction count of the main path only (scripts/dbg/loop_count.sh)
-                    if (false) {
-#else
                     if (__ballot(flags & (FLAG_PAIR_FIRST | FLAG_PAIR_SECOND))) {
-#endif
                         const bool is_first = (flags & FLAG_PAIR_FIRST) != 0, is_second = (flags & FLAG_PAIR_SECOND) != 0;
                         if ((is_first && j + 1 < n) || (is_second && j >= 1)) {
                             const float4* r1 = recs4 + (size_t)(is_first ? j + 1 : j - 1) * kRecParts;
@@ -1104,23 +1030,17 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         const bool acc = live && c1.cand && (!dense || key < pbnd);
                         const unsigned long long m = __ballot(acc);
                         if (m) {
-#ifndef OCC_DBG2_NO_LOG  // timing experiment only
                             if (acc && !nolog) {
                                 // 32-bit byte offsets from the wave-uniform bases (e < OCC_LOG_CAP): no 64-bit mad per lane
                                 const uint32_t e = (uint32_t)(nlog + lane_rank(m));
                                 if (OCC_BOUND(e < (uint32_t)OCC_LOG_CAP, 41, e, nlog)) {
                                     *reinterpret_cast<uint2*>(reinterpret_cast<char*>(lg.kt) + (e << 3)) =
                                         make_uint2(key, (uint32_t)pix | (uint32_t)(fseq_base + f) << 6);
-                                    // (the payload is read back for the kept entries only; writing it with the non-temporal hint:
-                                    // 1.990 vs 1.992 ms, nothing - round 4)
-#ifndef OCC_DBG2_NO_PAY  // timing experiment only: what the payload's 12 bytes per candidate cost (results are void)
+                                    // (the payload is read back for the kept entries only; a non-temporal hint: no gain, DESIGN_HISTORY.md H2)
                                     *reinterpret_cast<LogPay*>(reinterpret_cast<char*>(lg.pay) + __umul24(e, 12u)) = LogPay{c1.q, c1.ge, c1.ga};
-#endif
                                 }
                             }
-#endif
                             if (!nolog) nlog += __popcll(m);
-#ifndef OCC_DBG2_NO_ATOM  // timing experiment only
                             // accumulate: plain read-modify-write in sub-passes of four consecutive staged faces
                             const int f_first = __builtin_amdgcn_readfirstlane(f);
                             const int f_last = __builtin_amdgcn_readlane(f, nlive - 1);
@@ -1128,52 +1048,10 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                             // (one cross-lane read instead of redoing acc_slot's arithmetic), the copy adds a constant
                             const int slot = __shfl(myslot, pix, 64) + (int)__umul24((uint32_t)(f & (kCopies - 1)), (uint32_t)kAccStride);
                             const int grp = (f - f_first) >> kCopyBits;
-#ifdef OCC_EXP_ONE_SUBPASS  // timing experiment only (results void): every round applied in ONE sub-pass - the ceiling for more copies
-                            const int nsub = 1;
-#else
                             const int nsub = ((f_last - f_first) >> kCopyBits) + 1;
-#endif
-#ifdef OCC_DBG_STATS  // what more accumulator copies would buy: sub-passes per round with 4 / 5 / 6 / 8 copies
-                            {
-                                const int nf_ = f_last - f_first + 1;
-                                OCC_STAT(14, 1);  // rounds with at least one accepted pair
-                                OCC_STAT(15, (nf_ + 3) / 4);
-                                OCC_STAT(16, (nf_ + 4) / 5);
-                                OCC_STAT(17, (nf_ + 5) / 6);
-                                OCC_STAT(18, (nf_ + 7) / 8);
-                                OCC_STAT(19, nf_);
-                                // ... and if only the faces of ACCEPTED pairs counted (first to last accepted lane)
-                                const int fa_ = __builtin_amdgcn_readlane(f, __ffsll(m) - 1), fb_ = __builtin_amdgcn_readlane(f, 63 - __builtin_clzll(m));
-                                OCC_STAT(20, (fb_ - fa_ + 4) / 4);
-                                OCC_STAT(21, (fb_ - fa_ + 6) / 6);
-                                OCC_STAT(22, __popcll(m));  // accepted pairs
-                            }
-#endif
-#ifdef OCC_DBG_STATS  // exact conflict schedules (what a per-round rank by LDS atomics would give)
-                            {
-                                __shared__ uint32_t s_dbgrk[64];
-                                auto maxrank = [&](const bool on, const uint32_t k) {  // k < 256: counter (byte) index
-                                    s_dbgrk[lane] = 0u;
-                                    wave_lds_sync();
-                                    const uint32_t old = atomicAdd(&s_dbgrk[k >> 2], on ? 1u << (8u * (k & 3u)) : 0u);
-                                    wave_lds_sync();
-                                    const uint32_t rk = on ? (old >> (8u * (k & 3u))) & 255u : 0u;
-                                    return (int)wave_minmax_u32_dpp<true>(rk);
-                                };
-                                const uint32_t kc = (uint32_t)((f & 3) * 64 + pix), kp = (uint32_t)pix;
-                                OCC_STAT(23, maxrank(live, kc) + 1);          // copy = face & 3, schedule by rank among LIVE lanes of (pixel, copy)
-                                OCC_STAT(24, maxrank(acc, kc) + 1);           // ... among ACCEPTED lanes
-                                OCC_STAT(25, maxrank(live, kp) / 4 + 1);      // copy = rank & 3 among live lanes of the pixel
-                                OCC_STAT(26, maxrank(acc, kp) / 4 + 1);       // ... among accepted lanes (= arrival index)
-                            }
-#endif
                             auto subpasses = [&](auto with_bound) __attribute__((always_inline)) {
                                 for (int sp = 0; sp < nsub; ++sp) {
-#ifdef OCC_EXP_ONE_SUBPASS
-                                    if (acc) {
-#else
                                     if (acc && grp == sp) {
-#endif
                                         float4 a = s_acc[slot];
                                         a.x *= c1.q;
                                         if (GRAD) {
@@ -1190,9 +1068,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                             if (dense) subpasses(std::true_type{});
                             else subpasses(std::false_type{});
                             if (acc) kmx_lane = max(kmx_lane, key);
-#else
-                            asm volatile("" ::"v"(c1.q), "v"(c1.ge), "v"(c1.ga));
-#endif
                         }
                     }
                 }
@@ -1252,7 +1127,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
             }
 #endif
             bool selected = false;
-#ifndef OCC_DBG2_NO_SEL  // timing experiment only
             if (__ballot(ovf)) {
                 if (nolog) {  // cannot happen (the class bound counts every face that can reach the tile): say so loudly
                     if (lane == 0) atomicOr(&P.ws.status[eo / 3], OCC_STATUS_LIST_OVERFLOW);
@@ -1260,7 +1134,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                     selected = select_topk(std::false_type{});  // more than K candidates: keep the K nearest in z, A.4
                 }
             }
-#endif
             OCC_T(8);  // final selection
             OCC_T_ITEM(__ballot(ovf) != 0ull);
             float prod, sge, sga;

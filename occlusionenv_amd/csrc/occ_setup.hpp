@@ -120,8 +120,8 @@ __device__ __forceinline__ bool finish_tri(Tri& t, int S, float lim, float ifS) 
     // from the face's OWN box is farther than that from the triangle inside it: it can neither be inside nor within
     // the blur radius (relative margin 1e-3 on the squared distance against the rounding of either side).  Bits 28..31
     // of bbox.y: corner (xl, yl), (xh, yl), (xl, yh), (xh, yh) can be skipped; occ_raster2_kernel leaves those (face,
-    // pixel) pairs out of its rounds (6 % of the rounds of the bench's sub-pixel faces; the exact point-triangle
-    // distance per corner finds 2 % more and costs the setup kernel 0.6 ms: measured, not kept).
+    // pixel) pairs out of its rounds (6 % of the rounds of the bench's sub-pixel faces; an exact point-triangle distance
+    // per corner: not kept, DESIGN_HISTORY.md H4).
     uint32_t corner = 0u;
 #ifndef OCC_NO_CORNER_CUT  // (the A/B build of tests/test_gpu_parity.py: results must not change by a bit)
     {
@@ -507,13 +507,10 @@ __device__ __attribute__((noinline)) int clip_face_slow(const int* __restrict__ 
 constexpr int kSetupTB = OCC_SETUP_TB;  // threads per block of the setup kernel (one block per (env, object))
 constexpr int kHalfPad = 5;             // 16-byte parts of a staging slot: parts 0..4 of a record, then its three tangent parts (an odd
                                         // stride: the lanes' 16-byte stores fall on different banks)
-// BLOCK SIZE AND LDS (round 4).  Sixteen waves per CU either way (<= 128 VGPRs); the block size decides how many waves
-// share ONE copy of the object's vertices.  Round 3: 256-thread blocks, four to a CU with 40 KB each - whole records
-// staged (9 KB per wave), no room for the vertices (31 KB for a 2 562-vertex mesh: with them only two blocks fitted and
-// the kernel got 18 % slower, although at EQUAL residency the LDS vertices beat the global gathers by 13 %).  Now a
-// record is staged in two pieces through a five-part slot (5 KB per wave), and two 512-thread blocks per CU hold their
-// vertices in 78 KB each.  Measured on one box (step minus raster, us; scripts/ab_toggle.py): 256 threads / global
-// gathers 800, 256 / LDS (two blocks per CU) 880, 512 / global 818, 512 / LDS 786, 1024 / global 914, 1024 / LDS 880.
+// BLOCK SIZE AND LDS.  Sixteen waves per CU either way (<= 128 VGPRs); the block size decides how many waves share ONE
+// copy of the object's vertices (31 KB for a 2 562-vertex mesh).  A record is staged in two pieces through a five-part
+// slot (5 KB per wave), so that two 512-thread blocks per CU hold their vertices in 78 KB each.  (Other block sizes, with
+// and without LDS vertices, were measured slower: DESIGN_HISTORY.md H4.)
 template <bool GRAD, int TB>
 __global__ __launch_bounds__(TB, 4) void occ_setup_kernel(OccScene sc, const float* __restrict__ cam, OccWorkspace ws, int vcap) {
     constexpr int W = TB / 64;  // waves per block
@@ -642,12 +639,8 @@ __global__ __launch_bounds__(TB, 4) void occ_setup_kernel(OccScene sc, const flo
         const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
         const int pre = __popcll(m1 & lt) + __popcll(m2 & lt);
         if (lane == 0) s_wcnt[round][wave] = __popcll(m1) + __popcll(m2);
-#ifdef OCC_SETUP_FULL_BARRIER  // (A/B build)
-        __syncthreads();
-#else
         // (only the wave counts cross this barrier, through LDS: no need to wait for the round's record stores to land)
         block_lds_barrier();
-#endif
         int woff = 0, itot = 0;
         if (W <= 4) {
 #pragma unroll

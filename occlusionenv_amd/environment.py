@@ -38,8 +38,8 @@ from .spaces import Box
 _SCENE_RNG = np.random.default_rng()
 
 #: scenes containing a mesh with more faces than this are drawn again (the reference: 250 000,
-#: environment.py:296-298).  Every (env, object) slot of the render workspace holds records for the largest mesh in
-#: the pool, so lowering this bounds the memory of runs on datasets with a few huge models.
+#: environment.py:296-298).  Every (env, object) slot of the render workspace holds records for its own mesh
+#:, so lowering this bounds the memory a scene with a few huge models can ask for.
 MAX_MESH_FACES = int(os.environ.get("OCC_MAX_MESH_FACES", 250000))
 _OVERSIZE = set()  # (dataset token, model index) of models found to exceed it
 _DS_TOKENS: Dict[int, tuple] = {}  # id(dataset) -> (weak reference, token)

@@ -1,5 +1,5 @@
 """Diagnostic (GPU box): shader cycles per phase of occ_raster2_kernel from an OCC_DBG_TIME build.
-   OCC_HIP_LIB=build/dbg2/libocc_time.so python scripts/dbg/phase_time.py [envs]"""
+   scripts/build_variant.sh time -DOCC_DBG_TIME && OCC_HIP_LIB=build/ab/libocc_time.so python scripts/dbg/phase_time.py [envs]"""
 import ctypes, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

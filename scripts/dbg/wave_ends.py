@@ -1,5 +1,6 @@
 """Diagnostic (GPU box): when the waves of occ_raster2_kernel finish - from an OCC_DBG_ENDS build (plain stores, no atomics:
-the launch runs at production speed).    OCC_HIP_LIB=build/ab/libocc_ends.so python scripts/dbg/wave_ends.py [envs]"""
+the launch runs at production speed).
+   scripts/build_variant.sh ends -DOCC_DBG_ENDS && OCC_HIP_LIB=build/ab/libocc_ends.so python scripts/dbg/wave_ends.py [envs]"""
 import ctypes, os, sys
 import numpy as np
 import torch
