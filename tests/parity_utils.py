@@ -61,6 +61,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tests.dense_meshes import DENSE_KINDS  # noqa: E402
+
 TOL = 1e-4          # BASELINE.json north_star: "within 1e-4 fp32"
 TZ_REL = 1e-6       # two depths closer than this (relative, ~8 ulp at z = 4) can swap order
 TB_REL = 1e-4       # |dist - blur| <= TB_REL * blur: membership of the blur disc can flip
@@ -111,6 +113,16 @@ def make_case(n_env, seed, mesh="teapot", az_range=0.6, pool=None, device="cuda"
         offsets[:, 1, 0], offsets[:, 1, 2] = x2, 1.0
         offsets[:, 2, 0], offsets[:, 2, 2] = -x2, 2.0
         return dict(pool=pool, mesh_ids=mesh_ids, offsets=offsets, az=az, actions=actions)
+    elif mesh in DENSE_KINDS:
+        # dense meshes and exact-count sheets (tests/dense_meshes.py): fixed mesh slots and offsets per kind
+        from tests.dense_meshes import dense_layout, dense_pool_meshes
+
+        ids = [pool.add(v, f, key=("dense", mesh, i)) for i, (v, f) in enumerate(dense_pool_meshes(mesh))]
+        x2 = torch.randn(n_env, generator=g)
+        az = (torch.rand(n_env, generator=g) * 2 - 1) * az_range
+        actions = torch.randn(n_env, 2, generator=g)
+        slots, offsets = dense_layout(mesh, n_env, x2)
+        return dict(pool=pool, mesh_ids=torch.tensor(ids)[slots], offsets=offsets, az=az, actions=actions)
     else:
         n_models, mixed = (8, True) if mesh == "mixed" else (6, False)
         ds = SyntheticShapeNet(n_models=n_models, seed=1234 + seed, mixed=mixed, textured=(mesh == "textured"))
@@ -142,12 +154,14 @@ def oracle_env(case, i, img, shader="flat", faces_per_pixel=100):
 
 
 def run_engine(case, img, n_env=None, faces_per_pixel=100, radius=4.0, pixel_weight=None, render_too=False, shader="flat",
-               cost_order=True):
+               cost_order=True, setup_vertex_lds=None):
     from occlusionenv_amd import _native as nat
     from occlusionenv_amd.engine import OcclusionEngine
 
     n = n_env or case["mesh_ids"].shape[0]
     eng = OcclusionEngine(case["pool"], n, img, faces_per_pixel=faces_per_pixel, cost_order=cost_order)
+    if setup_vertex_lds is not None:  # False: the setup kernel gathers every vertex from global memory
+        eng.setup_vertex_lds = bool(setup_vertex_lds)
     eng.shader = {"flat": nat.SHADER_FLAT, "hard_phong": nat.SHADER_HARD_PHONG, "soft_phong": nat.SHADER_SOFT_PHONG}[shader]
     eng.set_scene(list(range(n)), case["mesh_ids"][:n], case["offsets"][:n])
     if pixel_weight is not None:
@@ -447,11 +461,12 @@ HAIR = "face visible / culled by a hair (area ~ kEpsilon)"
 REASON_LOG = None  # diagnostics (scripts/dbg): set to a list to collect (kind, obj, y, x, reasons) of every explained pixel
 
 
-def _classify(env, got_alphas, or_alphas, got_obs, or_obs, S, K, textured, decisions=None, records=None):
+def _classify(env, got_alphas, or_alphas, got_obs, or_obs, S, K, textured, decisions=None, records=None, hair_pixels=None):
     """Pixels beyond tolerance -> (tie mask (S,S) bool, list of unexplained (kind, obj, y, x, err)).  ``decisions`` (a
     set) collects what max_tie_pixels bounds: one entry per tie pixel, except that the pixels whose reason is the
     visibility of a needle face share one entry per such face (its whole blur footprint flips with it), and the pixels
-    whose only reason is the equal distance of the two halves of a z-clipped pair one entry per pair."""
+    whose only reason is the equal distance of the two halves of a z-clipped pair one entry per pair.  ``hair_pixels``
+    (a set) collects the (y, x) of the pixels counted through needle faces."""
     ties = torch.zeros(S, S, dtype=torch.bool)
     unexplained = []
     decisions = set() if decisions is None else decisions
@@ -476,6 +491,8 @@ def _classify(env, got_alphas, or_alphas, got_obs, or_obs, S, K, textured, decis
                 decisions.add(("upstream", o, y, x))
             elif HAIR in why:
                 decisions.update(("face", o, f) for f in hf)
+                if hair_pixels is not None:
+                    hair_pixels.add((y, x))
             elif why == [PAIR]:
                 decisions.update(("pair", o, f) for f in pf)
             else:
@@ -497,6 +514,8 @@ def _classify(env, got_alphas, or_alphas, got_obs, or_obs, S, K, textured, decis
             if REASON_LOG is not None:
                 REASON_LOG.append(("obs", -1, y, x, tuple(why)))
             decisions.update(("face", -1, f) for f in hf) if HAIR in why else decisions.add(("pixel", y, x))
+            if HAIR in why and hair_pixels is not None:
+                hair_pixels.add((y, x))
         else:
             unexplained.append(("obs", -1, y, x, float(dob[y, x])))
     return ties, unexplained
@@ -518,19 +537,20 @@ def run_parity_case(n_env=2, img=64, seed=0, mesh="teapot", az_range=0.6, check_
     envs = list(check_envs if check_envs is not None else range(n_env))
     textured = mesh == "textured"
     orc, weights, unexplained, n_ties, n_dec, n_up = {}, torch.ones(n_env, S, S), [], 0, 0, 0
+    n_hair, n_other, n_cov = 0, 0, 0
     for i in envs:
-        dec = set()
+        dec, hpx = set(), set()
         env = oracle_env(case, i, img, shader, faces_per_pixel)
         obs0 = env.reset(radius=radius, azimuth=float(case["az"][i]))
         al0 = torch.stack([im[0, ..., 3] for im in env.alphas]).detach()
         img0 = env.image.detach()
         t0, u0 = _classify(env, got["alphas0"][i], al0, got["obs0"][i], obs0[0].detach(), S, K, textured, dec,
-                         records=got["records0"][3 * i: 3 * i + 3])
+                         records=got["records0"][3 * i: 3 * i + 3], hair_pixels=hpx)
         a = case["actions"][i].clone().requires_grad_(True)
         obs, reward, done, info = env.step(a)
         al = torch.stack([im[0, ..., 3] for im in env.alphas]).detach()
         t1, u1 = _classify(env, got["alphas"][i], al, got["obs"][i], obs[0].detach(), S, K, textured, dec,
-                         records=got["records"][3 * i: 3 * i + 3])
+                         records=got["records"][3 * i: 3 * i + 3], hair_pixels=hpx)
         rnd = None
         if check_render:
             rimg, rdepth = env.render()
@@ -541,6 +561,11 @@ def run_parity_case(n_env=2, img=64, seed=0, mesh="teapot", az_range=0.6, check_
         n_ties = max(n_ties, int(ties.sum()))
         n_dec = max(n_dec, sum(1 for d in dec if d[0] != "upstream"))
         n_up = max(n_up, sum(1 for d in dec if d[0] == "upstream"))
+        # the same decisions split by kind: tie pixels counted through needle faces, every other decision, and the pixels
+        # any object covers (oracle alpha > 0, reset or step) - reported, not bounded here (violations)
+        n_hair = max(n_hair, len(hpx))
+        n_other = max(n_other, sum(1 for d in dec if d[0] in ("pixel", "pair")))
+        n_cov = max(n_cov, int(((al0 > 0).any(0) | (al > 0).any(0)).sum()))
         orc[i] = dict(env=env, obs0=obs0[0].detach(), al0=al0, img0=img0, a=a, obs=obs[0].detach(), al=al, ties=ties,
                       t0=t0, t1=t1, render=rnd)
     if n_ties:  # leave the tie pixels out of the loss on the GPU side too
@@ -549,7 +574,8 @@ def run_parity_case(n_env=2, img=64, seed=0, mesh="teapot", az_range=0.6, check_
         got_w = got
     res = dict(obs_maxabs=0.0, obs0_maxabs=0.0, alpha_maxabs=0.0, alpha0_maxabs=0.0, fs_maxabs=0.0, loss_rel=0.0,
                loss0_rel=0.0, reward_abs=0.0, grad_rel=0.0, grad_excess=0.0, grad_arbiter=[], render_maxabs=0.0,
-               tie_pixels=n_ties, tie_decisions=n_dec, upstream_pixels=n_up, fs_arith=0.0, unexplained=unexplained, img=img)
+               tie_pixels=n_ties, tie_decisions=n_dec, upstream_pixels=n_up, fs_arith=0.0, unexplained=unexplained, img=img,
+               tie_hair_pixels=n_hair, tie_other_decisions=n_other, covered_pixels=n_cov)
     for i in envs:
         o = orc[i]
         env, keep0, keep1, keep = o["env"], ~o["t0"], ~o["t1"], ~o["ties"]
