@@ -173,8 +173,14 @@ class OcclusionEngine:
     def set_norm_with_object_size(self, env_id: int, on: bool) -> None:
         on = bool(on)
         if self._norm_host[env_id] != on:
+            first = on and not self._norm_host.any()
             self._norm_host[env_id] = on
             self.norm_flags[env_id] = int(on)
+            if first and self.R:
+                # while no env had the flag, nothing kept _res_objsum: the slots that are READY now were stored without
+                # their sum.  Their alphas rows still hold that render (READY rows are not rendered again), so compute it
+                # for every slot here; from now on auto_reset keeps the PENDING slots' sums current
+                self._object_sum(self._alphas_all[self.N:], out=self._res_objsum)
 
     def _object_sum(self, alphas: torch.Tensor, gate=None, gate_value=0, out=None) -> torch.Tensor:
         """sum_px (a1 + a2 + a3)^2 per row of ``alphas`` (n,3,S,S) (environment.py:320,324; occ_object_mass)."""
