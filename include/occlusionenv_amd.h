@@ -23,6 +23,8 @@
  *   - SimpleVecEnv.step_wait's per-step host hand-off and auto-reset (SubProcVecEnv.py:209-218)
  *                                                                   -> occ_step_flags, occ_reset_commit,
  *                                                                      occ_auto_reset, occ_reserve_refill
+ *   - the frozen FullNetwork / PredictorNet encoder whose pooled feature PPO.select_action stores (PPO.py:47,152-162,
+ *     model.py:88-101,142-164), inference only                     -> occ_encoder_forward
  *
  * Conventions: plain pointers and sizes only; every pointer is DEVICE memory owned by the
  * caller (PyTorch's ROCm allocator in the Python host); calls are asynchronous on `stream`
@@ -41,7 +43,7 @@
 extern "C" {
 #endif
 
-#define OCC_ABI_VERSION 9
+#define OCC_ABI_VERSION 10
 
 /* return codes */
 #define OCC_OK 0
@@ -347,6 +349,41 @@ int occ_ppo_update(const float* feats, const float* actions, const float* old_lo
  * feats (n,256) in the order of adaptive_avg_pool2d(obs, 8).reshape(n, 256).  img: a multiple of 8.
  */
 int occ_pool8(const float* obs, int64_t n, int img, float* feats, void* stream);
+
+/*
+ * Frozen encoder (model.py:8-101, eval mode): Encoder(ch=8, levels=5, layers=2, k=3, dilation, bias=True, residual,
+ * separable) on obs (n_env,4,S,S) f32 -> feats (n_env,256) = AdaptiveAvgPool2d(1) of the last down output.  The skip
+ * outputs and the decoder are not computed.  Layers: initial Conv(4 -> 8, dilation 1); per level i (c = 8 * 2^i) Layer 1
+ * and Layer 2 Conv(c -> c, dilation), y = Layer2(Layer1(x)) (+ x if residual), down = dense 3x3 stride-2 Conv(c -> 2c,
+ * dilation 1).  Every Conv is bn(relu(conv(x))) with BN folded to a per-channel affine: scale = gamma / sqrt(var + 1e-5),
+ * shift = beta - mean * scale.  Spatial sizes halve with ceiling at every down (100 -> 50 -> 25 -> 13 -> 7 -> 4).
+ * f32 arithmetic with f32 accumulation; no atomics (features are bitwise independent of n_env and of an env's position);
+ * 17 launches on `stream`, nothing allocated or synchronised (capturable).
+ *
+ * Packed weights (occ_encoder_packed_floats floats), layers in the order initial, then per level Layer 1, Layer 2, down;
+ * per layer, in the order the kernels read them:
+ *   separable Conv(cin -> cout):  dw_v[cin][3] (the (3,1) depthwise taps, top to bottom) | dw_h[cin][3] (the (1,3) taps,
+ *                                 left to right) | pw[cin][cout] (pointwise weight, TRANSPOSED) | bias[cout] |
+ *                                 bn_scale[cout] | bn_shift[cout]
+ *   dense Conv(cin -> cout):      w[cin][ky * 3 + kx][cout] (TRANSPOSED conv weight) | bias[cout] | bn_scale[cout] |
+ *                                 bn_shift[cout]
+ * The down convs are always dense; `separable` selects the form of the initial layer and of Layers 1 and 2.
+ */
+#define OCC_ENCODER_FEATURES 256
+typedef struct OccEncoderConfig {
+    int32_t img;       /* S, in [32, 1024] */
+    int32_t dilation;  /* 1 or 2: dilation of Layers 1 and 2 (padding = dilation) */
+    int32_t residual;  /* 0 / 1: ConvBlock.residual */
+    int32_t separable; /* 0 / 1 */
+} OccEncoderConfig;
+/* Floats of the packed weight buffer for cfg->separable (independent of the other fields); -1 for a bad config. */
+int64_t occ_encoder_packed_floats(const OccEncoderConfig* cfg);
+/* Device workspace bytes occ_encoder_forward needs for n_env envs: three (n_env,8,S,S) f32 activation buffers and the
+ * per-tile partials of the pooled feature. */
+int occ_encoder_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* bytes);
+/* n_env in [1, 65535]; ws of at least the queried bytes (256-byte aligned). */
+int occ_encoder_forward(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
+                        size_t ws_bytes, float* feats, void* stream);
 
 /*
  * Host hand-off of SimpleVecEnv.step_wait (SubProcVecEnv.py:209-218): one int32 buffer

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OCC_HIP_LIB") or os.path.join(_HERE, "libocc_hip.so")
 
 # layout constants (must match include/occlusionenv_amd.h)
-ABI_VERSION = 9
+ABI_VERSION = 10
 CAM_STRIDE = 48
 REC_STRIDE = 32
 TILE = 8
@@ -152,6 +152,14 @@ class OccReserveStore(C.Structure):
 
 RS_EMPTY, RS_PENDING, RS_READY = 0, 1, 2
 
+
+class OccEncoderConfig(C.Structure):
+    """include/occlusionenv_amd.h: OccEncoderConfig (the frozen encoder of occ_encoder_forward)."""
+    _fields_ = [("img", C.c_int32), ("dilation", C.c_int32), ("residual", C.c_int32), ("separable", C.c_int32)]
+
+
+ENCODER_FEATURES = 256
+
 #: every symbol include/occlusionenv_amd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "occ_abi_version": (C.c_int, []),
@@ -188,6 +196,10 @@ SYMBOLS = {
     "occ_object_mass": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "occ_reserve_refill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "occ_encoder_packed_floats": (C.c_int64, [C.POINTER(OccEncoderConfig)]),
+    "occ_encoder_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t)]),
+    "occ_encoder_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p]),
     "occ_profile_enable": (C.c_int, [C.c_int]),
     "occ_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

@@ -27,6 +27,9 @@
 // second pass over the K-buffer, no atomics into grad_face_verts and no saved fragments.  It
 // equals what autograd + _C.rasterize_meshes_backward produce.
 //
+//   occ_enc_*_kernel    the frozen encoder of the PPO features (occ_encoder.hpp): fused separable layer, dense 3x3
+//                       conv, last down fused with the average pool
+//
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
 #include <hip/hip_runtime.h>
@@ -49,6 +52,7 @@ namespace occ {
 #include "occ_reset.hpp"
 #include "occ_oplevel.hpp"
 #include "occ_ppo.hpp"
+#include "occ_encoder.hpp"
 
 }  // namespace occ
 
@@ -587,5 +591,35 @@ extern "C" int occ_step_finish(const float* loss, const float* grad_elaz, const 
     if (!loss || !cam || !full_reward || !object_mass || !reward || !done || n_env <= 0) return OCC_ERR_ARG;
     hipLaunchKernelGGL(occ_finish_kernel, dim3((n_env + 63) / 64), dim3(64), 0, (hipStream_t)stream, loss, grad_elaz, cam,
                        full_reward, object_mass, reward, done, grad_action, n_env);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+static bool enc_cfg_ok(const OccEncoderConfig* c) {
+    return c && c->img >= 32 && c->img <= 1024 && (c->dilation == 1 || c->dilation == 2) && (c->residual == 0 || c->residual == 1) &&
+           (c->separable == 0 || c->separable == 1);
+}
+
+extern "C" int64_t occ_encoder_packed_floats(const OccEncoderConfig* cfg) {
+    if (!cfg || (cfg->separable != 0 && cfg->separable != 1)) return -1;
+    return enc_packed_floats(cfg->separable != 0);
+}
+
+extern "C" int occ_encoder_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* bytes) {
+    if (!enc_cfg_ok(cfg) || n_env <= 0 || !bytes) return OCC_ERR_ARG;
+    size_t buf, part;
+    enc_ws_layout(cfg->img, n_env, &buf, &part);
+    *bytes = 3 * buf + part;
+    return OCC_OK;
+}
+
+extern "C" int occ_encoder_forward(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
+                                   size_t ws_bytes, float* feats, void* stream) {
+    static_assert(kEncFeat == OCC_ENCODER_FEATURES, "occ_encoder.hpp and the header disagree");
+    if (!enc_cfg_ok(cfg) || !packed_weights || !obs || n_env <= 0 || n_env > 65535 || !ws || !feats) return OCC_ERR_ARG;
+    size_t need = 0;
+    occ_encoder_workspace_query(cfg, n_env, &need);
+    if (ws_bytes < need) return OCC_ERR_ARG;
+    enc_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, packed_weights, obs, n_env, (char*)ws, feats,
+                (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }

@@ -1,5 +1,5 @@
-"""Harness counterparts of the reference's callers of the hot path -- NOT a port of
-PPO.py / trainRL.py (out of scope), only the loops that drive ``step()`` and consume its outputs:
+"""Harness counterparts of the reference's callers of the hot path -- the loops that drive
+``step()`` and consume its outputs (the PPO learner is ``ppo.BatchedPPO``, the frozen encoder ``encoder.FrozenEncoder``):
 
   * ``gradient_ascent``  -- demo.py:80-114 / iterator.py:112-138: ``action = nn.Parameter(zeros(2))``,
     ``reward.backward()``, skip NaN gradients, ``action += lr * action.grad``.
@@ -39,7 +39,8 @@ def gradient_ascent(env, steps: int = 20, lr: float = 0.01, reset_kwargs: Option
 
 def gaussian_policy(std: float = 0.6) -> Callable:
     """Stand-in for ActorCritic.act (PPO.py:62-80): diagonal Gaussian around a linear read-out of the pooled
-    features; returns (action, logprob).  The real actor is the frozen FullNetwork encoder + a linear head."""
+    features; returns (action, logprob).  The reference's actor is the frozen FullNetwork encoder + a linear head:
+    ``encoder.FrozenEncoder`` and ``ppo.BatchedPPO.from_fullnetwork``."""
     w = None
 
     def act(features: torch.Tensor):

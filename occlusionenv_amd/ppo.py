@@ -10,7 +10,9 @@ Here the buffer is the (T, N, 261) rollout-record tensor of ``rollout.pack_recor
 reward | done), every env is its own trajectory, and the update is one batched pass over T*N samples.  With several
 GPUs every rank all-gathers the records (``rollout.all_gather_records``) and runs the SAME update on the same
 data with the same seed: the learner is replicated, no gradient collective is needed (the heads are 771 floats).
-The encoder itself is out of scope: ``rollout.pooled_features`` stands in for it.
+The features come from ``encoder``: ``BatchedPPO.from_fullnetwork`` runs the reference's frozen FullNetwork encoder
+natively (``encoder.FrozenEncoder``) and starts the heads from the checkpoint's; without an encoder
+``rollout.pooled_features`` (8x8 average pooling) stands in for it.
 
 On the GPU the K epochs of an update run in the library (``occ_ppo_update``, csrc/occ_ppo.hpp): one launch per epoch
 does forward, loss, backward and the Adam step over the 771 parameters (80 epochs over 12 800 samples: 1.3 ms instead
@@ -93,7 +95,8 @@ class BatchedPPO:
                  graph_epochs: bool = True, fused: Optional[bool] = None, encoder=None):
         """``encoder``: any callable obs (N,4,S,S) -> features (N,256), run under no_grad - the socket for the frozen
         encoder whose pooled features the reference stores (PPO.py:47,155-157: ``FullNetwork.forward``'s first output,
-        model.py:157-166).  Default: ``rollout.pooled_features`` (8x8 average pooling: the network is out of scope)."""
+        model.py:157-166), e.g. ``encoder.FrozenEncoder`` (``from_fullnetwork``).  Default: ``rollout.pooled_features``
+        (8x8 average pooling)."""
         self.encoder = encoder
         self.gamma, self.eps_clip, self.K_epochs = gamma, eps_clip, K_epochs
         self.action_std = action_std_init
@@ -125,6 +128,30 @@ class BatchedPPO:
                                      step=torch.zeros(1, **f32), scratch=torch.empty(nat.ppo_scratch_floats(), **f32),
                                      counter=torch.zeros(1, dtype=torch.int32, device=dev))
         self.records = []  # list of (N_total, 261) tensors, one per step
+
+    @classmethod
+    def from_fullnetwork(cls, sd_or_module, dilation: Optional[int] = None, residual: Optional[bool] = None,
+                         max_chunk: int = 256, **kw) -> "BatchedPPO":
+        """The reference's agent (PPO.py:47-48): a FullNetwork checkpoint (state dict, or the module itself) gives the
+        frozen encoder (``encoder.FrozenEncoder``, preset "ppo") and the initial action / value heads of ``policy`` and
+        ``policy_old`` (model.py:153-154,168-171).  ``kw``: the other BatchedPPO arguments (device default "cuda")."""
+        from .encoder import FrozenEncoder
+
+        kw.setdefault("device", "cuda")
+        if isinstance(sd_or_module, nn.Module):
+            enc = FrozenEncoder.from_module(sd_or_module, device=kw["device"], max_chunk=max_chunk)
+        else:
+            enc = FrozenEncoder.from_state_dict(sd_or_module, "ppo", dilation, residual, device=kw["device"], max_chunk=max_chunk)
+        if set(enc.heads) != {"action_head", "value_head"}:
+            raise ValueError("the checkpoint has no action_head / value_head")
+        agent = cls(encoder=enc, **kw)
+        with torch.no_grad():
+            for pol in (agent.policy, agent.policy_old):
+                for name, (w, b) in enc.heads.items():
+                    head = getattr(pol, name)
+                    head.weight.copy_(w.to(torch.float32))
+                    head.bias.copy_(b.to(torch.float32))
+        return agent
 
     # ---- acting (PPO.py:152-164) ------------------------------------------------------------
     def select_action(self, obs: torch.Tensor, generator: Optional[torch.Generator] = None):

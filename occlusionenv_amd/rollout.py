@@ -26,8 +26,9 @@ def env_shard(n_total: int, rank: int, world: int):
 
 
 def pooled_features(obs: torch.Tensor) -> torch.Tensor:
-    """Stand-in for the frozen encoder's 256-d pooled feature (PPO.py:155-157 takes FullNetwork features;
-    the network itself is out of scope): 4 channels x 8x8 adaptive average pool."""
+    """Stand-in for the frozen encoder's 256-d pooled feature (PPO.py:155-157 takes FullNetwork features; the native
+    encoder is ``encoder.FrozenEncoder``, used by ``ppo.BatchedPPO.from_fullnetwork``): 4 channels x 8x8 adaptive average
+    pool, the default of ``BatchedPPO()`` and of bench.py's rollout."""
     if obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 4 and obs.shape[1] == 4 and obs.shape[2] == obs.shape[3] \
             and obs.shape[2] % 8 == 0:
         # one pass at memory speed in the library (csrc/occ_ppo.hpp: occ_pool8_kernel); no fallback if it is missing
