@@ -3,7 +3,9 @@
 GPU.  Config 5 gathers 2 048 envs x T = 50 = 102 400 samples on every rank of an 8-GPU node (PPO.py:196-217 runs its 80
 epochs over the whole buffer); one rank alone has 12 800.
 
-  python scripts/ppo_learner_scale.py [lib=path[:max_blocks]] ...   -> JSON on stdout
+  python scripts/ppo_learner_scale.py [name=path] ...   -> JSON on stdout   (default: head=occlusionenv_amd/libocc_hip.so)
+
+The scratch of every run is sized from the block cap of the library it loaded (occ_ppo_max_blocks).
 """
 import ctypes as C
 import json
@@ -26,7 +28,7 @@ def load(path):
     return lib
 
 
-def run(lib, max_blocks, M, epochs=80, reps=5):
+def run(lib, M, epochs=80, reps=5):
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     feats = torch.rand(M, 256, device=dev, generator=g)
@@ -36,7 +38,7 @@ def run(lib, max_blocks, M, epochs=80, reps=5):
     P = lambda *shape: (torch.randn(*shape, device=dev, generator=g) * 0.05).contiguous()  # noqa: E731
     w_a, b_a, w_v, b_v = P(2, 256), P(2), P(1, 256), P(1)
     m, v, step = torch.zeros(771, device=dev), torch.zeros(771, device=dev), torch.zeros(1, device=dev)
-    scratch = torch.empty(max_blocks * 773, device=dev)
+    scratch = torch.empty(int(lib.occ_ppo_max_blocks()) * (nat.PPO_PARAMS + 2), device=dev)
     counter = torch.zeros(1, dtype=torch.int32, device=dev)
     losses = torch.empty(epochs, 2, device=dev)
     ps = nat.OccPpoState()
@@ -62,15 +64,14 @@ def run(lib, max_blocks, M, epochs=80, reps=5):
 
 
 def main():
-    specs = sys.argv[1:] or ["head=occlusionenv_amd/libocc_hip.so:64"]
+    specs = sys.argv[1:] or ["head=occlusionenv_amd/libocc_hip.so"]
     out = []
     for spec in specs:
         name, rest = spec.split("=", 1)
-        path, _, mb = rest.partition(":")
-        lib = load(path)
+        lib = load(rest)
         for M in (12800, 25600, 51200, 102400):
-            ms = run(lib, int(mb or 64), M)
-            out.append(dict(variant=name, max_blocks=int(mb or 64), samples=M, epochs=80, update_ms=ms, us_per_epoch=ms / 80 * 1e3,
+            ms = run(lib, M)
+            out.append(dict(variant=name, max_blocks=int(lib.occ_ppo_max_blocks()), samples=M, epochs=80, update_ms=ms, us_per_epoch=ms / 80 * 1e3,
                             feature_GBps=M * 1024 * 80 / (ms * 1e-3) / 1e9))
             print(out[-1], file=sys.stderr, flush=True)
     print(json.dumps(out, indent=1))
