@@ -25,6 +25,9 @@
  *                                                                      occ_auto_reset, occ_reserve_refill
  *   - the frozen FullNetwork / PredictorNet encoder whose pooled feature PPO.select_action stores (PPO.py:47,152-162,
  *     model.py:88-101,142-164), inference only                     -> occ_encoder_forward
+ *   - the segmentation decoder of the same network (model.py:25-33,52-67,109-166: the predicted occlusion map, the third
+ *     output of FullNetwork.forward / the output of Segmenter.forward), inference only, and the accuracy / IoU counts
+ *     the pretrainer judges it by (pretrainer.py:127-141)          -> occ_segment_forward, occ_seg_metrics
  *
  * Conventions: plain pointers and sizes only; every pointer is DEVICE memory owned by the
  * caller (PyTorch's ROCm allocator in the Python host); calls are asynchronous on `stream`
@@ -43,7 +46,7 @@
 extern "C" {
 #endif
 
-#define OCC_ABI_VERSION 10
+#define OCC_ABI_VERSION 11
 
 /* return codes */
 #define OCC_OK 0
@@ -384,6 +387,45 @@ int occ_encoder_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* 
 /* n_env in [1, 65535]; ws of at least the queried bytes (256-byte aligned). */
 int occ_encoder_forward(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
                         size_t ws_bytes, float* feats, void* stream);
+
+/*
+ * Segmentation decoder (model.py:109-125 on top of the encoder above, eval mode): x = the last down output
+ * (n_env,256,S/32,S/32); for j = 0..4, c = 128, 64, 32, 16, 8: x = up_j(x) + skip, where up_j = TrConv(2c -> c) =
+ * bn(relu(ConvTranspose2d(2c, c, 3, stride 2, padding 1, output_padding 1))) (BN folded as above) and skip is the
+ * encoder's feature of level 4 - j: Layer 2's output plus the residual when cfg->residual, the tensor the down conv reads.
+ * Then logit = Conv2d(8, 1, 1)(x), prob = sigmoid(logit), both (n_env,1,S,S).  TrConvBlock.forward returns self.up(x)
+ * (model.py:63-67): the `net` layers of the decoder blocks have no effect on the output, are not run and are not packed.
+ * The skip add needs S % 32 == 0 (so does the reference).
+ *
+ * Packed decoder (occ_decoder_packed_floats floats): per up layer j, in decoder order,
+ *   w[ci][ky * 3 + kx][co] (ConvTranspose2d weight (2c, c, 3, 3) with co moved last) | bias[c] | bn_scale[c] | bn_shift[c]
+ * then the classifier: cls_w[8] | cls_b[1].
+ *
+ * occ_segment_forward runs the encoder (the same 17 launches on the same values: feats is bitwise what
+ * occ_encoder_forward writes) keeping the five skip tensors and the last down output, then 5 decoder launches; the
+ * classifier and the sigmoid are fused into the last.  22 launches on `stream`, nothing allocated or synchronised.
+ * Workspace: two (n_env,8,S,S) activation buffers, the skips (1.94 such buffers), the last down output and the pool
+ * partials: 3.97 buffers against the encoder's 3, i.e. 7.94 MiB per env at 256^2 and 31.75 MiB per env at 512^2
+ * (256 envs x 256^2 or 64 envs x 512^2: 1.98 GiB).
+ */
+/* Floats of the packed decoder (the same for every valid cfg); -1 for a null cfg or a bad `separable`. */
+int64_t occ_decoder_packed_floats(const OccEncoderConfig* cfg);
+/* As occ_encoder_workspace_query; additionally cfg->img % 32 must be 0. */
+int occ_segment_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* bytes);
+/* feats (n_env,256) and prob (n_env,1,S,S) are required; logit (n_env,1,S,S) and dec_feat (n_env,8,S,S), the input of the
+ * classifier, may be NULL and are then not stored.  Map pointers 8-byte aligned.  OCC_ERR_ARG before any launch for a null
+ * required pointer, cfg->img % 32 != 0, n_env outside [1, 65535] or a short workspace. */
+int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                        int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* logit, float* dec_feat,
+                        void* stream);
+/*
+ * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
+ * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
+ * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)
+ * image).  Integer sums: the result does not depend on scheduling.  counts is cleared on `stream` first.
+ */
+int occ_seg_metrics(const float* pred, const float* target, int target_stride, int n_env, int img, int64_t* counts,
+                    void* stream);
 
 /*
  * Host hand-off of SimpleVecEnv.step_wait (SubProcVecEnv.py:209-218): one int32 buffer

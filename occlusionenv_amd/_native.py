@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OCC_HIP_LIB") or os.path.join(_HERE, "libocc_hip.so")
 
 # layout constants (must match include/occlusionenv_amd.h)
-ABI_VERSION = 10
+ABI_VERSION = 11
 CAM_STRIDE = 48
 REC_STRIDE = 32
 TILE = 8
@@ -200,6 +200,11 @@ SYMBOLS = {
     "occ_encoder_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t)]),
     "occ_encoder_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p]),
+    "occ_decoder_packed_floats": (C.c_int64, [C.POINTER(OccEncoderConfig)]),
+    "occ_segment_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t)]),
+    "occ_segment_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_size_t] + [C.c_void_p] * 5),
+    "occ_seg_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "occ_profile_enable": (C.c_int, [C.c_int]),
     "occ_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

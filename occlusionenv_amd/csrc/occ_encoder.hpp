@@ -14,7 +14,8 @@
 //   occ_enc_dense_kernel  dense 3x3 Conv, stride 1 or 2, dilation 1 or 2, + bias, ReLU, BN affine (+ residual): the
 //                         down convs and the dense layers of the "predictor" preset.  POOL = true (the last down): the
 //                         output is not stored; each block writes the per-channel sum over its tile's pixels (a fixed
-//                         sequential order) to a partials row instead.
+//                         sequential order) to a partials row instead.  KEEP = true (occ_segment_forward) stores the
+//                         output as well, from the same registers: the partials do not change by a bit.
 //   occ_enc_pool_kernel   per (env, channel) one fixed-order sum of the tile partials / (Ho * Wo).
 //
 // A thread owns one output pixel and COG output channels; a block is a T x T pixel tile times NG channel groups (one
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void occ_enc_sep_kernel(const float* __restric
     }
 }
 
-template <int T, int COG, bool POOL>
+template <int T, int COG, bool POOL, bool KEEP = false>
 __global__ __launch_bounds__(256) void occ_enc_dense_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                             const float* __restrict__ resid, const float* __restrict__ w,
                                                             int cin, int cout, int H, int W, int Ho, int Wo, int stride,
@@ -185,6 +186,9 @@ __global__ __launch_bounds__(256) void occ_enc_dense_kernel(const float* __restr
             float v = fmaxf(acc[j] + bias[co], 0.f);
             v = fmaf(v, bns[co], bnt[co]);
             s[(g * COG + j) * TT + p] = valid ? v : 0.f;
+            if constexpr (KEEP) {
+                if (valid) y[((size_t)blockIdx.z * cout + co) * oplane + (size_t)oy * Wo + ox] = v;
+            }
         }
         __syncthreads();
         if (tid < ng * COG) {
@@ -270,14 +274,18 @@ static void enc_launch_sep(const float* x, float* y, const float* resid, const f
 
 template <int T>
 static void enc_launch_dense_t(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int stride,
-                               int d, int n, float* partials, hipStream_t st) {
+                               int d, int n, float* partials, bool keep, hipStream_t st) {
     const int Ho = enc_out_size(H, stride);
     const int cog = enc_cog(cout), ng = enc_groups(T, cout);
     const int tiles_x = (Ho + T - 1) / T;
     const dim3 grid(tiles_x * tiles_x, cout / (cog * ng), n), block(T * T * ng);
     if (partials) {  // the last down: cout = 256
-        hipLaunchKernelGGL((occ_enc_dense_kernel<T, 32, true>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho, stride,
-                           d, tiles_x, partials);
+        if (keep)
+            hipLaunchKernelGGL((occ_enc_dense_kernel<T, 32, true, true>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho,
+                               stride, d, tiles_x, partials);
+        else
+            hipLaunchKernelGGL((occ_enc_dense_kernel<T, 32, true>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho,
+                               stride, d, tiles_x, partials);
         return;
     }
     switch (cog) {
@@ -291,20 +299,29 @@ static void enc_launch_dense_t(const float* x, float* y, const float* resid, con
 }
 
 static void enc_launch_dense(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int stride,
-                             int d, int n, float* partials, hipStream_t st) {
-    if (enc_tile(enc_out_size(H, stride)) == 16) enc_launch_dense_t<16>(x, y, resid, w, cin, cout, H, stride, d, n, partials, st);
-    else enc_launch_dense_t<8>(x, y, resid, w, cin, cout, H, stride, d, n, partials, st);
+                             int d, int n, float* partials, hipStream_t st, bool keep = false) {
+    if (enc_tile(enc_out_size(H, stride)) == 16) enc_launch_dense_t<16>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st);
+    else enc_launch_dense_t<8>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st);
 }
 
 // The whole encoder on n envs: 17 launches (the initial layer, two layers and a down per level, the pool).
+// keep = null (occ_encoder_forward): ws holds b0, b1, b2 and the partials.  keep = the five skip tensors and the last
+// down output (occ_segment_forward, occ_decoder.hpp): ws holds b0, b1 and the partials; every level's Layer 2 writes its
+// skip tensor instead of b2 and the last down also stores its output.  The same kernels run on the same values in the
+// same order either way, so the pooled feature is the same to the bit.
+struct EncKeep {
+    float* skip[kEncLevels];  // (n, 8 << lv, S >> lv, S >> lv): Layer 2 (+ residual), what the down conv reads
+    float* last;              // (n, 256, S / 32, S / 32)
+};
+
 static void enc_forward(int img, int dil, bool residual, bool separable, const float* packed, const float* obs, int n, char* ws,
-                        float* feats, hipStream_t st) {
+                        float* feats, hipStream_t st, const EncKeep* keep = nullptr) {
     size_t buf_bytes, part_bytes;
     enc_ws_layout(img, n, &buf_bytes, &part_bytes);
     float* b0 = (float*)ws;
     float* b1 = (float*)(ws + buf_bytes);
-    float* b2 = (float*)(ws + 2 * buf_bytes);
-    float* part = (float*)(ws + 3 * buf_bytes);
+    float* b2 = keep ? nullptr : (float*)(ws + 2 * buf_bytes);
+    float* part = (float*)(ws + (keep ? 2 : 3) * buf_bytes);
     const float* w = packed;
     int H = img;
     // initial: Conv(4 -> 8) with dilation 1 (model.py:92)
@@ -313,6 +330,7 @@ static void enc_forward(int img, int dil, bool residual, bool separable, const f
     w += enc_layer_floats(4, kEncCh, separable);
     for (int lv = 0; lv < kEncLevels; ++lv) {
         const int c = kEncCh << lv;
+        if (keep) b2 = keep->skip[lv];
         // Layer 1: b0 -> b1; Layer 2: b1 (+ b0) -> b2; down: b2 -> b0 (or the partials of the pooled feature)
         if (separable) enc_launch_sep(b0, b1, nullptr, w, c, c, H, dil, n, st);
         else enc_launch_dense(b0, b1, nullptr, w, c, c, H, 1, dil, n, nullptr, st);
@@ -321,7 +339,8 @@ static void enc_forward(int img, int dil, bool residual, bool separable, const f
         else enc_launch_dense(b1, b2, residual ? b0 : nullptr, w, c, c, H, 1, dil, n, nullptr, st);
         w += enc_layer_floats(c, c, separable);
         const bool last = lv == kEncLevels - 1;
-        enc_launch_dense(b2, b0, nullptr, w, c, 2 * c, H, 2, 1, n, last ? part : nullptr, st);
+        enc_launch_dense(b2, last && keep ? keep->last : b0, nullptr, w, c, 2 * c, H, 2, 1, n, last ? part : nullptr, st,
+                         last && keep);
         w += enc_layer_floats(c, 2 * c, false);
         H = enc_out_size(H, 2);
     }

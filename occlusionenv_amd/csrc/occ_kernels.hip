@@ -29,6 +29,8 @@
 //
 //   occ_enc_*_kernel    the frozen encoder of the PPO features (occ_encoder.hpp): fused separable layer, dense 3x3
 //                       conv, last down fused with the average pool
+//   occ_dec_up_kernel   the segmentation decoder of the same network (occ_decoder.hpp): transposed conv + skip add per
+//                       launch, classifier and sigmoid fused into the last; occ_seg_metrics_kernel: accuracy / IoU counts
 //
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
@@ -53,6 +55,7 @@ namespace occ {
 #include "occ_oplevel.hpp"
 #include "occ_ppo.hpp"
 #include "occ_encoder.hpp"
+#include "occ_decoder.hpp"
 
 }  // namespace occ
 
@@ -621,5 +624,45 @@ extern "C" int occ_encoder_forward(const OccEncoderConfig* cfg, const float* pac
     if (ws_bytes < need) return OCC_ERR_ARG;
     enc_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, packed_weights, obs, n_env, (char*)ws, feats,
                 (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- segmentation decoder (occ_decoder.hpp) ----------------------------------------------------------------------------
+extern "C" int64_t occ_decoder_packed_floats(const OccEncoderConfig* cfg) {
+    if (!cfg || (cfg->separable != 0 && cfg->separable != 1)) return -1;
+    return dec_packed_floats();  // the up layers are dense transposed convs whatever the encoder's form
+}
+
+extern "C" int occ_segment_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* bytes) {
+    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || n_env <= 0 || !bytes) return OCC_ERR_ARG;
+    *bytes = seg_ws_layout(cfg->img, n_env).total;
+    return OCC_OK;
+}
+
+extern "C" int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                                   int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* logit, float* dec_feat,
+                                   void* stream) {
+    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || !enc_packed || !dec_packed || !obs || n_env <= 0 || n_env > 65535 || !ws ||
+        !feats || !prob)
+        return OCC_ERR_ARG;
+    // the quad rows are stored as float2
+    if ((((uintptr_t)ws | (uintptr_t)prob | (uintptr_t)logit | (uintptr_t)dec_feat) & 7) != 0) return OCC_ERR_ARG;
+    size_t need = 0;
+    occ_segment_workspace_query(cfg, n_env, &need);
+    if (ws_bytes < need) return OCC_ERR_ARG;
+    seg_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, obs, n_env, (char*)ws,
+                feats, prob, logit, dec_feat, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_seg_metrics(const float* pred, const float* target, int target_stride, int n_env, int img, int64_t* counts,
+                               void* stream) {
+    if (!pred || !target || !counts || target_stride < 1 || n_env <= 0 || n_env > 65535 || img < 1 || img > 1024)
+        return OCC_ERR_ARG;
+    const int npix = img * img;
+    if (hipMemsetAsync(counts, 0, (size_t)n_env * 3 * sizeof(int64_t), (hipStream_t)stream) != hipSuccess) return OCC_ERR_LAUNCH;
+    hipLaunchKernelGGL(occ_seg_metrics_kernel, dim3((npix + kSegMetricsPerBlock - 1) / kSegMetricsPerBlock, n_env),
+                       dim3(kSegMetricsBlock), 0, (hipStream_t)stream, pred, target, target_stride, npix,
+                       (unsigned long long*)counts);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }

@@ -12,6 +12,14 @@ Presets (model.py: a state dict stores neither the dilation nor the residual fla
   ``"ppo"``        FullNetwork(8, dilation=2, separable=True), residual=True, keys ``encoder.*`` (PPO.py:47, test.py)
   ``"predictor"``  PredictorNet(8): dense 3x3, dilation 1, no residual, keys ``features.*`` (train_predict.py:27)
 
+  ``"segmenter"``  Segmenter(8): dense 3x3, dilation 1, residual=True, keys ``encoder.*``, ``decoder.features.*``,
+                   ``classifier.*``; no grad head (train_segm.py:28)
+
+The segmentation decoder (csrc/occ_decoder.hpp; model.py:109-125,147-150) is picked up when its keys are in the state dict
+(``enc.has_decoder``): ``enc.segment(obs)`` is the predicted occlusion map, ``enc.forward_full(obs)`` the triple of
+``FullNetwork.forward`` from one pass over the encoder, ``enc.occlusion_metrics(pred, target)`` the accuracy / IoU counts
+of pretrainer.py:127-141.
+
 Whole-module checkpoints (``torch.save(model)``, as pretrainer.py writes them) need the reference's ``model.py`` to
 unpickle; with it on the path use ``FrozenEncoder.from_module(torch.load(path, weights_only=False))``.
 """
@@ -32,6 +40,12 @@ PRESETS = {
     # name: (key prefix, grad head, tanh on the grad head, dilation, residual)
     "ppo": ("encoder.", "gradPredictor.", False, 2, True),
     "predictor": ("features.", "output.", True, 1, False),
+    "segmenter": ("encoder.", None, False, 1, True),
+}
+# name: (key prefix of Decoder.features, key prefix of the 1x1 classifier); "predictor" has no decoder
+DECODER_KEYS = {
+    "ppo": ("segmenter.0.features.", "segmenter.1."),
+    "segmenter": ("decoder.features.", "classifier."),
 }
 
 
@@ -119,6 +133,46 @@ def pack_state_dict(sd, prefix: str):
     return separable, torch.cat(parts).to(torch.float32).numpy(), offsets
 
 
+def decoder_plan():
+    """[(index j in Decoder.features, cin = 2c, cout = c)] in packed (= decoder) order: c = 128, 64, 32, 16, 8."""
+    return [(j, 2 * (CH << (LEVELS - 1 - j)), CH << (LEVELS - 1 - j)) for j in range(LEVELS)]
+
+
+def decoder_packed_floats() -> int:
+    return sum(9 * cin * cout + 3 * cout for _, cin, cout in decoder_plan()) + CH + 1
+
+
+def pack_decoder(sd, prefix: str, classifier: str):
+    """Parse, check and fold the decoder of a state dict -> packed f32 numpy buffer (include/occlusionenv_amd.h).
+
+    Only the ``up`` TrConv of every block is read: TrConvBlock.forward returns ``self.up(x)`` and discards what its
+    ``net`` layers computed (model.py:63-67), so ``{prefix}{j}.net.*`` keys are neither needed nor used."""
+    stems = [k[len(prefix):] for k in sd if k.startswith(prefix)]
+    if not stems:
+        raise ValueError(f"decoder state dict: no key starts with {prefix!r}")
+    levels = {int(m.group(1)) for s in stems for m in [re.match(r"(\d+)\.", s)] if m}
+    if levels != set(range(LEVELS)):
+        raise ValueError(f"decoder state dict: levels {sorted(levels)}; only levels=5 matches the encoder's five skips")
+    parts = []
+    for j, cin, cout in decoder_plan():
+        stem = f"{prefix}{j}.up."
+        wkey = stem + "conv.weight"
+        if wkey not in sd:
+            raise ValueError(f"decoder state dict: missing key {wkey!r}")
+        w = torch.as_tensor(sd[wkey])
+        if w.dim() == 4 and (w.shape[0] != cin or w.shape[1] != cout):
+            raise ValueError(f"decoder state dict: {wkey!r} maps {w.shape[0]} -> {w.shape[1]} channels, expected {cin} -> {cout} "
+                             "(only ch=8, levels=5 is supported)")
+        w = _get(sd, wkey, (cin, cout, 3, 3))  # ConvTranspose2d: input channels first
+        bias = _get(sd, stem + "conv.bias", (cout,))
+        scale, shift = fold_bn(sd, stem, cout)
+        parts += [w.permute(0, 2, 3, 1).reshape(-1), bias, scale, shift]
+    parts += [_get(sd, classifier + "weight", (1, CH, 1, 1)).reshape(-1), _get(sd, classifier + "bias", (1,))]
+    buf = torch.cat(parts).to(torch.float32).numpy()
+    assert buf.size == decoder_packed_floats()
+    return buf
+
+
 class FrozenEncoder:
     """Native inference of the frozen encoder: ``enc(obs)`` (N,4,S,S) f32 on the GPU -> (N,256) f32 pooled features,
     the callable ``BatchedPPO(encoder=...)`` takes; ``enc.predict_grad(obs)`` -> (N,2) from the grad head.
@@ -127,7 +181,7 @@ class FrozenEncoder:
     every env's features are computed independently, so the chunking changes no bit."""
 
     def __init__(self, packed: np.ndarray, separable: bool, dilation: int, residual: bool, preset: str, grad_head=None,
-                 heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None):
+                 heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None, decoder=None):
         if dilation not in (1, 2):
             raise ValueError(f"dilation must be 1 or 2, got {dilation}")
         if int(max_chunk) < 1:
@@ -152,37 +206,62 @@ class FrozenEncoder:
             self.grad_b = grad_head[1].to(self.device, torch.float32).contiguous()
         self.heads = heads or {}
         self._ws = {}
+        self.dec_packed_host = self.dec_packed = None
+        if decoder is not None:
+            self.dec_packed_host = np.ascontiguousarray(decoder, dtype=np.float32)
+            if lib.occ_decoder_packed_floats(C.byref(cfg)) != self.dec_packed_host.size:
+                raise nat.NativeError("packed decoder weights do not match the library's layout")
+            self.dec_packed = torch.from_numpy(self.dec_packed_host).to(self.device)
+        self._seg_ws = {}
+
+    @property
+    def has_decoder(self) -> bool:
+        """Whether the checkpoint held the segmentation decoder (``segment`` / ``forward_full`` need it)."""
+        return self.dec_packed is not None
 
     # ---- construction ------------------------------------------------------------------------------------------
     @classmethod
     def from_state_dict(cls, sd, preset: str = "ppo", dilation: Optional[int] = None, residual: Optional[bool] = None,
                         device="cuda", max_chunk: int = 256) -> "FrozenEncoder":
-        """A ``FullNetwork`` (preset "ppo") or ``PredictorNet`` (preset "predictor") state dict.  The dilation and the
-        residual flag are not in a state dict: they come from the preset unless given."""
+        """A ``FullNetwork`` (preset "ppo"), ``PredictorNet`` (preset "predictor") or ``Segmenter`` (preset "segmenter")
+        state dict.  The dilation and the residual flag are not in a state dict: they come from the preset unless given.
+        The segmentation decoder is loaded when its keys are there (``has_decoder``)."""
         if preset not in PRESETS:
             raise ValueError(f"unknown preset {preset!r}; one of {sorted(PRESETS)}")
+        if preset == "segmenter" and any(k.startswith(("segmenter.0.", "gradPredictor.")) for k in sd):
+            # both networks keep their encoder under "encoder.": without this a FullNetwork would load with the Segmenter's
+            # dilation and without its decoder
+            raise ValueError("state dict holds FullNetwork keys ('segmenter.0.*' / 'gradPredictor.*'): unknown preset "
+                             "'segmenter' for such a checkpoint, use preset='ppo'")
         prefix, ghead, _tanh, d0, r0 = PRESETS[preset]
         separable, packed, offsets = pack_state_dict(sd, prefix)
+        decoder = None
+        if preset in DECODER_KEYS:
+            dprefix, dcls = DECODER_KEYS[preset]
+            if any(k.startswith(dprefix) or k.startswith(dcls) for k in sd):
+                decoder = pack_decoder(sd, dprefix, dcls)
         grad_head = None
-        if ghead + "weight" in sd:
+        if ghead is not None and ghead + "weight" in sd:
             grad_head = (_get(sd, ghead + "weight", (2, FEATURES)), _get(sd, ghead + "bias", (2,)))
         heads = {}
         for name, rows in (("action_head.", 2), ("value_head.", 1)):
             if name + "weight" in sd:
                 heads[name[:-1]] = (_get(sd, name + "weight", (rows, FEATURES)), _get(sd, name + "bias", (rows,)))
         return cls(packed, separable, d0 if dilation is None else int(dilation), r0 if residual is None else bool(residual),
-                   preset, grad_head, heads, device, max_chunk, offsets)
+                   preset, grad_head, heads, device, max_chunk, offsets, decoder)
 
     @classmethod
     def from_module(cls, m, device="cuda", max_chunk: int = 256) -> "FrozenEncoder":
-        """A ``FullNetwork`` or ``PredictorNet`` module: dilation and residual are read from the module (the dilation of
-        the first block's Layer 1 conv, ``ConvBlock.residual``)."""
+        """A ``FullNetwork``, ``PredictorNet`` or ``Segmenter`` module: dilation and residual are read from the module
+        (the dilation of the first block's Layer 1 conv, ``ConvBlock.residual``)."""
         if hasattr(m, "encoder") and hasattr(m, "gradPredictor"):
             preset, enc = "ppo", m.encoder
+        elif hasattr(m, "encoder") and hasattr(m, "decoder") and hasattr(m, "classifier"):
+            preset, enc = "segmenter", m.encoder
         elif hasattr(m, "features") and hasattr(m, "output"):
             preset, enc = "predictor", m.features
         else:
-            raise ValueError("from_module expects a FullNetwork or a PredictorNet")
+            raise ValueError("from_module expects a FullNetwork, a PredictorNet or a Segmenter")
         block = enc.features[0]
         conv = block.net[0].conv
         dil = conv[0].dilation[0] if isinstance(conv, torch.nn.Sequential) else conv.dilation[0]
@@ -249,3 +328,120 @@ class FrozenEncoder:
             raise ValueError("this checkpoint has no gradPredictor / output head")
         g = torch.addmm(self.grad_b, self(obs), self.grad_w.t())
         return torch.tanh(g) if self.grad_tanh else g
+
+    # ---- segmentation decoder --------------------------------------------------------------------------------------
+    def _seg_workspace(self, n: int, img: int):
+        key = (n, img)
+        ws = self._seg_ws.get(key)
+        if ws is None:
+            nbytes = C.c_size_t()
+            nat.check(nat.load().occ_segment_workspace_query(C.byref(self._cfg(img)), n, C.byref(nbytes)),
+                      "occ_segment_workspace_query")
+            ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+            self._seg_ws[key] = ws
+        return ws
+
+    def _segment(self, obs: torch.Tensor, want_logits: bool, want_features: bool):
+        """-> (pooled (N,256), prob (N,1,S,S), logits or None, decoder feature (N,8,S,S) or None): one occ_segment_forward
+        per chunk on the caller's stream."""
+        if not isinstance(obs, torch.Tensor) or not obs.is_cuda:
+            raise nat.NativeError("FrozenEncoder needs CUDA/ROCm tensors; there is no CPU fallback")
+        if not self.has_decoder:
+            raise ValueError("this checkpoint has no segmentation decoder (no 'segmenter.0.features.*' / 'decoder.features.*' keys)")
+        if obs.dim() != 4 or obs.shape[1] != 4 or obs.shape[2] != obs.shape[3]:
+            raise ValueError(f"obs must be (N,4,S,S), got {tuple(obs.shape)}")
+        if obs.device != self.packed.device:
+            raise ValueError(f"obs is on {obs.device}, the encoder's weights on {self.packed.device}")
+        img = int(obs.shape[2])
+        if not 32 <= img <= 1024 or img % 32 != 0:
+            raise ValueError(f"image side {img}: the decoder's skip additions need a multiple of 32 in [32, 1024]")
+        obs = obs.detach().to(torch.float32).contiguous()
+        n_all = int(obs.shape[0])
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=obs.device)  # noqa: E731
+        feats, prob = new(n_all, FEATURES), new(n_all, 1, img, img)
+        logits = new(n_all, 1, img, img) if want_logits else None
+        dfeat = new(n_all, CH, img, img) if want_features else None
+        if n_all == 0:
+            return feats, prob, logits, dfeat
+        lib = nat.load()
+        cfg = self._cfg(img)
+        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        pix = 4 * img * img  # bytes of one f32 map
+
+        def at(t, lo, per_env_bytes):
+            return C.c_void_p(t.data_ptr() + lo * per_env_bytes) if t is not None else None
+
+        for lo in range(0, n_all, self.max_chunk):
+            n = min(self.max_chunk, n_all - lo)
+            ws = self._seg_workspace(n, img)
+            nat.check(lib.occ_segment_forward(C.byref(cfg), C.c_void_p(self.packed.data_ptr()), C.c_void_p(self.dec_packed.data_ptr()),
+                                              at(obs, lo, 4 * pix), n, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                              at(feats, lo, 4 * FEATURES), at(prob, lo, pix), at(logits, lo, pix),
+                                              at(dfeat, lo, CH * pix), stream),
+                      "occ_segment_forward")
+        return feats, prob, logits, dfeat
+
+    @torch.no_grad()
+    def segment(self, obs: torch.Tensor, return_logits: bool = False, return_features: bool = False):
+        """The predicted occlusion map ``sigmoid(segmenter(encoder(obs)))`` (model.py:159), (N,1,S,S) f32; S a multiple of
+        32.  With ``return_features`` the (N,8,S,S) decoder feature comes first, as in ``Segmenter.forward`` (model.py:
+        135-140): ``(features, predictions)``; with ``return_logits`` the classifier's output before the sigmoid comes last."""
+        _f, prob, logits, dfeat = self._segment(obs, return_logits, return_features)
+        out = ((dfeat,) if return_features else ()) + (prob,) + ((logits,) if return_logits else ())
+        return out[0] if len(out) == 1 else out
+
+    @torch.no_grad()
+    def forward_full(self, obs: torch.Tensor):
+        """``FullNetwork.forward`` (model.py:156-166) from one pass over the encoder: (pooled (N,256), segm (N,1,S,S),
+        grad (N,2)).  The pooled feature is bitwise ``self(obs)``."""
+        if self.grad_w is None:
+            raise ValueError("this checkpoint has no gradPredictor / output head")
+        feats, prob, _l, _d = self._segment(obs, False, False)
+        g = torch.addmm(self.grad_b, feats, self.grad_w.t())
+        return feats, prob, (torch.tanh(g) if self.grad_tanh else g)
+
+    @torch.no_grad()
+    def occlusion_metrics(self, pred: torch.Tensor, target: torch.Tensor) -> dict:
+        """The judgement of pretrainer.py:133-141 on a batch: both maps thresholded at 0.5; per-env int64 counts
+        ``correct`` (pixels where they agree), ``intersection``, ``union`` on the device, and over the whole batch
+        ``accuracy`` = sum(correct) / pixels and ``iou`` = sum(intersection) / sum(union) as 0-d f64 tensors (0 / 0 = nan,
+        as in the reference).  pred (N,1,S,S) or (N,S,S); target likewise, any float tensor; a strided view such as
+        ``full_state[..., 3]`` is read in place."""
+        c = seg_counts(pred, target)
+        total = c.sum(0).to(torch.float64)
+        n, img = int(c.shape[0]), int(pred.shape[-1])
+        return dict(correct=c[:, 0], intersection=c[:, 1], union=c[:, 2], accuracy=total[0] / float(n * img * img),
+                    iou=total[1] / total[2])
+
+
+def _maps(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise nat.NativeError("occlusion_metrics needs CUDA/ROCm tensors; there is no CPU fallback")
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or t.shape[1] != t.shape[2]:
+        raise ValueError(f"{what} must be (N,S,S) or (N,1,S,S), got {tuple(t.shape)}")
+    return t if t.dtype == torch.float32 else t.to(torch.float32)
+
+
+def seg_counts(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """(N,3) int64 on the device: per env #(p == t), #(p and t), #(p or t) with p = pred > 0.5, t = target > 0.5
+    (occ_seg_metrics)."""
+    pred, target = _maps(pred, "pred").contiguous(), _maps(target, "target")
+    if pred.shape != target.shape or pred.device != target.device:
+        raise ValueError(f"pred {tuple(pred.shape)} on {pred.device} and target {tuple(target.shape)} on {target.device} differ")
+    n, img = int(pred.shape[0]), int(pred.shape[1])
+    if img > 1024:
+        raise ValueError(f"image side {img} above 1024")
+    counts = torch.empty(n, 3, dtype=torch.int64, device=pred.device)
+    if n == 0:
+        return counts
+    k = target.stride(2)
+    if not (k >= 1 and target.stride(1) == k * img and target.stride(0) == k * img * img):
+        target, k = target.contiguous(), 1
+    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+    for lo in range(0, n, 65535):
+        m = min(65535, n - lo)
+        nat.check(nat.load().occ_seg_metrics(C.c_void_p(pred[lo:].data_ptr()), C.c_void_p(target[lo:].data_ptr()), int(k), m, img,
+                                             C.c_void_p(counts[lo:].data_ptr()), stream), "occ_seg_metrics")
+    return counts

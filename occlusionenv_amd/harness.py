@@ -6,6 +6,9 @@
   * ``collect_rollout``  -- trainRL.py:189-229 + PPO.py:152-164 in batched form: T steps of a policy over N envs,
     one rollout record per env-step (256 pooled features, action, logprob, reward, done = 1044 B) and one
     all-gather of the records per step when torch.distributed is initialised (rollout.py).
+  * ``evaluate_segmentation`` -- the measuring half of pretrainer.py:176-189 (``val``) against the live environment
+    instead of a stored dataset: the predicted occlusion map of a FullNetwork checkpoint against the occlusion image
+    every step renders anyway.
 """
 from __future__ import annotations
 
@@ -73,3 +76,31 @@ def collect_rollout(venv, T: int = 50, policy: Optional[Callable] = None, with_g
         rec = rollout.pack_records(obs, action, logprob, rewards, dones)
         recs.append(rollout.all_gather_records(rec))
     return dict(records=torch.stack(recs), action_grads=torch.stack(grads) if grads else None, obs=obs)
+
+
+@torch.no_grad()
+def evaluate_segmentation(venv, enc, steps: int, policy: Optional[Callable] = None) -> dict:
+    """``steps`` batched steps of ``venv``; every step's observation goes through ``enc.forward_full`` and the predicted
+    occlusion map is judged against the step's own occlusion image, the alpha channel of ``full_state`` (what
+    dataset_io.py writes as the pretrainer's target), as pretrainer.py:133-141 judges it: both thresholded at 0.5, counts
+    summed over everything seen.  ``policy(pooled) -> (action, logprob)`` chooses the actions (default: zeros).  Returns
+    accuracy and IoU in percent, as the reference prints them, and the raw counts; one host sync, at the end."""
+    obs = venv.reset()
+    n = int(obs.shape[0])
+    totals = torch.zeros(3, dtype=torch.int64, device=obs.device)
+    pixels = 0
+    action = torch.zeros(n, 2, device=obs.device)
+    for _ in range(int(steps)):
+        obs, _rewards, _dones, infos = venv.step(action)
+        obs = obs[:, 0] if obs.dim() == 5 else obs
+        occl = torch.cat([infos[i]["full_state"] for i in range(n)])[..., 3]
+        pooled, segm, _grad = enc.forward_full(obs)
+        m = enc.occlusion_metrics(segm, occl)
+        totals += torch.stack([m["correct"].sum(), m["intersection"].sum(), m["union"].sum()])
+        pixels += occl.numel()
+        if policy is not None:
+            action = policy(pooled)[0].detach()
+    correct, inter, union = (int(v) for v in totals.tolist())
+    return dict(accuracy=100.0 * correct / pixels if pixels else float("nan"),
+                iou=100.0 * inter / union if union else float("nan"), correct=correct, intersection=inter, union=union,
+                pixels=pixels)
