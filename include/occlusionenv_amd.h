@@ -28,6 +28,9 @@
  *   - the segmentation decoder of the same network (model.py:25-33,52-67,109-166: the predicted occlusion map, the third
  *     output of FullNetwork.forward / the output of Segmenter.forward), inference only, and the accuracy / IoU counts
  *     the pretrainer judges it by (pretrainer.py:127-141)          -> occ_segment_forward, occ_seg_metrics
+ *   - the pretrainer's segmentation criterion on that map (pretrainer.py:89,127-141,176-189; loss.py:24-39
+ *     BinaryDiceLoss, nn.BCELoss): the sums of both losses and the counts in one read, and the gradient with respect to the
+ *     prediction                                                   -> occ_seg_criterion, occ_seg_criterion_grad
  *
  * Conventions: plain pointers and sizes only; every pointer is DEVICE memory owned by the
  * caller (PyTorch's ROCm allocator in the Python host); calls are asynchronous on `stream`
@@ -46,7 +49,7 @@
 extern "C" {
 #endif
 
-#define OCC_ABI_VERSION 11
+#define OCC_ABI_VERSION 12
 
 /* return codes */
 #define OCC_OK 0
@@ -426,6 +429,36 @@ int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, co
  */
 int occ_seg_metrics(const float* pred, const float* target, int target_stride, int n_env, int img, int64_t* counts,
                     void* stream);
+
+/*
+ * The pretrainer's segmentation criterion (pretrainer.py:89: BinaryDiceLoss() or nn.BCELoss(); :127-141 and :176-189: the
+ * loss and the accuracy / IoU lines) from ONE read of pred and target.  pred, target, target_stride, n_env and img as for
+ * occ_seg_metrics (same limits, same status returns); target may be soft, in [0,1].  Per env, with p = pred, t = target:
+ *   sums[env] = { sum p t, sum p^2, sum t^2, sum -(t max(log p, -100) + (1 - t) max(log(1 - p), -100)) }   (double)
+ * the first three being what loss.py:29-30 sums for p = 2, the fourth nn.BCELoss's per-pixel term with its clamp;
+ *   counts[env] = the three int64 counts of occ_seg_metrics, bit-identical; counts may be NULL.
+ * BinaryDiceLoss per env = 1 - (sums[0] + smooth) / (sums[1] + sums[2] + smooth); BCELoss = sum_env sums[3] / (n img^2).
+ * No floating-point atomics and a fixed summation order, every addition in f64: sums[env] is bitwise independent of n_env,
+ * of the env's position, of how a caller splits the batch over calls, and of the run.  scratch: device memory of
+ * occ_seg_criterion_scratch_bytes(n_env, img) bytes (8-byte aligned; the per-block partial sums), 0 for bad arguments.
+ * Two launches (and the clearing of counts) on `stream`.
+ */
+size_t occ_seg_criterion_scratch_bytes(int n_env, int img);
+int occ_seg_criterion(const float* pred, const float* target, int target_stride, int n_env, int img, double* sums,
+                      int64_t* counts, void* scratch, void* stream);
+/*
+ * The criterion's gradient with respect to pred, elementwise; grad_pred (n_env,img,img) f32 is overwritten.
+ *   OCC_CRITERION_DICE: grad = coef[env][0] t + coef[env][1] p.  With num = sums[0] + smooth, den = sums[1] + sums[2] +
+ *     smooth and u the upstream gradient of the env's loss 1 - num / den (reduction folded in): coef = { -u / den,
+ *     2 u num / den^2 }.
+ *   OCC_CRITERION_BCE: grad = coef[env][0] (p - t) / max(p (1 - p), 1e-12), the backward rule of nn.BCELoss;
+ *     coef[env][0] = upstream / (n img^2), coef[env][1] is not read.
+ * coef is (n_env,2) double on the device.  One launch.
+ */
+#define OCC_CRITERION_DICE 0
+#define OCC_CRITERION_BCE 1
+int occ_seg_criterion_grad(const float* pred, const float* target, int target_stride, int n_env, int img, int mode,
+                           const double* coef, float* grad_pred, void* stream);
 
 /*
  * Host hand-off of SimpleVecEnv.step_wait (SubProcVecEnv.py:209-218): one int32 buffer

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OCC_HIP_LIB") or os.path.join(_HERE, "libocc_hip.so")
 
 # layout constants (must match include/occlusionenv_amd.h)
-ABI_VERSION = 11
+ABI_VERSION = 12
 CAM_STRIDE = 48
 REC_STRIDE = 32
 TILE = 8
@@ -159,6 +159,7 @@ class OccEncoderConfig(C.Structure):
 
 
 ENCODER_FEATURES = 256
+CRITERION_DICE, CRITERION_BCE = 0, 1
 
 #: every symbol include/occlusionenv_amd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -205,6 +206,11 @@ SYMBOLS = {
     "occ_segment_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_size_t] + [C.c_void_p] * 5),
     "occ_seg_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "occ_seg_criterion_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "occ_seg_criterion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "occ_seg_criterion_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "occ_profile_enable": (C.c_int, [C.c_int]),
     "occ_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

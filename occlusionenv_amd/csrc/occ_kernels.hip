@@ -31,6 +31,8 @@
 //                       conv, last down fused with the average pool
 //   occ_dec_up_kernel   the segmentation decoder of the same network (occ_decoder.hpp): transposed conv + skip add per
 //                       launch, classifier and sigmoid fused into the last; occ_seg_metrics_kernel: accuracy / IoU counts
+//   occ_seg_criterion_* the pretrainer's criterion on that map (occ_criterion.hpp): Dice / BCE sums and the counts in one
+//                       read, fixed-order f64 sums, and the gradient with respect to the prediction
 //
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
@@ -56,6 +58,7 @@ namespace occ {
 #include "occ_ppo.hpp"
 #include "occ_encoder.hpp"
 #include "occ_decoder.hpp"
+#include "occ_criterion.hpp"
 
 }  // namespace occ
 
@@ -664,5 +667,40 @@ extern "C" int occ_seg_metrics(const float* pred, const float* target, int targe
     hipLaunchKernelGGL(occ_seg_metrics_kernel, dim3((npix + kSegMetricsPerBlock - 1) / kSegMetricsPerBlock, n_env),
                        dim3(kSegMetricsBlock), 0, (hipStream_t)stream, pred, target, target_stride, npix,
                        (unsigned long long*)counts);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- pretrainer criterion (occ_criterion.hpp) ----------------------------------------------------------------------------
+static bool crit_args_ok(const void* pred, const void* target, int target_stride, int n_env, int img) {
+    return pred && target && target_stride >= 1 && n_env > 0 && n_env <= 65535 && img >= 1 && img <= 1024;
+}
+
+extern "C" size_t occ_seg_criterion_scratch_bytes(int n_env, int img) {
+    if (n_env <= 0 || n_env > 65535 || img < 1 || img > 1024) return 0;
+    return (size_t)n_env * crit_blocks(img * img) * 4 * sizeof(double);
+}
+
+extern "C" int occ_seg_criterion(const float* pred, const float* target, int target_stride, int n_env, int img, double* sums,
+                                 int64_t* counts, void* scratch, void* stream) {
+    if (!crit_args_ok(pred, target, target_stride, n_env, img) || !sums || !scratch || ((uintptr_t)scratch & 7) != 0)
+        return OCC_ERR_ARG;
+    const int npix = img * img;
+    hipStream_t st = (hipStream_t)stream;
+    if (counts && hipMemsetAsync(counts, 0, (size_t)n_env * 3 * sizeof(int64_t), st) != hipSuccess) return OCC_ERR_LAUNCH;
+    crit_launch(pred, target, target_stride, n_env, npix, (double*)scratch, (unsigned long long*)counts, st);
+    hipLaunchKernelGGL(occ_seg_criterion_final_kernel, dim3((n_env * 4 + 63) / 64), dim3(64), 0, st, (const double*)scratch,
+                       crit_blocks(npix), n_env, sums);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_seg_criterion_grad(const float* pred, const float* target, int target_stride, int n_env, int img, int mode,
+                                      const double* coef, float* grad_pred, void* stream) {
+    if (!crit_args_ok(pred, target, target_stride, n_env, img) || !coef || !grad_pred ||
+        (mode != OCC_CRITERION_DICE && mode != OCC_CRITERION_BCE))
+        return OCC_ERR_ARG;
+    if (mode == OCC_CRITERION_BCE)
+        crit_grad_launch<true>(pred, target, target_stride, n_env, img * img, coef, grad_pred, (hipStream_t)stream);
+    else
+        crit_grad_launch<false>(pred, target, target_stride, n_env, img * img, coef, grad_pred, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }

@@ -18,7 +18,8 @@ Presets (model.py: a state dict stores neither the dilation nor the residual fla
 The segmentation decoder (csrc/occ_decoder.hpp; model.py:109-125,147-150) is picked up when its keys are in the state dict
 (``enc.has_decoder``): ``enc.segment(obs)`` is the predicted occlusion map, ``enc.forward_full(obs)`` the triple of
 ``FullNetwork.forward`` from one pass over the encoder, ``enc.occlusion_metrics(pred, target)`` the accuracy / IoU counts
-of pretrainer.py:127-141.
+of pretrainer.py:127-141, ``enc.validation_losses(...)`` one batch of ``PreTrainer.val()`` (losses and metrics from one read
+of the maps, csrc/occ_criterion.hpp).
 
 Whole-module checkpoints (``torch.save(model)``, as pretrainer.py writes them) need the reference's ``model.py`` to
 unpickle; with it on the path use ``FrozenEncoder.from_module(torch.load(path, weights_only=False))``.
@@ -412,6 +413,32 @@ class FrozenEncoder:
         n, img = int(c.shape[0]), int(pred.shape[-1])
         return dict(correct=c[:, 0], intersection=c[:, 1], union=c[:, 2], accuracy=total[0] / float(n * img * img),
                     iou=total[1] / total[2])
+
+    @torch.no_grad()
+    def validation_losses(self, segm: torch.Tensor, grad_pred: torch.Tensor, occlusion: torch.Tensor, grad: torch.Tensor,
+                          use_dice: bool = True, use_l1: bool = False) -> dict:
+        """One batch of ``PreTrainer.val()`` (pretrainer.py:176-189) on the outputs of ``forward_full``: ``segm_loss`` =
+        BinaryDiceLoss() (``use_dice``) or nn.BCELoss() of the predicted map against ``occlusion``, ``grad_loss`` =
+        nn.MSELoss() or nn.SmoothL1Loss(beta=0.01) (``use_l1``) of the (N,2) gradient prediction, ``loss`` their sum,
+        ``accuracy`` and ``iou`` as fractions over the batch (0 / 0 = nan, as in the reference), all 0-d f64 tensors on the
+        device, plus the per-env int64 ``correct``, ``intersection``, ``union``.  The maps are read once
+        (``ops.seg_criterion``); no host sync."""
+        from . import ops
+
+        c = ops.seg_criterion(segm, occlusion)
+        n, pixels = int(c["s_pt"].shape[0]), int(segm.shape[-1]) * int(segm.shape[-2])
+        if use_dice:
+            segm_loss = ops.dice_from_sums(c["s_pt"], c["s_pp"], c["s_tt"])[0].mean()
+        else:
+            segm_loss = c["s_bce"].sum() / float(n * pixels)
+        gp, g = grad_pred.to(torch.float32), grad.to(grad_pred.device, torch.float32)
+        if gp.shape != g.shape:
+            raise ValueError(f"grad_pred {tuple(gp.shape)} and grad {tuple(g.shape)} differ")
+        grad_loss = (torch.nn.functional.smooth_l1_loss(gp, g, beta=0.01) if use_l1 else torch.nn.functional.mse_loss(gp, g)).double()
+        correct, inter, union = c["correct"], c["intersection"], c["union"]
+        return dict(loss=grad_loss + segm_loss, segm_loss=segm_loss, grad_loss=grad_loss,
+                    accuracy=correct.sum().double() / float(n * pixels), iou=inter.sum().double() / union.sum().double(),
+                    correct=correct, intersection=inter, union=union)
 
 
 def _maps(t: torch.Tensor, what: str) -> torch.Tensor:

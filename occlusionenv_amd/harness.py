@@ -9,6 +9,8 @@
   * ``evaluate_segmentation`` -- the measuring half of pretrainer.py:176-189 (``val``) against the live environment
     instead of a stored dataset: the predicted occlusion map of a FullNetwork checkpoint against the occlusion image
     every step renders anyway.
+  * ``validate_pretrained`` -- pretrainer.py:162-204 (``val``) itself, on a stored dataset: Loss / Dice / MSE / Accuracy /
+    IoU as the means of the per-batch values.
 """
 from __future__ import annotations
 
@@ -104,3 +106,33 @@ def evaluate_segmentation(venv, enc, steps: int, policy: Optional[Callable] = No
     return dict(accuracy=100.0 * correct / pixels if pixels else float("nan"),
                 iou=100.0 * inter / union if union else float("nan"), correct=correct, intersection=inter, union=union,
                 pixels=pixels)
+
+
+@torch.no_grad()
+def validate_pretrained(enc, batches, use_dice: bool = True, use_l1: bool = False) -> dict:
+    """``PreTrainer.val()`` (pretrainer.py:162-204) for a FullNetwork checkpoint loaded as ``enc`` (a ``FrozenEncoder``):
+    ``batches`` is any iterable of ``(img, occlusion, grad, _)``, as ``dataset_io.OcclusionDataset`` behind a DataLoader
+    yields them (host tensors are moved to the encoder's device).  Every batch goes through ``enc.forward_full`` and
+    ``enc.validation_losses``; returned are the five numbers the reference prints and selects a checkpoint by, computed its
+    way: ``loss``, ``segm_loss``, ``grad_loss`` = the mean over batches of the per-batch losses, ``accuracy`` and ``iou`` =
+    the mean over batches of the per-batch ratios x 100 (a batch with an empty union contributes nan, as in the reference;
+    ``evaluate_segmentation`` pools the counts instead).  Also the pooled counts ``correct``, ``intersection``, ``union``,
+    ``pixels`` and ``batches``.  One host sync, at the end."""
+    rows, totals, pixels = [], None, 0
+    for img, occlusion, grad, *_ in batches:
+        img, occlusion, grad = img.to(enc.device), occlusion.to(enc.device), grad.to(enc.device)
+        _pooled, segm, grad_pred = enc.forward_full(img)
+        v = enc.validation_losses(segm, grad_pred, occlusion, grad, use_dice=use_dice, use_l1=use_l1)
+        rows.append(torch.stack([v[k].double() for k in ("loss", "segm_loss", "grad_loss", "accuracy", "iou")]))
+        t = torch.stack([v["correct"].sum(), v["intersection"].sum(), v["union"].sum()])
+        totals = t if totals is None else totals + t
+        pixels += segm.numel()
+    if not rows:
+        raise ValueError("validate_pretrained: no batches")
+    means = torch.stack(rows).mean(0)
+    # one transfer: the counts are exact in f64 below 2^53
+    host = torch.cat([means, totals.double()]).cpu().tolist()
+    loss, segm_loss, grad_loss, acc, iou = host[:5]
+    correct, inter, union = (int(x) for x in host[5:])
+    return dict(loss=loss, segm_loss=segm_loss, grad_loss=grad_loss, accuracy=100.0 * acc, iou=100.0 * iou, correct=correct,
+                intersection=inter, union=union, pixels=pixels, batches=len(rows))
