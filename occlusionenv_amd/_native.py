@@ -250,6 +250,24 @@ def ppo_scratch_floats() -> int:
     return int(load().occ_ppo_max_blocks()) * (PPO_PARAMS + 2)
 
 
+def ptr(t, byte_offset: int = 0):
+    """A tensor's address (plus ``byte_offset``) as the ``c_void_p`` argument of a native call; None stays None."""
+    return None if t is None else C.c_void_p(t.data_ptr() + byte_offset)
+
+
+def stream_ptr(device):
+    """The current torch stream of ``device``, as the stream argument of a native call."""
+    import torch
+
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def row_chunks(n: int, cap: int):
+    """(lo, rows) of consecutive calls over ``n`` rows with at most ``cap`` rows each."""
+    for lo in range(0, n, cap):
+        yield lo, min(cap, n - lo)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise NativeError(f"{what} failed with status {rc} (1 = bad argument, 2 = launch failure)")

@@ -19,7 +19,7 @@ The segmentation decoder (csrc/occ_decoder.hpp; model.py:109-125,147-150) is pic
 (``enc.has_decoder``): ``enc.segment(obs)`` is the predicted occlusion map, ``enc.forward_full(obs)`` the triple of
 ``FullNetwork.forward`` from one pass over the encoder, ``enc.occlusion_metrics(pred, target)`` the accuracy / IoU counts
 of pretrainer.py:127-141, ``enc.validation_losses(...)`` one batch of ``PreTrainer.val()`` (losses and metrics from one read
-of the maps, csrc/occ_criterion.hpp).
+of the maps, csrc/occ_criterion.hpp); both hand on to ``segmentation.py``, the home of everything that consumes a predicted map.
 
 Whole-module checkpoints (``torch.save(model)``, as pretrainer.py writes them) need the reference's ``model.py`` to
 unpickle; with it on the path use ``FrozenEncoder.from_module(torch.load(path, weights_only=False))``.
@@ -34,6 +34,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import segmentation
+from .segmentation import seg_counts  # noqa: F401
 
 CH, LEVELS, FEATURES = 8, 5, 256
 BN_EPS = 1e-5
@@ -206,14 +208,13 @@ class FrozenEncoder:
             self.grad_w = grad_head[0].to(self.device, torch.float32).contiguous()
             self.grad_b = grad_head[1].to(self.device, torch.float32).contiguous()
         self.heads = heads or {}
-        self._ws = {}
+        self._ws = {}  # (kind, chunk size, S) -> workspace
         self.dec_packed_host = self.dec_packed = None
         if decoder is not None:
             self.dec_packed_host = np.ascontiguousarray(decoder, dtype=np.float32)
             if lib.occ_decoder_packed_floats(C.byref(cfg)) != self.dec_packed_host.size:
                 raise nat.NativeError("packed decoder weights do not match the library's layout")
             self.dec_packed = torch.from_numpy(self.dec_packed_host).to(self.device)
-        self._seg_ws = {}
 
     @property
     def has_decoder(self) -> bool:
@@ -281,45 +282,65 @@ class FrozenEncoder:
         cfg.img, cfg.dilation, cfg.residual, cfg.separable = int(img), self.dilation, int(self.residual), int(self.separable)
         return cfg
 
-    def _workspace(self, n: int, img: int):
-        key = (n, img)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = C.c_size_t()
-            nat.check(nat.load().occ_encoder_workspace_query(C.byref(self._cfg(img)), n, C.byref(nbytes)),
-                      "occ_encoder_workspace_query")
-            ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
-        return ws
-
-    @torch.no_grad()
-    def __call__(self, obs: torch.Tensor) -> torch.Tensor:
+    def _check_obs(self, obs: torch.Tensor, decoder: bool) -> int:
+        """The checks of a forward call, before anything native is touched -> the image side.  ``decoder``: the call runs the
+        segmentation decoder, whose skip additions need a side that is a multiple of 32."""
         if not isinstance(obs, torch.Tensor) or not obs.is_cuda:
             raise nat.NativeError("FrozenEncoder needs CUDA/ROCm tensors; there is no CPU fallback")
+        if decoder and not self.has_decoder:
+            raise ValueError("this checkpoint has no segmentation decoder (no 'segmenter.0.features.*' / 'decoder.features.*' keys)")
         if obs.dim() != 4 or obs.shape[1] != 4 or obs.shape[2] != obs.shape[3]:
             raise ValueError(f"obs must be (N,4,S,S), got {tuple(obs.shape)}")
         if obs.device != self.packed.device:
             raise ValueError(f"obs is on {obs.device}, the encoder's weights on {self.packed.device}")
         img = int(obs.shape[2])
+        if decoder and not (32 <= img <= 1024 and img % 32 == 0):
+            raise ValueError(f"image side {img}: the decoder's skip additions need a multiple of 32 in [32, 1024]")
         if not 32 <= img <= 1024:
             raise ValueError(f"image side {img} outside [32, 1024]")
+        return img
+
+    def _workspace(self, kind: str, n: int, img: int):
+        """The kept workspace of ``occ_<kind>_forward`` (kind "encoder" or "segment") for a chunk of n envs."""
+        key = (kind, n, img)
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes, what = C.c_size_t(), f"occ_{kind}_workspace_query"
+            nat.check(getattr(nat.load(), what)(C.byref(self._cfg(img)), n, C.byref(nbytes)), what)
+            ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+            self._ws[key] = ws
+        return ws
+
+    def _forward(self, obs: torch.Tensor, decoder: bool, want_logits: bool = False, want_features: bool = False):
+        """-> (pooled (N,256), prob (N,1,S,S), logits, decoder feature (N,8,S,S)), None for what was not asked for: one
+        occ_segment_forward (``decoder``) or occ_encoder_forward per chunk on the caller's stream."""
+        img = self._check_obs(obs, decoder)
         obs = obs.detach().to(torch.float32).contiguous()
         n_all = int(obs.shape[0])
-        feats = torch.empty(n_all, FEATURES, dtype=torch.float32, device=obs.device)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=obs.device)  # noqa: E731
+        feats = new(n_all, FEATURES)
+        prob = new(n_all, 1, img, img) if decoder else None
+        logits = new(n_all, 1, img, img) if want_logits else None
+        dfeat = new(n_all, CH, img, img) if want_features else None
         if n_all == 0:
-            return feats
-        lib = nat.load()
-        cfg = self._cfg(img)
-        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        per_env = 4 * img * img
-        for lo in range(0, n_all, self.max_chunk):
-            n = min(self.max_chunk, n_all - lo)
-            ws = self._workspace(n, img)
-            nat.check(lib.occ_encoder_forward(C.byref(cfg), C.c_void_p(self.packed.data_ptr()),
-                                              C.c_void_p(obs.data_ptr() + 4 * lo * per_env), n, C.c_void_p(ws.data_ptr()),
-                                              ws.numel(), C.c_void_p(feats.data_ptr() + 4 * lo * FEATURES), stream),
-                      "occ_encoder_forward")
-        return feats
+            return feats, prob, logits, dfeat
+        lib, cfg, stream = nat.load(), self._cfg(img), nat.stream_ptr(obs.device)
+        pix = 4 * img * img  # bytes of one f32 map
+        for lo, n in nat.row_chunks(n_all, self.max_chunk):
+            ws = self._workspace("segment" if decoder else "encoder", n, img)
+            obs_lo, feats_lo = nat.ptr(obs, lo * 4 * pix), nat.ptr(feats, lo * 4 * FEATURES)
+            if decoder:
+                nat.check(lib.occ_segment_forward(C.byref(cfg), nat.ptr(self.packed), nat.ptr(self.dec_packed), obs_lo, n, nat.ptr(ws),
+                                                  ws.numel(), feats_lo, nat.ptr(prob, lo * pix), nat.ptr(logits, lo * pix),
+                                                  nat.ptr(dfeat, lo * CH * pix), stream), "occ_segment_forward")
+            else:
+                nat.check(lib.occ_encoder_forward(C.byref(cfg), nat.ptr(self.packed), obs_lo, n, nat.ptr(ws), ws.numel(), feats_lo,
+                                                  stream), "occ_encoder_forward")
+        return feats, prob, logits, dfeat
+
+    @torch.no_grad()
+    def __call__(self, obs: torch.Tensor) -> torch.Tensor:
+        return self._forward(obs, False)[0]
 
     @torch.no_grad()
     def predict_grad(self, obs: torch.Tensor) -> torch.Tensor:
@@ -331,56 +352,10 @@ class FrozenEncoder:
         return torch.tanh(g) if self.grad_tanh else g
 
     # ---- segmentation decoder --------------------------------------------------------------------------------------
-    def _seg_workspace(self, n: int, img: int):
-        key = (n, img)
-        ws = self._seg_ws.get(key)
-        if ws is None:
-            nbytes = C.c_size_t()
-            nat.check(nat.load().occ_segment_workspace_query(C.byref(self._cfg(img)), n, C.byref(nbytes)),
-                      "occ_segment_workspace_query")
-            ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-            self._seg_ws[key] = ws
-        return ws
-
     def _segment(self, obs: torch.Tensor, want_logits: bool, want_features: bool):
         """-> (pooled (N,256), prob (N,1,S,S), logits or None, decoder feature (N,8,S,S) or None): one occ_segment_forward
         per chunk on the caller's stream."""
-        if not isinstance(obs, torch.Tensor) or not obs.is_cuda:
-            raise nat.NativeError("FrozenEncoder needs CUDA/ROCm tensors; there is no CPU fallback")
-        if not self.has_decoder:
-            raise ValueError("this checkpoint has no segmentation decoder (no 'segmenter.0.features.*' / 'decoder.features.*' keys)")
-        if obs.dim() != 4 or obs.shape[1] != 4 or obs.shape[2] != obs.shape[3]:
-            raise ValueError(f"obs must be (N,4,S,S), got {tuple(obs.shape)}")
-        if obs.device != self.packed.device:
-            raise ValueError(f"obs is on {obs.device}, the encoder's weights on {self.packed.device}")
-        img = int(obs.shape[2])
-        if not 32 <= img <= 1024 or img % 32 != 0:
-            raise ValueError(f"image side {img}: the decoder's skip additions need a multiple of 32 in [32, 1024]")
-        obs = obs.detach().to(torch.float32).contiguous()
-        n_all = int(obs.shape[0])
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=obs.device)  # noqa: E731
-        feats, prob = new(n_all, FEATURES), new(n_all, 1, img, img)
-        logits = new(n_all, 1, img, img) if want_logits else None
-        dfeat = new(n_all, CH, img, img) if want_features else None
-        if n_all == 0:
-            return feats, prob, logits, dfeat
-        lib = nat.load()
-        cfg = self._cfg(img)
-        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        pix = 4 * img * img  # bytes of one f32 map
-
-        def at(t, lo, per_env_bytes):
-            return C.c_void_p(t.data_ptr() + lo * per_env_bytes) if t is not None else None
-
-        for lo in range(0, n_all, self.max_chunk):
-            n = min(self.max_chunk, n_all - lo)
-            ws = self._seg_workspace(n, img)
-            nat.check(lib.occ_segment_forward(C.byref(cfg), C.c_void_p(self.packed.data_ptr()), C.c_void_p(self.dec_packed.data_ptr()),
-                                              at(obs, lo, 4 * pix), n, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                              at(feats, lo, 4 * FEATURES), at(prob, lo, pix), at(logits, lo, pix),
-                                              at(dfeat, lo, CH * pix), stream),
-                      "occ_segment_forward")
-        return feats, prob, logits, dfeat
+        return self._forward(obs, True, want_logits, want_features)
 
     @torch.no_grad()
     def segment(self, obs: torch.Tensor, return_logits: bool = False, return_features: bool = False):
@@ -401,20 +376,14 @@ class FrozenEncoder:
         g = torch.addmm(self.grad_b, feats, self.grad_w.t())
         return feats, prob, (torch.tanh(g) if self.grad_tanh else g)
 
-    @torch.no_grad()
     def occlusion_metrics(self, pred: torch.Tensor, target: torch.Tensor) -> dict:
         """The judgement of pretrainer.py:133-141 on a batch: both maps thresholded at 0.5; per-env int64 counts
         ``correct`` (pixels where they agree), ``intersection``, ``union`` on the device, and over the whole batch
         ``accuracy`` = sum(correct) / pixels and ``iou`` = sum(intersection) / sum(union) as 0-d f64 tensors (0 / 0 = nan,
         as in the reference).  pred (N,1,S,S) or (N,S,S); target likewise, any float tensor; a strided view such as
         ``full_state[..., 3]`` is read in place."""
-        c = seg_counts(pred, target)
-        total = c.sum(0).to(torch.float64)
-        n, img = int(c.shape[0]), int(pred.shape[-1])
-        return dict(correct=c[:, 0], intersection=c[:, 1], union=c[:, 2], accuracy=total[0] / float(n * img * img),
-                    iou=total[1] / total[2])
+        return segmentation.occlusion_metrics(pred, target)
 
-    @torch.no_grad()
     def validation_losses(self, segm: torch.Tensor, grad_pred: torch.Tensor, occlusion: torch.Tensor, grad: torch.Tensor,
                           use_dice: bool = True, use_l1: bool = False) -> dict:
         """One batch of ``PreTrainer.val()`` (pretrainer.py:176-189) on the outputs of ``forward_full``: ``segm_loss`` =
@@ -422,53 +391,5 @@ class FrozenEncoder:
         nn.MSELoss() or nn.SmoothL1Loss(beta=0.01) (``use_l1``) of the (N,2) gradient prediction, ``loss`` their sum,
         ``accuracy`` and ``iou`` as fractions over the batch (0 / 0 = nan, as in the reference), all 0-d f64 tensors on the
         device, plus the per-env int64 ``correct``, ``intersection``, ``union``.  The maps are read once
-        (``ops.seg_criterion``); no host sync."""
-        from . import ops
-
-        c = ops.seg_criterion(segm, occlusion)
-        n, pixels = int(c["s_pt"].shape[0]), int(segm.shape[-1]) * int(segm.shape[-2])
-        if use_dice:
-            segm_loss = ops.dice_from_sums(c["s_pt"], c["s_pp"], c["s_tt"])[0].mean()
-        else:
-            segm_loss = c["s_bce"].sum() / float(n * pixels)
-        gp, g = grad_pred.to(torch.float32), grad.to(grad_pred.device, torch.float32)
-        if gp.shape != g.shape:
-            raise ValueError(f"grad_pred {tuple(gp.shape)} and grad {tuple(g.shape)} differ")
-        grad_loss = (torch.nn.functional.smooth_l1_loss(gp, g, beta=0.01) if use_l1 else torch.nn.functional.mse_loss(gp, g)).double()
-        correct, inter, union = c["correct"], c["intersection"], c["union"]
-        return dict(loss=grad_loss + segm_loss, segm_loss=segm_loss, grad_loss=grad_loss,
-                    accuracy=correct.sum().double() / float(n * pixels), iou=inter.sum().double() / union.sum().double(),
-                    correct=correct, intersection=inter, union=union)
-
-
-def _maps(t: torch.Tensor, what: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise nat.NativeError("occlusion_metrics needs CUDA/ROCm tensors; there is no CPU fallback")
-    if t.dim() == 4 and t.shape[1] == 1:
-        t = t[:, 0]
-    if t.dim() != 3 or t.shape[1] != t.shape[2]:
-        raise ValueError(f"{what} must be (N,S,S) or (N,1,S,S), got {tuple(t.shape)}")
-    return t if t.dtype == torch.float32 else t.to(torch.float32)
-
-
-def seg_counts(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """(N,3) int64 on the device: per env #(p == t), #(p and t), #(p or t) with p = pred > 0.5, t = target > 0.5
-    (occ_seg_metrics)."""
-    pred, target = _maps(pred, "pred").contiguous(), _maps(target, "target")
-    if pred.shape != target.shape or pred.device != target.device:
-        raise ValueError(f"pred {tuple(pred.shape)} on {pred.device} and target {tuple(target.shape)} on {target.device} differ")
-    n, img = int(pred.shape[0]), int(pred.shape[1])
-    if img > 1024:
-        raise ValueError(f"image side {img} above 1024")
-    counts = torch.empty(n, 3, dtype=torch.int64, device=pred.device)
-    if n == 0:
-        return counts
-    k = target.stride(2)
-    if not (k >= 1 and target.stride(1) == k * img and target.stride(0) == k * img * img):
-        target, k = target.contiguous(), 1
-    stream = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-    for lo in range(0, n, 65535):
-        m = min(65535, n - lo)
-        nat.check(nat.load().occ_seg_metrics(C.c_void_p(pred[lo:].data_ptr()), C.c_void_p(target[lo:].data_ptr()), int(k), m, img,
-                                             C.c_void_p(counts[lo:].data_ptr()), stream), "occ_seg_metrics")
-    return counts
+        (``segmentation.seg_criterion``); no host sync."""
+        return segmentation.validation_losses(segm, grad_pred, occlusion, grad, use_dice, use_l1)

@@ -18,14 +18,11 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._native import ptr as _p
 from .meshes import MeshPool
 
 
 WAVES_PER_CU = 12  # resident persistent waves per CU of occ_raster2_kernel (3 per SIMD at <= 168 VGPRs, 12.2 KB LDS each)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class _RewardGrad(torch.autograd.Function):
@@ -411,7 +408,7 @@ class OcclusionEngine:
 
     # ---- launches -------------------------------------------------------------------------
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return nat.stream_ptr(self.device)
 
     def _camera_args(self, mode, action, el, az, rad, pos_out, n, pos2=None) -> nat.OccCameraArgs:
         ca = nat.OccCameraArgs()
@@ -608,7 +605,7 @@ class OcclusionEngine:
         h[:n, 4:13] = off.view(np.int32)
         # the kernel reads the rows straight from the pinned buffer when it runs (no copy launch): the buffers alternate, and
         # before this one is written again the host has waited for a later event on the stream (the next step's report)
-        nat.check(self.lib.occ_reserve_refill(C.c_void_p(host.data_ptr()), n, self.N, self.R, _p(self._mesh_all), _p(self._off_all),
+        nat.check(self.lib.occ_reserve_refill(_p(host), n, self.N, self.R, _p(self._mesh_all), _p(self._off_all),
                                               _p(self.rs_state), _p(self._skip), self._stream()), "occ_reserve_refill")
 
     def auto_reset(self, out) -> dict:

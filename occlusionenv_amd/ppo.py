@@ -265,14 +265,13 @@ class BatchedPPO:
         losses = torch.empty(self.K_epochs, 2, dtype=torch.float32, device=feats.device)
         g_a, g_v = self.optimizer.param_groups
         b1, b2 = g_a["betas"]
-        stream = C.c_void_p(torch.cuda.current_stream(feats.device).cuda_stream)
+        stream = nat.stream_ptr(feats.device)
         with torch.no_grad():
             nat.check(nat.load().occ_ppo_update(
-                C.c_void_p(feats.data_ptr()), C.c_void_p(actions.data_ptr()), C.c_void_p(old_lp.data_ptr()),
-                C.c_void_p(returns.data_ptr()), int(feats.shape[0]), float(self.action_std) ** 2, float(self.eps_clip),
-                float(g_a["lr"]), float(g_v["lr"]), float(b1), float(b2), float(g_a["eps"]), C.byref(ps), int(self.K_epochs),
-                C.c_void_p(losses.data_ptr()), C.c_void_p(st["scratch"].data_ptr()), C.c_void_p(st["counter"].data_ptr()),
-                stream), "occ_ppo_update")
+                nat.ptr(feats), nat.ptr(actions), nat.ptr(old_lp), nat.ptr(returns), int(feats.shape[0]),
+                float(self.action_std) ** 2, float(self.eps_clip), float(g_a["lr"]), float(g_v["lr"]), float(b1), float(b2),
+                float(g_a["eps"]), C.byref(ps), int(self.K_epochs), nat.ptr(losses), nat.ptr(st["scratch"]),
+                nat.ptr(st["counter"]), stream), "occ_ppo_update")
         self._keep = (feats, actions, old_lp, returns)  # alive until the stream has run the launches
         return losses[:, 0], losses[:, 1]
 

@@ -1,4 +1,4 @@
-"""The fused pretrainer criterion (occlusionenv_amd/ops.py: seg_criterion + binary_dice_loss forward and backward,
+"""The fused pretrainer criterion (occlusionenv_amd/segmentation.py: seg_criterion + binary_dice_loss forward and backward,
 csrc/occ_criterion.hpp) against the same expressions as PyTorch-ROCm ops with autograd (loss.py's formula restated, plus
 the accuracy / IoU lines of pretrainer.py:133-141), in one process with interleaved repeats.
 
