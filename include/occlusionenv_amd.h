@@ -28,6 +28,7 @@
  *   - the segmentation decoder of the same network (model.py:25-33,52-67,109-166: the predicted occlusion map, the third
  *     output of FullNetwork.forward / the output of Segmenter.forward), inference only, and the accuracy / IoU counts
  *     the pretrainer judges it by (pretrainer.py:127-141)          -> occ_segment_forward, occ_seg_metrics
+ *     fine-tuning of that decoder with the encoder frozen (additive in ABI 12) -> occ_segment_train_forward, occ_segment_backward
  *   - the pretrainer's segmentation criterion on that map (pretrainer.py:89,127-141,176-189; loss.py:24-39
  *     BinaryDiceLoss, nn.BCELoss): the sums of both losses and the counts in one read, and the gradient with respect to the
  *     prediction                                                   -> occ_seg_criterion, occ_seg_criterion_grad
@@ -421,6 +422,32 @@ int occ_segment_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* 
 int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
                         int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* logit, float* dec_feat,
                         void* stream);
+/*
+ * Training of the decoder and the classifier with the encoder frozen (additive in ABI 12; csrc/occ_decoder_bwd.hpp).  The
+ * decoder's BatchNorm runs with its running statistics, as in inference: with u = convT(x_j) + bias, r = relu(u),
+ * y_j = bn_scale r + bn_shift + skip, the parameters that receive a gradient are w, bias, bn_scale, bn_shift of every up
+ * layer and cls_w, cls_b.  Neither d obs, d skip nor any encoder gradient is computed.
+ *
+ * occ_segment_train_forward is occ_segment_forward (feats and prob are the same to the bit) that keeps, in ws, every level's
+ * input x_j, its relu output r_j, the decoder feature y_4 and prob.  Workspace, every part 256-byte aligned: the
+ * workspace of occ_segment_forward (occ_segment_workspace_query bytes), then for j = 0..4 y_j | r_j, each
+ * (n_env, 128 >> j, S/16 << j, S/16 << j) f32, then prob (n_env,S,S), then two gradient buffers of the sizes of y_4 and y_3.
+ *
+ * occ_segment_backward is the backward of the LATEST occ_segment_train_forward on ws (same cfg, n_env and dec_packed) for the
+ * upstream gradient grad_prob = d loss / d prob (n_env,1,S,S) f32, 16-byte aligned.  grad_packed receives
+ * occ_decoder_packed_floats floats in the layout of dec_packed: per level dw[ci][ky * 3 + kx][co] | dbias | dbn_scale |
+ * dbn_shift, then dcls_w[8] | dcls_b; it is OVERWRITTEN, not accumulated.  The relu gate is the forward's own r > 0.
+ * scratch: device memory of the queried scratch_bytes (16-byte aligned; block partials).  No floating-point atomics; block
+ * partials are added in a fixed order in f64: every gradient is bitwise the same from call to call.  24 launches on
+ * `stream`, nothing allocated or synchronised.  OCC_ERR_ARG before any launch for a null pointer, cfg->img % 32 != 0, n_env
+ * outside [1, 65535], a misaligned or a short buffer.
+ */
+int occ_segment_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes);
+int occ_segment_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                              int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, void* stream);
+int occ_segment_backward(const OccEncoderConfig* cfg, const float* dec_packed, int n_env, void* ws, size_t ws_bytes,
+                         const float* grad_prob, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream);
+
 /*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at

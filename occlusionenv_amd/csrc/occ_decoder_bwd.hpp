@@ -1,0 +1,574 @@
+// occ_decoder_bwd.hpp -- training of the segmentation decoder and classifier with the encoder frozen: a forward that keeps
+// what the backward needs, and the backward with respect to every decoder parameter.  Part of the single translation unit
+// occ_kernels.hip (included inside namespace occ, after occ_decoder.hpp, whose quad mapping, LDS staging and packed layout
+// it mirrors, and after occ_criterion.hpp's reduction rule, which it follows).
+//
+// Forward per level j (c = 128 .. 8): u = convT(x_j) + b, r = relu(u), y_j = s r + t + skip, x_{j+1} = y_j; after the last
+// level z = cls_w y_4 + cls_b, p = sigmoid(z).  BatchNorm runs with its running statistics (s, t folded by the host).
+//
+//   occ_dec_up_train_kernel     occ_dec_up_kernel with the same FMA order (prob and the pooled feature are the same to
+//                               the bit), which also stores r_j and, at the last level, y_4 and a second copy of p.
+//   occ_dec_bwd_act_kernel      per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0] written over dY, with dY = dz
+//                               cls_w[c], dz = g p (1 - p) at the last level; f64 block partials of dS = sum dY r, dT = sum
+//                               dY, dB = sum dU (and sum dz y_4[c], sum dz at the last level).  The gate is the forward's
+//                               own r > 0.
+//   occ_dec_bwd_act_final_kernel  one wave per (channel, sum): lane l adds partials l, l + 64, .. in order, then six
+//                               __shfl_down steps; all f64, rounded once to f32.
+//   occ_dec_bwd_dx_kernel       dX[ci][iy][ix] = sum_co sum_k w[ci][k][co] dU[co][2 iy - 1 + ky][2 ix - 1 + kx]: the mirror
+//                               of the forward's quad mapping.  A thread owns one input pixel for 16 input channels; the
+//                               (2 T + 1)^2 dU tile is staged in LDS 8 output channels at a time (row / column -1 and 2 H
+//                               read as zero); weights are wave-uniform scalar loads of 8 consecutive co.  Not launched for
+//                               level 0: the encoder is frozen.
+//   occ_dec_bwd_dw_kernel       dW[ci][k][co] = sum_{n,iy,ix} x[ci][iy][ix] dU[co][2 iy - 1 + ky][2 ix - 1 + kx], a
+//                               (2c) x (9c) contraction over K = N H^2.  A thread owns 16 ci x 9 taps x 1 co (144 f32
+//                               accumulators); a block owns a CIB x COB tile of (ci, co) and one slice of K (consecutive
+//                               T x T pixel tiles, envs in order); when the (ci, co) tile needs fewer than 256 threads the
+//                               others take other pixels of the tile (P pixel lanes), which are added inside the wave by
+//                               __shfl_xor steps in a fixed order.  Every block writes its partial dW (one per wave or per
+//                               pixel lane) to caller scratch.
+//   occ_dec_bwd_sum_kernel      the partials added per element in a fixed order (four interleaved chains in f64, then the
+//                               four in order), rounded once to f32.
+//
+// No floating-point atomics; the split of K is a function of (S, N) alone: every gradient is bitwise the same from call to
+// call.  f32 chains: a thread's accumulator sees at most tiles-per-slice x T^2 / P products before the f64 stage.
+
+constexpr int kBwdChunk = 4096;   // pixels of one (env, channel) plane per block of the activation step
+constexpr int kBwdDxCC = 8;       // output channels of dU staged per step of the input gradient
+constexpr int kBwdDxCIG = 16;     // input channels per thread of the input gradient
+constexpr int kBwdDwBlocks = 512;  // blocks of the weight gradient per level (K slices x (ci, co) tiles)
+
+template <int T, int COG, bool FUSE>
+__global__ __launch_bounds__(256) void occ_dec_up_train_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                               float* __restrict__ rkeep, const float* __restrict__ skip,
+                                                               const float* __restrict__ w, int cin, int cout, int H,
+                                                               int tiles_x, const float* __restrict__ cls,
+                                                               float* __restrict__ prob, float* __restrict__ pkeep) {
+    constexpr int TT = T * T, R = T + 1, RR = R * R;
+    __shared__ float s[kEncCC * RR];
+    const int tid = threadIdx.x;
+    const int p = tid % TT;
+    const int ng = blockDim.x / TT;
+    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
+    const int co0 = (blockIdx.y * ng + g) * COG;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int iy0 = ty * T, ix0 = tx * T;
+    const int py = p / T, px = p % T;
+    const size_t plane = (size_t)H * H;
+    const float* xe = x + (size_t)blockIdx.z * cin * plane;
+    const float* bias = w + (size_t)cin * 9 * cout;
+    const float* bns = bias + cout;
+    const float* bnt = bns + cout;
+
+    float acc[4][COG];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < COG; ++j) acc[q][j] = 0.f;
+
+    for (int ci0 = 0; ci0 < cin; ci0 += kEncCC) {
+        const int cc = min(kEncCC, cin - ci0);
+        __syncthreads();
+        for (int i = tid; i < cc * RR; i += blockDim.x) {
+            const int c = i / RR, r = i - c * RR;
+            const int ry = r / R, rx = r - ry * R;
+            const int gy = iy0 + ry, gx = ix0 + rx;
+            float v = 0.f;
+            if (gy < H && gx < H) v = xe[(ci0 + c) * plane + (size_t)gy * H + gx];
+            s[i] = v;
+        }
+        __syncthreads();
+        for (int c = 0; c < cc; ++c) {
+            const float* sc = s + c * RR + py * R + px;
+            const float a = sc[0], b = sc[1], cv = sc[R], dv = sc[R + 1];
+            const float* wr = w + (size_t)(ci0 + c) * 9 * cout + co0;  // w[ci][ky * 3 + kx][co]
+#pragma unroll
+            for (int j = 0; j < COG; ++j) {  // the FMA order of occ_dec_up_kernel
+                acc[0][j] = fmaf(wr[4 * cout + j], a, acc[0][j]);
+                acc[1][j] = fmaf(wr[3 * cout + j], b, fmaf(wr[5 * cout + j], a, acc[1][j]));
+                acc[2][j] = fmaf(wr[1 * cout + j], cv, fmaf(wr[7 * cout + j], a, acc[2][j]));
+                acc[3][j] = fmaf(wr[0 * cout + j], dv,
+                                 fmaf(wr[2 * cout + j], cv, fmaf(wr[6 * cout + j], b, fmaf(wr[8 * cout + j], a, acc[3][j]))));
+            }
+        }
+    }
+    const int iy = iy0 + py, ix = ix0 + px;
+    if (iy >= H || ix >= H) return;
+    const int W2 = 2 * H;
+    const size_t oplane = 4 * plane;
+    const size_t off = (size_t)(2 * iy) * W2 + 2 * ix;
+    const size_t ebase = (size_t)blockIdx.z * cout * oplane;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < COG; ++j) {
+        const int co = co0 + j;
+        const float2 s0 = *reinterpret_cast<const float2*>(skip + ebase + co * oplane + off);
+        const float2 s1 = *reinterpret_cast<const float2*>(skip + ebase + co * oplane + off + W2);
+        float r[4], v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            r[q] = fmaxf(acc[q][j] + bias[co], 0.f);
+            v[q] = fmaf(r[q], bns[co], bnt[co]);
+        }
+        v[0] += s0.x;
+        v[1] += s0.y;
+        v[2] += s1.x;
+        v[3] += s1.y;
+        *reinterpret_cast<float2*>(rkeep + ebase + co * oplane + off) = make_float2(r[0], r[1]);
+        *reinterpret_cast<float2*>(rkeep + ebase + co * oplane + off + W2) = make_float2(r[2], r[3]);
+        *reinterpret_cast<float2*>(y + ebase + co * oplane + off) = make_float2(v[0], v[1]);
+        *reinterpret_cast<float2*>(y + ebase + co * oplane + off + W2) = make_float2(v[2], v[3]);
+        if constexpr (FUSE) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) z[q] = fmaf(cls[j], v[q], z[q]);
+        }
+    }
+    if constexpr (FUSE) {
+        float pr[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            z[q] += cls[COG];
+            pr[q] = 1.f / (1.f + expf(-z[q]));
+        }
+        const size_t o = (size_t)blockIdx.z * oplane + off;
+        *reinterpret_cast<float2*>(prob + o) = make_float2(pr[0], pr[1]);
+        *reinterpret_cast<float2*>(prob + o + W2) = make_float2(pr[2], pr[3]);
+        *reinterpret_cast<float2*>(pkeep + o) = make_float2(pr[0], pr[1]);
+        *reinterpret_cast<float2*>(pkeep + o + W2) = make_float2(pr[2], pr[3]);
+    }
+}
+
+// Activation step of one level.  g: (n, c, plane) dY on entry (not read when LAST), dU on exit.  r: the forward's relu(u).
+// LAST: gp = d loss / d prob and prob are (n, plane), y4 (n, c, plane), clsw[c].
+// partials[((ch * n + env) * chunks + chunk) * NS + k], NS = LAST ? 5 : 3: k = 0 dS, 1 dT, 2 dB, 3 sum dz y4[ch], 4 sum dz.
+template <bool LAST>
+__global__ __launch_bounds__(256) void occ_dec_bwd_act_kernel(float* __restrict__ g, const float* __restrict__ r,
+                                                              const float* __restrict__ bns, int c, int plane,
+                                                              const float* __restrict__ gp, const float* __restrict__ prob,
+                                                              const float* __restrict__ y4, const float* __restrict__ clsw,
+                                                              double* __restrict__ partials) {
+    constexpr int NS = LAST ? 5 : 3;
+    __shared__ double part[4][NS];
+    const int ch = blockIdx.y, env = blockIdx.z;
+    const size_t base = ((size_t)env * c + ch) * plane;
+    const float sc = bns[ch];
+    const float cw = LAST ? clsw[ch] : 0.f;
+    double sum[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) sum[k] = 0.0;
+    const int lo = blockIdx.x * kBwdChunk;
+#pragma unroll
+    for (int j = 0; j < kBwdChunk / 1024; ++j) {
+        const int i = lo + 4 * ((int)threadIdx.x + 256 * j);  // plane % 4 == 0: the four pixels are inside or outside together
+        if (i >= plane) break;
+        const float4 r4 = *reinterpret_cast<const float4*>(r + base + i);
+        const float rv[4] = {r4.x, r4.y, r4.z, r4.w};
+        float dy[4], dz[4] = {0.f, 0.f, 0.f, 0.f}, yv[4] = {0.f, 0.f, 0.f, 0.f}, du[4];
+        if constexpr (LAST) {
+            const float4 g4 = *reinterpret_cast<const float4*>(gp + (size_t)env * plane + i);
+            const float4 p4 = *reinterpret_cast<const float4*>(prob + (size_t)env * plane + i);
+            const float4 y = *reinterpret_cast<const float4*>(y4 + base + i);
+            const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, pv[4] = {p4.x, p4.y, p4.z, p4.w};
+            yv[0] = y.x, yv[1] = y.y, yv[2] = y.z, yv[3] = y.w;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                dz[q] = gv[q] * (pv[q] * (1.f - pv[q]));
+                dy[q] = dz[q] * cw;
+            }
+        } else {
+            const float4 d4 = *reinterpret_cast<const float4*>(g + base + i);
+            dy[0] = d4.x, dy[1] = d4.y, dy[2] = d4.z, dy[3] = d4.w;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            du[q] = rv[q] > 0.f ? dy[q] * sc : 0.f;
+            sum[0] = fma((double)dy[q], (double)rv[q], sum[0]);
+            sum[1] += (double)dy[q];
+            sum[2] += (double)du[q];
+            if constexpr (LAST) {
+                sum[3] = fma((double)dz[q], (double)yv[q], sum[3]);
+                sum[4] += (double)dz[q];
+            }
+        }
+        *reinterpret_cast<float4*>(g + base + i) = make_float4(du[0], du[1], du[2], du[3]);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) sum[k] += __shfl_down(sum[k], d);
+    const int wave = threadIdx.x / 64;
+    if (threadIdx.x % 64 == 0)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) part[wave][k] = sum[k];
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        double t = 0.0;
+        for (int k = 0; k < 4; ++k) t += part[k][threadIdx.x];
+        partials[((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * NS + threadIdx.x] = t;
+    }
+}
+
+// One wave per (channel, sum k): dst[k][ch] = the channel's nparts partials.  dst[4] (sum dz) is taken from channel 0 only
+// (every channel's block forms the same dz).
+struct BwdActDst {
+    float* p[5];  // dscale, dshift, dbias, dcls_w, dcls_b
+};
+
+__global__ __launch_bounds__(64) void occ_dec_bwd_act_final_kernel(const double* __restrict__ partials, int nparts, int ns,
+                                                                   BwdActDst dst) {
+    const int ch = blockIdx.x, k = blockIdx.y;
+    const double* pe = partials + (size_t)ch * nparts * ns + k;
+    double sum = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 64) sum += pe[(size_t)i * ns];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, d);
+    if (threadIdx.x != 0) return;
+    if (k < 4) dst.p[k][ch] = (float)sum;
+    else if (ch == 0) dst.p[4][0] = (float)sum;
+}
+
+// du: (n, cout, 2H, 2H); dx: (n, cin, H, H); w: the level's packed w[ci][k][co].  cin % 16 == 0, cout % 8 == 0.
+template <int T>
+__global__ __launch_bounds__(256) void occ_dec_bwd_dx_kernel(const float* __restrict__ du, float* __restrict__ dx,
+                                                             const float* __restrict__ w, int cin, int cout, int H, int tiles_x) {
+    constexpr int TT = T * T, R = 2 * T + 1, RR = R * R, CIG = kBwdDxCIG, CC = kBwdDxCC;
+    __shared__ float s[CC * RR];
+    const int tid = threadIdx.x;
+    const int p = tid % TT;
+    const int ng = blockDim.x / TT;
+    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
+    const int ci0 = (blockIdx.y * ng + g) * CIG;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int iy0 = ty * T, ix0 = tx * T;
+    const int py = p / T, px = p % T;
+    const int W2 = 2 * H;
+    const size_t oplane = (size_t)W2 * W2;
+    const float* de = du + (size_t)blockIdx.z * cout * oplane;
+
+    float acc[CIG];
+#pragma unroll
+    for (int j = 0; j < CIG; ++j) acc[j] = 0.f;
+
+    for (int co0 = 0; co0 < cout; co0 += CC) {
+        __syncthreads();
+        for (int i = tid; i < CC * RR; i += blockDim.x) {
+            const int c = i / RR, r = i - c * RR;
+            const int ry = r / R, rx = r - ry * R;
+            const int gy = 2 * iy0 - 1 + ry, gx = 2 * ix0 - 1 + rx;
+            float v = 0.f;
+            if (gy >= 0 && gy < W2 && gx >= 0 && gx < W2) v = de[(co0 + c) * oplane + (size_t)gy * W2 + gx];
+            s[i] = v;
+        }
+        __syncthreads();
+        float d[CC][9];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+            const float* sp = s + c * RR + 2 * py * R + 2 * px;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) d[c][k] = sp[(k / 3) * R + k % 3];
+        }
+        const float* wr = w + (size_t)ci0 * 9 * cout + co0;
+#pragma unroll
+        for (int j = 0; j < CIG; ++j)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const float* wk = wr + (size_t)(j * 9 + k) * cout;
+#pragma unroll
+                for (int c = 0; c < CC; ++c) acc[j] = fmaf(wk[c], d[c][k], acc[j]);
+            }
+    }
+    const int iy = iy0 + py, ix = ix0 + px;
+    if (iy >= H || ix >= H) return;
+    const size_t plane = (size_t)H * H;
+    float* xe = dx + ((size_t)blockIdx.z * cin + ci0) * plane + (size_t)iy * H + ix;
+#pragma unroll
+    for (int j = 0; j < CIG; ++j) xe[j * plane] = acc[j];
+}
+
+// x: (n, cin, H, H); du: (n, cout, 2H, 2H); part: [slice * PB + wave or pixel lane][cin * 9 * cout], PB = 256 / max(Q, 64).
+// A slice is the tiles [blockIdx.x * tps, .. + tps) of the n * tiles_x^2 tiles, envs in order.
+template <int T, int CIB, int COB>
+__global__ __launch_bounds__(256) void occ_dec_bwd_dw_kernel(const float* __restrict__ x, const float* __restrict__ du,
+                                                             float* __restrict__ part, int cin, int cout, int H, int tiles_x,
+                                                             int total_tiles, int tps) {
+    constexpr int TT = T * T, R = 2 * T + 1, RR = R * R, XP = TT + 1, Q = (CIB / 16) * COB, P = 256 / Q;
+    static_assert(Q <= 256 && 256 % Q == 0 && (Q >= 64 || 64 % Q == 0), "thread layout");
+    __shared__ float xs[CIB * XP];
+    __shared__ float ds[COB * RR];
+    const int tid = threadIdx.x;
+    const int q = tid % Q, pl = tid / Q;
+    const int col = q % COB, cig = q / COB;
+    const int nco = cout / COB;
+    const int ci0 = (blockIdx.y / nco) * CIB, co0 = (blockIdx.y % nco) * COB;
+    const int W2 = 2 * H;
+    const size_t plane = (size_t)H * H, oplane = 4 * plane;
+    const int tiles_env = tiles_x * tiles_x;
+
+    float acc[16][9];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) acc[i][k] = 0.f;
+
+    const int t0 = blockIdx.x * tps, t1 = min(t0 + tps, total_tiles);
+    for (int t = t0; t < t1; ++t) {
+        const int env = t / tiles_env, rem = t - env * tiles_env;
+        const int iy0 = (rem / tiles_x) * T, ix0 = (rem % tiles_x) * T;
+        const float* xe = x + ((size_t)env * cin + ci0) * plane;
+        const float* de = du + ((size_t)env * cout + co0) * oplane;
+        __syncthreads();
+        for (int i = tid; i < CIB * TT; i += 256) {
+            const int c = i / TT, p = i - c * TT;
+            const int gy = iy0 + p / T, gx = ix0 + p % T;
+            float v = 0.f;
+            if (gy < H && gx < H) v = xe[c * plane + (size_t)gy * H + gx];
+            xs[c * XP + p] = v;
+        }
+        for (int i = tid; i < COB * RR; i += 256) {
+            const int c = i / RR, r = i - c * RR;
+            const int ry = r / R, rx = r - ry * R;
+            const int gy = 2 * iy0 - 1 + ry, gx = 2 * ix0 - 1 + rx;
+            float v = 0.f;
+            if (gy >= 0 && gy < W2 && gx >= 0 && gx < W2) v = de[c * oplane + (size_t)gy * W2 + gx];
+            ds[i] = v;
+        }
+        __syncthreads();
+        for (int p = pl; p < TT; p += P) {
+            const float* dp = ds + col * RR + 2 * (p / T) * R + 2 * (p % T);
+            float d[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) d[k] = dp[(k / 3) * R + k % 3];
+            const float* xp = xs + cig * 16 * XP + p;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float xv = xp[i * XP];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) acc[i][k] = fmaf(xv, d[k], acc[i][k]);
+            }
+        }
+    }
+    if constexpr (Q < 64) {  // the pixel lanes of a wave, in a fixed order
+#pragma unroll
+        for (int d = Q; d < 64; d <<= 1)
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+#pragma unroll
+                for (int k = 0; k < 9; ++k) acc[i][k] += __shfl_xor(acc[i][k], d);
+        if (tid % 64 >= Q) return;
+    }
+    constexpr int PB = 256 / (Q < 64 ? 64 : Q);
+    const int pb = Q < 64 ? tid / 64 : pl;
+    const size_t nout = (size_t)cin * 9 * cout;
+    float* dst = part + ((size_t)blockIdx.x * PB + pb) * nout + (size_t)(ci0 + cig * 16) * 9 * cout + co0 + col;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dst[(size_t)(i * 9 + k) * cout] = acc[i][k];
+}
+
+// out[e] = part[0][e] + part[1][e] + ..: four interleaved f64 chains (partials s, s + 4, ..), then the four in order.
+__global__ __launch_bounds__(256) void occ_dec_bwd_sum_kernel(const float* __restrict__ part, int nparts, int nout,
+                                                              float* __restrict__ out) {
+    __shared__ double red[4][64];
+    const int lane = threadIdx.x % 64, sub = threadIdx.x / 64;
+    const int e = blockIdx.x * 64 + lane;
+    double sum = 0.0;
+    if (e < nout)
+        for (int p = sub; p < nparts; p += 4) sum += (double)part[(size_t)p * nout + e];
+    red[sub][lane] = sum;
+    __syncthreads();
+    if (sub == 0 && e < nout) out[e] = (float)(((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+// The (ci, co) tile, pixel tile and K split of the weight gradient of decoder level j (cout = 128 >> j).
+struct BwdDwPlan {
+    int T, cib, cob, pb, grid_y, tiles_x, total_tiles, tps, slices;
+    size_t part_bytes;
+};
+
+inline BwdDwPlan bwd_dw_plan(int j, int H, int n) {
+    const int cout = kEncCh << (kEncLevels - 1 - j), cin = 2 * cout;
+    BwdDwPlan p;
+    if (cout >= 64) p.T = 4, p.cib = 64, p.cob = 64;
+    else if (cout == 32) p.T = 4, p.cib = 64, p.cob = 32;
+    else if (cout == 16) p.T = 8, p.cib = 32, p.cob = 16;
+    else p.T = 8, p.cib = 16, p.cob = 8;
+    const int q = (p.cib / 16) * p.cob;
+    p.pb = 256 / (q < 64 ? 64 : q);
+    p.grid_y = (cin / p.cib) * (cout / p.cob);
+    p.tiles_x = (H + p.T - 1) / p.T;
+    p.total_tiles = n * p.tiles_x * p.tiles_x;
+    const int want = kBwdDwBlocks / p.grid_y;
+    p.tps = (p.total_tiles + want - 1) / want;
+    p.slices = (p.total_tiles + p.tps - 1) / p.tps;
+    p.part_bytes = (size_t)p.slices * p.pb * cin * 9 * cout * sizeof(float);
+    return p;
+}
+
+inline int bwd_chunks(int plane) { return (plane + kBwdChunk - 1) / kBwdChunk; }
+
+// workspace of occ_segment_train_forward / occ_segment_backward: the workspace of occ_segment_forward (b0 | b1 | partials |
+// skips | last; b0 and b1 serve the encoder only), then per level j: y_j | r_j, then p, then the two gradient buffers
+// g0 (the size of y_4) and g1 (the size of y_3) that dY / dU of the levels alternate in.
+struct TrainWs {
+    SegWs seg;
+    size_t lvl_bytes[kEncLevels], p_bytes, total, scratch;
+};
+
+inline TrainWs train_ws_layout(int img, int n) {
+    TrainWs l;
+    l.seg = seg_ws_layout(img, n);
+    l.total = l.seg.total;
+    l.scratch = 0;
+    int H = img >> kEncLevels;
+    for (int j = 0; j < kEncLevels; ++j) {
+        const int c = kEncCh << (kEncLevels - 1 - j);
+        l.lvl_bytes[j] = enc_align((size_t)n * c * (2 * H) * (2 * H) * sizeof(float));
+        l.total += 2 * l.lvl_bytes[j];
+        const size_t act = (size_t)c * n * bwd_chunks(4 * H * H) * 5 * sizeof(double);
+        const size_t dw = bwd_dw_plan(j, H, n).part_bytes;
+        l.scratch = act > l.scratch ? act : l.scratch;
+        l.scratch = dw > l.scratch ? dw : l.scratch;
+        H *= 2;
+    }
+    l.p_bytes = enc_align((size_t)n * img * img * sizeof(float));
+    l.total += l.p_bytes + l.lvl_bytes[kEncLevels - 1] + l.lvl_bytes[kEncLevels - 2];
+    return l;
+}
+
+struct TrainPtrs {
+    float *last, *skip[kEncLevels], *y[kEncLevels], *r[kEncLevels], *p, *g[2];
+};
+
+inline TrainPtrs train_ptrs(const TrainWs& l, char* ws) {
+    TrainPtrs t;
+    char* at = ws + 2 * l.seg.buf_bytes + l.seg.part_bytes;
+    for (int lv = 0; lv < kEncLevels; ++lv) {
+        t.skip[lv] = (float*)at;
+        at += l.seg.skip_bytes[lv];
+    }
+    t.last = (float*)at;
+    at += l.seg.last_bytes;
+    for (int j = 0; j < kEncLevels; ++j) {
+        t.y[j] = (float*)at;
+        t.r[j] = (float*)(at + l.lvl_bytes[j]);
+        at += 2 * l.lvl_bytes[j];
+    }
+    t.p = (float*)at;
+    at += l.p_bytes;
+    t.g[0] = (float*)at;
+    t.g[1] = (float*)(at + l.lvl_bytes[kEncLevels - 1]);
+    return t;
+}
+
+static void dec_launch_up_train(const float* x, float* y, float* r, const float* skip, const float* w, int cin, int cout, int H,
+                                int n, const float* cls, float* prob, float* pkeep, hipStream_t st) {
+    const int T = H >= 16 ? 16 : 8;  // the grids of dec_launch_up
+    const int tiles_x = (H + T - 1) / T;
+    if (cls) {
+        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, 8, true>), dim3(tiles_x * tiles_x, 1, n), dim3(256), 0, st, x, y, r, skip, w,
+                           cin, cout, H, tiles_x, cls, prob, pkeep);
+        return;
+    }
+    constexpr int COG = 16;
+    if (T == 16) {
+        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, COG, false>), dim3(tiles_x * tiles_x, cout / COG, n), dim3(256), 0, st, x, y, r,
+                           skip, w, cin, cout, H, tiles_x, nullptr, nullptr, nullptr);
+    } else {
+        const int ng = cout / COG < 4 ? cout / COG : 4;
+        hipLaunchKernelGGL((occ_dec_up_train_kernel<8, COG, false>), dim3(tiles_x * tiles_x, cout / (COG * ng), n), dim3(64 * ng), 0,
+                           st, x, y, r, skip, w, cin, cout, H, tiles_x, nullptr, nullptr, nullptr);
+    }
+}
+
+// Encoder (17 launches) + decoder (5 launches), every decoder activation kept.
+static void seg_train_forward(int img, int dil, bool residual, bool separable, const float* enc_packed, const float* dec_packed,
+                              const float* obs, int n, char* ws, float* feats, float* prob, hipStream_t st) {
+    const TrainWs l = train_ws_layout(img, n);
+    const TrainPtrs t = train_ptrs(l, ws);
+    EncKeep keep;
+    for (int lv = 0; lv < kEncLevels; ++lv) keep.skip[lv] = t.skip[lv];
+    keep.last = t.last;
+    enc_forward(img, dil, residual, separable, enc_packed, obs, n, ws, feats, st, &keep);
+
+    const float* w = dec_packed;
+    const float* cls = dec_packed + dec_packed_floats() - (kEncCh + 1);
+    const float* x = t.last;
+    int H = img >> kEncLevels;
+    for (int j = 0; j < kEncLevels; ++j) {
+        const int lv = kEncLevels - 1 - j;
+        const int c = kEncCh << lv;
+        const bool last = j == kEncLevels - 1;
+        dec_launch_up_train(x, t.y[j], t.r[j], t.skip[lv], w, 2 * c, c, H, n, last ? cls : nullptr, prob, t.p, st);
+        w += 9LL * 2 * c * c + 3LL * c;
+        x = t.y[j];
+        H *= 2;
+    }
+}
+
+template <int T, int CIB, int COB>
+static void bwd_launch_dw(const BwdDwPlan& p, const float* x, const float* du, float* part, int cin, int cout, int H,
+                          hipStream_t st) {
+    hipLaunchKernelGGL((occ_dec_bwd_dw_kernel<T, CIB, COB>), dim3(p.slices, p.grid_y), dim3(256), 0, st, x, du, part, cin, cout, H,
+                       p.tiles_x, p.total_tiles, p.tps);
+}
+
+// The backward of the latest seg_train_forward on this workspace: per level, last first, the activation step (2 launches),
+// the weight gradient (2 launches) and, above level 0, the input gradient: 24 launches.  grad_packed is overwritten.
+static void seg_backward(int img, const float* dec_packed, int n, char* ws, const float* grad_prob, char* scratch,
+                         float* grad_packed, hipStream_t st) {
+    const TrainWs l = train_ws_layout(img, n);
+    const TrainPtrs t = train_ptrs(l, ws);
+    long long woff[kEncLevels];
+    long long off = 0;
+    for (int j = 0; j < kEncLevels; ++j) {
+        const int c = kEncCh << (kEncLevels - 1 - j);
+        woff[j] = off;
+        off += 9LL * 2 * c * c + 3LL * c;
+    }
+    float* gcls = grad_packed + off;
+    const float* cls = dec_packed + off;
+    for (int j = kEncLevels - 1; j >= 0; --j) {
+        const int c = kEncCh << (kEncLevels - 1 - j), cin = 2 * c;
+        const int H = (img >> kEncLevels) << j, plane = 4 * H * H;
+        const bool last = j == kEncLevels - 1;
+        const float* w = dec_packed + woff[j];
+        float* gw = grad_packed + woff[j];
+        float* gbias = gw + 9LL * cin * c;
+        float* g = t.g[(kEncLevels - 1 - j) % 2];
+        const float* x = j == 0 ? t.last : t.y[j - 1];
+        const int chunks = bwd_chunks(plane);
+        const dim3 agrid(chunks, c, n);
+        const BwdActDst dst = {{gbias + c, gbias + 2 * c, gbias, gcls, gcls + kEncCh}};
+        if (last)
+            hipLaunchKernelGGL((occ_dec_bwd_act_kernel<true>), agrid, dim3(256), 0, st, g, t.r[j], w + 9LL * cin * c + c, c, plane,
+                               grad_prob, t.p, t.y[j], cls, (double*)scratch);
+        else
+            hipLaunchKernelGGL((occ_dec_bwd_act_kernel<false>), agrid, dim3(256), 0, st, g, t.r[j], w + 9LL * cin * c + c, c, plane,
+                               nullptr, nullptr, nullptr, nullptr, (double*)scratch);
+        hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(c, last ? 5 : 3), dim3(64), 0, st, (const double*)scratch, n * chunks,
+                           last ? 5 : 3, dst);
+        const BwdDwPlan p = bwd_dw_plan(j, H, n);
+        float* part = (float*)scratch;
+        if (c >= 64) bwd_launch_dw<4, 64, 64>(p, x, g, part, cin, c, H, st);
+        else if (c == 32) bwd_launch_dw<4, 64, 32>(p, x, g, part, cin, c, H, st);
+        else if (c == 16) bwd_launch_dw<8, 32, 16>(p, x, g, part, cin, c, H, st);
+        else bwd_launch_dw<8, 16, 8>(p, x, g, part, cin, c, H, st);
+        const int nout = 9 * cin * c;
+        hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, part, p.slices * p.pb, nout, gw);
+        if (j > 0) {
+            float* dx = t.g[(kEncLevels - j) % 2];  // dY of level j - 1
+            const int T = H >= 16 ? 16 : 8;
+            const int tiles_x = (H + T - 1) / T;
+            if (T == 16) {
+                hipLaunchKernelGGL((occ_dec_bwd_dx_kernel<16>), dim3(tiles_x * tiles_x, cin / kBwdDxCIG, n), dim3(256), 0, st, g, dx, w,
+                                   cin, c, H, tiles_x);
+            } else {
+                const int ng = cin / kBwdDxCIG < 4 ? cin / kBwdDxCIG : 4;
+                hipLaunchKernelGGL((occ_dec_bwd_dx_kernel<8>), dim3(tiles_x * tiles_x, cin / (kBwdDxCIG * ng), n), dim3(64 * ng), 0, st,
+                                   g, dx, w, cin, c, H, tiles_x);
+            }
+        }
+    }
+}

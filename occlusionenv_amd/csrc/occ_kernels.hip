@@ -31,6 +31,8 @@
 //                       conv, last down fused with the average pool
 //   occ_dec_up_kernel   the segmentation decoder of the same network (occ_decoder.hpp): transposed conv + skip add per
 //                       launch, classifier and sigmoid fused into the last; occ_seg_metrics_kernel: accuracy / IoU counts
+//   occ_dec_bwd_*       training of that decoder with the encoder frozen (occ_decoder_bwd.hpp): a forward that keeps its
+//                       activations, then activation step, input gradient and weight gradient per level, fixed-order sums
 //   occ_seg_criterion_* the pretrainer's criterion on that map (occ_criterion.hpp): Dice / BCE sums and the counts in one
 //                       read, fixed-order f64 sums, and the gradient with respect to the prediction
 //
@@ -58,6 +60,7 @@ namespace occ {
 #include "occ_ppo.hpp"
 #include "occ_encoder.hpp"
 #include "occ_decoder.hpp"
+#include "occ_decoder_bwd.hpp"
 #include "occ_criterion.hpp"
 
 }  // namespace occ
@@ -655,6 +658,41 @@ extern "C" int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc
     if (ws_bytes < need) return OCC_ERR_ARG;
     seg_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, obs, n_env, (char*)ws,
                 feats, prob, logit, dec_feat, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- decoder training (occ_decoder_bwd.hpp) ------------------------------------------------------------------------------
+extern "C" int occ_segment_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
+    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || n_env <= 0 || n_env > 65535 || !ws_bytes || !scratch_bytes) return OCC_ERR_ARG;
+    const TrainWs l = train_ws_layout(cfg->img, n_env);
+    *ws_bytes = l.total;
+    *scratch_bytes = l.scratch;
+    return OCC_OK;
+}
+
+extern "C" int occ_segment_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
+                                         const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
+                                         void* stream) {
+    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || !enc_packed || !dec_packed || !obs || n_env <= 0 || n_env > 65535 || !ws ||
+        !feats || !prob)
+        return OCC_ERR_ARG;
+    if ((((uintptr_t)ws & 15) | ((uintptr_t)prob & 7)) != 0) return OCC_ERR_ARG;
+    if (ws_bytes < train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
+    seg_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, obs, n_env,
+                      (char*)ws, feats, prob, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_segment_backward(const OccEncoderConfig* cfg, const float* dec_packed, int n_env, void* ws, size_t ws_bytes,
+                                    const float* grad_prob, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream) {
+    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || !dec_packed || n_env <= 0 || n_env > 65535 || !ws || !grad_prob || !scratch ||
+        !grad_packed)
+        return OCC_ERR_ARG;
+    // the planes are read as float4, the partials are doubles
+    if ((((uintptr_t)ws | (uintptr_t)grad_prob) & 15) != 0 || ((uintptr_t)scratch & 15) != 0) return OCC_ERR_ARG;
+    const TrainWs l = train_ws_layout(cfg->img, n_env);
+    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
+    seg_backward(cfg->img, dec_packed, n_env, (char*)ws, grad_prob, (char*)scratch, grad_packed, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

@@ -176,6 +176,17 @@ def pack_decoder(sd, prefix: str, classifier: str):
     return buf
 
 
+DECODER_TENSORS = ("conv.weight", "conv.bias", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var")
+
+
+def decoder_tensors(sd, prefix: str, classifier: str) -> dict:
+    """The unfolded tensors ``pack_decoder`` reads, under their full state-dict keys (what ``seghead.SegmentationHead``
+    trains and ``FrozenEncoder.with_decoder`` takes back); call after ``pack_decoder`` has checked them."""
+    keys = [f"{prefix}{j}.up.{t}" for j, _cin, _cout in decoder_plan() for t in DECODER_TENSORS]
+    keys += [classifier + "weight", classifier + "bias"]
+    return {k: torch.as_tensor(sd[k]).detach().to("cpu").clone() for k in keys}
+
+
 class FrozenEncoder:
     """Native inference of the frozen encoder: ``enc(obs)`` (N,4,S,S) f32 on the GPU -> (N,256) f32 pooled features,
     the callable ``BatchedPPO(encoder=...)`` takes; ``enc.predict_grad(obs)`` -> (N,2) from the grad head.
@@ -184,7 +195,8 @@ class FrozenEncoder:
     every env's features are computed independently, so the chunking changes no bit."""
 
     def __init__(self, packed: np.ndarray, separable: bool, dilation: int, residual: bool, preset: str, grad_head=None,
-                 heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None, decoder=None):
+                 heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None, decoder=None,
+                 decoder_state: Optional[dict] = None):
         if dilation not in (1, 2):
             raise ValueError(f"dilation must be 1 or 2, got {dilation}")
         if int(max_chunk) < 1:
@@ -210,6 +222,7 @@ class FrozenEncoder:
         self.heads = heads or {}
         self._ws = {}  # (kind, chunk size, S) -> workspace
         self.dec_packed_host = self.dec_packed = None
+        self.decoder_state = decoder_state  # the decoder's unfolded tensors by state-dict key (None without a decoder)
         if decoder is not None:
             self.dec_packed_host = np.ascontiguousarray(decoder, dtype=np.float32)
             if lib.occ_decoder_packed_floats(C.byref(cfg)) != self.dec_packed_host.size:
@@ -237,11 +250,12 @@ class FrozenEncoder:
                              "'segmenter' for such a checkpoint, use preset='ppo'")
         prefix, ghead, _tanh, d0, r0 = PRESETS[preset]
         separable, packed, offsets = pack_state_dict(sd, prefix)
-        decoder = None
+        decoder = decoder_state = None
         if preset in DECODER_KEYS:
             dprefix, dcls = DECODER_KEYS[preset]
             if any(k.startswith(dprefix) or k.startswith(dcls) for k in sd):
                 decoder = pack_decoder(sd, dprefix, dcls)
+                decoder_state = decoder_tensors(sd, dprefix, dcls)
         grad_head = None
         if ghead is not None and ghead + "weight" in sd:
             grad_head = (_get(sd, ghead + "weight", (2, FEATURES)), _get(sd, ghead + "bias", (2,)))
@@ -250,7 +264,24 @@ class FrozenEncoder:
             if name + "weight" in sd:
                 heads[name[:-1]] = (_get(sd, name + "weight", (rows, FEATURES)), _get(sd, name + "bias", (rows,)))
         return cls(packed, separable, d0 if dilation is None else int(dilation), r0 if residual is None else bool(residual),
-                   preset, grad_head, heads, device, max_chunk, offsets, decoder)
+                   preset, grad_head, heads, device, max_chunk, offsets, decoder, decoder_state)
+
+    def with_decoder(self, sd) -> "FrozenEncoder":
+        """A ``FrozenEncoder`` with this one's encoder (the packed weights are shared, not copied) and the decoder of
+        ``sd``, a state dict holding the decoder and classifier keys of this preset (``DECODER_KEYS``), such as
+        ``seghead.SegmentationHead.state_dict()`` after fine-tuning.  This encoder is left as it is."""
+        import copy
+
+        if self.preset not in DECODER_KEYS:
+            raise ValueError(f"preset {self.preset!r} has no segmentation decoder")
+        dprefix, dcls = DECODER_KEYS[self.preset]
+        packed = pack_decoder(sd, dprefix, dcls)
+        new = copy.copy(self)
+        new._ws = {}
+        new.dec_packed_host = np.ascontiguousarray(packed, dtype=np.float32)
+        new.dec_packed = torch.from_numpy(new.dec_packed_host).to(self.device)
+        new.decoder_state = decoder_tensors(sd, dprefix, dcls)
+        return new
 
     @classmethod
     def from_module(cls, m, device="cuda", max_chunk: int = 256) -> "FrozenEncoder":

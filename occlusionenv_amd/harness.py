@@ -9,6 +9,8 @@
   * ``evaluate_segmentation`` -- the measuring half of pretrainer.py:176-189 (``val``) against the live environment
     instead of a stored dataset: the predicted occlusion map of a FullNetwork checkpoint against the occlusion image
     every step renders anyway.
+  * ``finetune_segmentation`` -- the learning half of the same loop (pretrainer.py:91,120-141): every step's occlusion image is
+    the target of one AdamW step on the segmentation head (``seghead.SegmentationHead``), the encoder frozen.
   * ``validate_pretrained`` -- pretrainer.py:162-204 (``val``) itself, on a stored dataset: Loss / Dice / MSE / Accuracy /
     IoU as the means of the per-batch values.
 """
@@ -106,6 +108,42 @@ def evaluate_segmentation(venv, enc, steps: int, policy: Optional[Callable] = No
     return dict(accuracy=100.0 * correct / pixels if pixels else float("nan"),
                 iou=100.0 * inter / union if union else float("nan"), correct=correct, intersection=inter, union=union,
                 pixels=pixels)
+
+
+def finetune_segmentation(venv, enc_or_head, steps: int, lr: float = 1e-3, weight_decay: float = 1e-5, use_dice: bool = True,
+                          policy: Optional[Callable] = None) -> dict:
+    """The loop of ``evaluate_segmentation`` with a learning step inside: every step renders, takes the engine's occlusion
+    map (the alpha channel of ``full_state``) as the target, applies ``binary_dice_loss`` (``use_dice``) or
+    ``binary_cross_entropy`` to ``head(obs)``, runs ``backward`` and one ``torch.optim.AdamW`` step (the optimizer of
+    pretrainer.py:91) on the head's parameters.  ``enc_or_head``: a ``SegmentationHead``, or a ``FrozenEncoder`` with a
+    decoder, from which one is made.  The decoder's BatchNorm keeps its running statistics (``seghead``).  Returns ``head``,
+    the per-step ``losses`` and the per-step ``accuracy`` / ``iou`` in percent of the prediction the step learned from
+    (``segmentation.seg_criterion``'s counts), as lists of floats; one host sync, at the end."""
+    from . import segmentation
+    from .seghead import SegmentationHead
+
+    head = enc_or_head if isinstance(enc_or_head, SegmentationHead) else SegmentationHead.from_encoder(enc_or_head)
+    opt = torch.optim.AdamW(head.parameters(), lr=lr, weight_decay=weight_decay)
+    obs = venv.reset()
+    n = int(obs.shape[0])
+    action = torch.zeros(n, 2, device=obs.device)
+    rows = []
+    for _ in range(int(steps)):
+        obs, _rewards, _dones, infos = venv.step(action)
+        obs = obs[:, 0] if obs.dim() == 5 else obs
+        occl = torch.cat([infos[i]["full_state"] for i in range(n)])[..., 3]
+        opt.zero_grad(set_to_none=True)
+        pooled, segm = head(obs, return_features=True)
+        loss = segmentation.binary_dice_loss(segm, occl) if use_dice else segmentation.binary_cross_entropy(segm, occl)
+        loss.backward()
+        opt.step()
+        c = segmentation.seg_criterion(segm, occl)
+        correct, inter, union = c["correct"].sum().double(), c["intersection"].sum().double(), c["union"].sum().double()
+        rows.append(torch.stack([loss.detach().double(), 100.0 * correct / float(occl.numel()), 100.0 * inter / union]))
+        if policy is not None:
+            action = policy(pooled)[0].detach()
+    host = torch.stack(rows).cpu().tolist() if rows else []
+    return dict(head=head, losses=[r[0] for r in host], accuracy=[r[1] for r in host], iou=[r[2] for r in host], steps=len(host))
 
 
 @torch.no_grad()

@@ -1,0 +1,152 @@
+"""Host-side checks of the decoder training path (csrc/occ_decoder_bwd.hpp, occlusionenv_amd/seghead.py): the three entry
+points are exported and check their arguments before anything is launched, the workspace query covers what the backward
+needs, and the mapping between the packed gradient and the parameters is right.  No GPU."""
+import ctypes as C
+
+import torch
+import torch.nn.functional as F
+
+from occlusionenv_amd import _native as nat
+
+TRAIN_SYMBOLS = ("occ_segment_train_workspace_query", "occ_segment_train_forward", "occ_segment_backward")
+P16 = C.c_void_p(4096)  # never dereferenced: every call below is rejected before a launch
+
+
+def _cfg(img=64):
+    cfg = nat.OccEncoderConfig()
+    cfg.img, cfg.dilation, cfg.residual, cfg.separable = img, 2, 1, 1
+    return cfg
+
+
+def _query(lib, img, n):
+    ws, sc = C.c_size_t(), C.c_size_t()
+    assert lib.occ_segment_train_workspace_query(C.byref(_cfg(img)), n, C.byref(ws), C.byref(sc)) == 0
+    return int(ws.value), int(sc.value)
+
+
+def test_symbols_exported_and_abi_stays_12():
+    lib = C.CDLL(nat.LIB_PATH)
+    for name in TRAIN_SYMBOLS:
+        assert hasattr(lib, name) and name in nat.SYMBOLS
+    assert nat.load().occ_abi_version() == 12 == nat.ABI_VERSION
+
+
+def test_argument_checks_need_no_gpu():
+    lib = nat.load()
+    ws, sc = C.c_size_t(), C.c_size_t()
+    good, bad = _cfg(64), _cfg(100)
+    assert lib.occ_segment_train_workspace_query(None, 2, C.byref(ws), C.byref(sc)) == 1
+    assert lib.occ_segment_train_workspace_query(C.byref(good), 2, None, C.byref(sc)) == 1
+    assert lib.occ_segment_train_workspace_query(C.byref(good), 2, C.byref(ws), None) == 1
+    assert lib.occ_segment_train_workspace_query(C.byref(good), 0, C.byref(ws), C.byref(sc)) == 1
+    assert lib.occ_segment_train_workspace_query(C.byref(bad), 2, C.byref(ws), C.byref(sc)) == 1
+    big = 1 << 40
+    # occ_segment_train_forward(cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, stream)
+    full = [C.byref(good), P16, P16, P16, 2, P16, big, P16, P16, None]
+    for i in (0, 1, 2, 3, 5, 7, 8):
+        args = list(full)
+        args[i] = None
+        assert lib.occ_segment_train_forward(*args) == 1, i
+    assert lib.occ_segment_train_forward(C.byref(bad), *full[1:]) == 1
+    assert lib.occ_segment_train_forward(*full[:4], 0, *full[5:]) == 1
+    need_ws, need_sc = _query(lib, 64, 2)
+    short = list(full)
+    short[6] = need_ws - 1
+    assert lib.occ_segment_train_forward(*short) == 1
+    # occ_segment_backward(cfg, dec_packed, n_env, ws, ws_bytes, grad_prob, scratch, scratch_bytes, grad_packed, stream)
+    full = [C.byref(good), P16, 2, P16, big, P16, P16, big, P16, None]
+    for i in (0, 1, 3, 5, 6, 8):
+        args = list(full)
+        args[i] = None
+        assert lib.occ_segment_backward(*args) == 1, i
+    assert lib.occ_segment_backward(C.byref(bad), *full[1:]) == 1
+    for i, short_by in ((4, need_ws - 1), (7, need_sc - 1)):
+        args = list(full)
+        args[i] = short_by
+        assert lib.occ_segment_backward(*args) == 1, i
+
+
+def _kept_bytes(img, n):
+    """x_j and r_j of every level, y_4 and prob, as f32."""
+    floats = n * 256 * (img // 32) ** 2  # x_0: the encoder's last down output
+    for j in range(5):
+        c, side = 128 >> j, (img // 16) << j
+        y = n * c * side * side
+        floats += 2 * y  # r_j, and y_j = x_{j+1} (y_4, the decoder feature, at the last level)
+    return 4 * (floats + n * img * img)
+
+
+def test_workspace_query_covers_the_kept_tensors():
+    lib = nat.load()
+    prev = 0
+    for n in (1, 2, 5, 64):
+        ws, sc = _query(lib, 128, n)
+        assert ws > prev and sc > 0
+        prev = ws
+        seg = C.c_size_t()
+        assert lib.occ_segment_workspace_query(C.byref(_cfg(128)), n, C.byref(seg)) == 0
+        assert ws >= _kept_bytes(128, n) and ws > seg.value
+    for img in (32, 96, 512):
+        assert _query(lib, img, 3)[0] >= _kept_bytes(img, 3)
+
+
+def test_packed_gradient_round_trip():
+    from occlusionenv_amd.encoder import decoder_packed_floats, decoder_plan
+    from occlusionenv_amd.seghead import pack_decoder_buffer, unpack_decoder_buffer
+
+    g = torch.Generator().manual_seed(1)
+    buf = torch.randn(decoder_packed_floats(), generator=g)
+    levels, cls_w, cls_b = unpack_decoder_buffer(buf)
+    assert [tuple(l[0].shape) for l in levels] == [(cin, cout, 3, 3) for _j, cin, cout in decoder_plan()]
+    assert cls_w.shape == (1, 8, 1, 1) and cls_b.shape == (1,)
+    assert torch.equal(pack_decoder_buffer(levels, cls_w, cls_b), buf)
+    # the layout is the one pack_decoder documents: w[ci][ky * 3 + kx][co], then bias | scale | shift
+    w0, b0, s0, t0 = levels[0]
+    assert float(w0[5, 7, 2, 1]) == float(buf[(5 * 9 + 2 * 3 + 1) * 128 + 7])
+    off = 9 * 256 * 128
+    assert torch.equal(b0, buf[off:off + 128]) and torch.equal(s0, buf[off + 128:off + 256]) and torch.equal(t0, buf[off + 256:off + 384])
+    assert torch.equal(cls_b, buf[-1:]) and torch.equal(cls_w.reshape(-1), buf[-9:-1])
+
+
+def test_pack_matches_the_encoders_fold():
+    """Packing the unfolded tensors with the fold of seghead equals encoder.pack_decoder on the same state dict."""
+    import numpy as np
+
+    from occlusionenv_amd.encoder import DECODER_KEYS, LEVELS, pack_decoder
+    from occlusionenv_amd.seghead import fold_bn_vectors, pack_decoder_buffer
+    from tests.segmenter_model import golden_seg_state_dict
+    import os
+
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "segmenter_golden.npz"))
+    for preset in ("ppo", "segmenter"):
+        sd = {k: v.float() for k, v in golden_seg_state_dict(g, preset).items()}
+        dp, dc = DECODER_KEYS[preset]
+        levels = []
+        for j in range(LEVELS):
+            st = f"{dp}{j}.up."
+            scale, shift, _ = fold_bn_vectors(sd[st + "bn.weight"], sd[st + "bn.bias"], sd[st + "bn.running_mean"], sd[st + "bn.running_var"])
+            levels.append((sd[st + "conv.weight"], sd[st + "conv.bias"], scale, shift))
+        got = pack_decoder_buffer(levels, sd[dc + "weight"], sd[dc + "bias"])
+        assert np.array_equal(got.numpy(), pack_decoder(sd, dp, dc))
+
+
+def test_bn_parameter_gradients_against_autograd():
+    """dgamma / dbeta from the gradients of the folded affine against f64 autograd through F.batch_norm in eval mode."""
+    from occlusionenv_amd.seghead import bn_param_grads, fold_bn_vectors
+
+    g = torch.Generator().manual_seed(2)
+    c = 16
+    r = torch.relu(torch.randn(3, c, 6, 6, generator=g, dtype=torch.float64))
+    gamma = (torch.rand(c, generator=g, dtype=torch.float64) + 0.5).requires_grad_()
+    beta = torch.randn(c, generator=g, dtype=torch.float64).requires_grad_()
+    mean = torch.randn(c, generator=g, dtype=torch.float64)
+    var = torch.rand(c, generator=g, dtype=torch.float64) + 0.1
+    up = torch.randn(3, c, 6, 6, generator=g, dtype=torch.float64)
+    y = F.batch_norm(r, mean, var, gamma, beta, False, 0.0, 1e-5)
+    (y * up).sum().backward()
+    scale, shift, _rstd = fold_bn_vectors(gamma.detach(), beta.detach(), mean, var)
+    assert torch.allclose(r * scale[None, :, None, None] + shift[None, :, None, None], y.detach(), rtol=1e-13, atol=1e-13)
+    dscale, dshift = (up * r).sum((0, 2, 3)), up.sum((0, 2, 3))  # what the kernels produce: sum dY r, sum dY
+    dgamma, dbeta = bn_param_grads(dscale, dshift, mean, var)
+    assert torch.allclose(dgamma, gamma.grad, rtol=1e-12, atol=1e-12)
+    assert torch.allclose(dbeta, beta.grad, rtol=1e-12, atol=1e-12)
