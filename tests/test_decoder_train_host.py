@@ -150,3 +150,65 @@ def test_bn_parameter_gradients_against_autograd():
     dgamma, dbeta = bn_param_grads(dscale, dshift, mean, var)
     assert torch.allclose(dgamma, gamma.grad, rtol=1e-12, atol=1e-12)
     assert torch.allclose(dbeta, beta.grad, rtol=1e-12, atol=1e-12)
+
+
+def test_scratch_query_equals_the_split_model():
+    """scratch_bytes = max over the levels of (activation partials, weight-gradient partials), tests/decoder_split_model.py."""
+    from tests import decoder_split_model as m
+
+    lib = nat.load()
+    accepted = 0
+    for img in (32, 64, 96, 128, 256, 512):
+        for n in (1, 2, 3, 16, 64, 65, 128, 130, 256):
+            ws, sc = C.c_size_t(), C.c_size_t()
+            rc = lib.occ_segment_train_workspace_query(C.byref(_cfg(img)), n, C.byref(ws), C.byref(sc))
+            if rc != 0:  # a rejected combination says nothing about sizes
+                continue
+            accepted += 1
+            assert int(sc.value) == m.scratch_bytes(img, n), (img, n)
+            # the gradient buffers at the end of the workspace, after everything _kept_bytes counts
+            g = m.level_bytes(img, n)
+            assert int(ws.value) >= _kept_bytes(img, n) + g[4] + g[3], (img, n)
+    assert accepted == 54  # every one of these is inside the documented contract (img % 32 == 0, 1 <= n <= 65535)
+
+
+def test_split_model_on_the_table_of_known_shapes():
+    """Tiles and tiles per slice of the shapes the GPU tests and the published timing use."""
+    from tests import decoder_split_model as m
+
+    def col(img, n, key):
+        return [p[key] for p in m.dw_plans(img, n)]
+
+    assert col(32, 1, "total_tiles") == [1, 1, 1, 1, 4] and col(32, 1, "tps") == [1] * 5
+    assert col(64, 3, "total_tiles") == [3, 3, 12, 12, 48] and col(64, 3, "tps") == [1] * 5
+    assert col(96, 2, "total_tiles") == [2, 8, 18, 18, 72] and col(96, 2, "tps") == [1] * 5
+    assert col(256, 128, "total_tiles") == [512, 2048, 8192, 8192, 32768] and col(256, 128, "tps") == [8, 8, 16, 16, 64]
+    assert col(128, 16, "tps") == [1, 1, 1, 1, 2]  # the harness test: several tiles per block on the last level only
+    for img, n in ((32, 1), (96, 65), (256, 128), (512, 64)):
+        for p in m.dw_plans(img, n):
+            assert p["slices"] * p["grid_y"] <= m.DW_BLOCKS and (p["slices"] - 1) * p["tps"] < p["total_tiles"] <= p["slices"] * p["tps"]
+
+
+def test_split_cases_reach_the_tile_loop():
+    """What the split cases of tests/test_gpu_decoder_train.py have to reach, on the model alone: a change of a tile size
+    or of the block count that takes the reach away fails here."""
+    from tests import decoder_split_model as m
+
+    assert m.SPLIT_CASES == [("ppo", 96, 65), ("segmenter", 64, 130)]
+    plans = {(img, n): m.dw_plans(img, n) for _preset, img, n in m.SPLIT_CASES}
+    assert [p["tps"] for p in plans[(96, 65)]] == [2, 2, 2, 2, 5]
+    assert [p["tps"] for p in plans[(64, 130)]] == [3, 1, 2, 2, 5]
+    levels = [[ps[j] for ps in plans.values()] for j in range(m.LEVELS)]
+    assert all(any(p["tps"] >= 2 for p in lv) for lv in levels)  # every level runs its tile loop more than once somewhere
+    flat = [p for lv in levels for p in lv]
+    assert any(p["short_last"] for p in flat)
+    assert any(p["straddles"] and p["tps"] >= 2 for p in flat)
+    assert any(p["tps"] >= 5 for p in flat)
+    # the one-hot envs of test_gradients_of_one_env: env 64 alone fills the short last slice of level 0; the first slices
+    # that cross an env boundary on levels 2 to 4 end in env 1
+    p96 = plans[(96, 65)]
+    assert p96[0]["short_last"] and p96[0]["tiles_env"] == 1 and p96[0]["total_tiles"] - (p96[0]["slices"] - 1) * p96[0]["tps"] == 1
+    for j in (2, 3, 4):
+        te, tps = p96[j]["tiles_env"], p96[j]["tps"]
+        first = next(s for s in range(p96[j]["slices"]) if (s * tps) // te != (s * tps + tps - 1) // te)
+        assert (first * tps) // te == 0 and (first * tps + tps - 1) // te == 1

@@ -7,13 +7,31 @@ parameters can represent), used as exactly those values in f64 by the host model
 
 Shapes (the smallest that reach every code path): S=32 N=1 (deepest level 1x1: every neighbour is the zero edge; one tile per
 level), S=64 N=3 (several envs in the K split of the weight gradient), S=96 N=2 (H = 3, 6, 12, 24, 48: partial 4-, 8- and
-16-tiles); preset "ppo" on all three, "segmenter" on S=64.
+16-tiles); preset "ppo" on all three, "segmenter" on S=64.  In all of these a block of the weight gradient
+(occ_dec_bwd_dw_kernel) owns one pixel tile.  The split cases give it a slice of several (tests/decoder_split_model.py, whose
+reach is asserted without a GPU in tests/test_decoder_train_host.py): "ppo" S=96 N=65 has 2, 2, 2, 2, 5 tiles per slice on
+levels 0 to 4, a short last slice on levels 0, 2 and 3 and slices that cross an env boundary on levels 2 to 4 (9 and 36 tiles
+per env); "segmenter" S=64 N=130 has 3, 1, 2, 2, 5 with a short last slice on level 0 (the dense preset's f64 encode is
+cheap, so the large N is there).  At "ppo" S=96 N=65 the backward also runs with an upstream gradient in one env alone,
+where a tile given to the wrong env or dropped from the last slice is the whole signal; at "segmenter" S=64 N=130 it runs
+through the C entry points on guarded buffers of exactly the queried sizes, and again after everything it may only write was
+filled with NaNs; at "ppo" S=64 N=3 with the classifier scaled until the stored f32 p is exactly 0 or 1.
 
 Bars.  Kept relu outputs: within 1e-4 max(1, max |r64|) of the f64 relu(u).  Gates r > 0: may differ from the f64 gate only
 where |u64| <= 1e-4 max(1, max |u64|), on at most 1e-3 of the elements; the band itself holds at most 1e-3 of the elements
 for these seeds (asserted).  Gradients: per tensor max |got - want| <= 1e-4 max |want| (no floor), the oracle evaluated with
 the GPU's own gate (relu(u) replaced by u * gate), so that a flipped borderline pixel is judged by the gate test and not
-smeared into every weight sum."""
+smeared into every weight sum.
+
+Measured on an MI355X against the f64 model (worst relative error per tensor kind; the bar is 1e-4):
+                     conv.weight  conv.bias  bn.weight  bn.bias  classifier weight  bias
+  one tile per block   8.8e-7      5.6e-7     1.5e-6    5.5e-7       5.1e-7        1.8e-7
+  split cases          7.2e-7      7.5e-7     7.1e-7    5.3e-7       2.1e-7        1.8e-7
+  one env alone        1.3e-6      3.2e-7     7.9e-7    5.8e-7       1.1e-7        2.4e-8
+  saturated p          1.5e-6      3.3e-7     3.3e-7    2.5e-7       6.6e-8        8.2e-8
+Kept relu outputs at the split cases: 1.9e-6; one gate differed from the f64 gate ("ppo" S=96 N=65, level 1), inside the
+band.  Largest band share 3.7e-4 and 4.1e-4.  With `env` taken from the slice's first tile, or with the tile loop ended after
+one tile, every gradient test of the split cases and both one-env tests fail and every one-tile case still passes."""
 import os
 
 import numpy as np
@@ -21,6 +39,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import criterion_model, decoder_split_model
 from tests.encoder_model import make_obs
 from tests.segmenter_model import PRESETS, encode_full, golden_seg_state_dict, up_conv
 
@@ -29,7 +48,9 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "segmenter_golden.npz")
 TOL = 1e-4
 BAND_SHARE = 1e-3
-CASES = [("ppo", 32, 1), ("ppo", 64, 3), ("ppo", 96, 2), ("segmenter", 64, 3)]
+SPLIT_CASES = [("ppo", 96, 65), ("segmenter", 64, 130)]  # several tiles per block of the weight gradient, see the docstring
+assert SPLIT_CASES == decoder_split_model.SPLIT_CASES  # what they reach is asserted on the host (test_decoder_train_host.py)
+CASES = [("ppo", 32, 1), ("ppo", 64, 3), ("ppo", 96, 2), ("segmenter", 64, 3)] + SPLIT_CASES
 IDS = [f"{p}-S{s}-N{n}" for p, s, n in CASES]
 WORST = {}  # measured worst relative error per tensor kind (printed with -s)
 
@@ -71,6 +92,11 @@ class HostModel:
 
     def forward(self, gates=None):
         """-> (prob, [u_j detached]); ``gates``: relu(u) is replaced by u * gate."""
+        logit, us = self.logit(gates)
+        return torch.sigmoid(logit), us
+
+    def logit(self, gates=None):
+        """-> (logit, [u_j detached]): ``forward`` before the sigmoid."""
         sd, x, us = self.sd, self.x_last, []
         for j, y in enumerate(self.skips[::-1]):
             stem = f"{self.p['decoder']}{j}.up."
@@ -79,8 +105,7 @@ class HostModel:
             r = torch.relu(u) if gates is None else u * gates[j]
             x = F.batch_norm(r, sd[stem + "bn.running_mean"], sd[stem + "bn.running_var"], sd[stem + "bn.weight"],
                              sd[stem + "bn.bias"], False, 0.0, 1e-5) + y
-        logit = F.conv2d(x, sd[self.p["classifier"] + "weight"], sd[self.p["classifier"] + "bias"])
-        return torch.sigmoid(logit), us
+        return F.conv2d(x, sd[self.p["classifier"] + "weight"], sd[self.p["classifier"] + "bias"]), us
 
     def grads(self, loss):
         for v in self.params.values():
@@ -236,6 +261,135 @@ def test_reproducible_overwrite_and_accumulation(runs):
                                                   nat.stream_ptr(up.device)), "occ_segment_backward")
         outs.append(gp)
     assert torch.equal(outs[0], outs[1]) and bool(torch.isfinite(outs[0]).all())
+
+
+@pytest.mark.parametrize("env", [64, 1])
+def test_gradients_of_one_env(runs, env):
+    """The upstream gradient is randn in one env and zero in the others, so that env's tiles are the whole signal: env 64
+    alone fills the short last slice of level 0; env 1 is where the first slices that cross an env boundary on levels 2 to
+    4 end (asserted on the host model, test_decoder_train_host.py)."""
+    preset, img, n = SPLIT_CASES[0]
+    r = runs(preset, img, n)
+    head, host = r["head"], r["host"]
+    up = torch.zeros(n, 1, img, img)
+    up[env] = torch.randn(1, img, img, generator=torch.Generator().manual_seed(_seed(img, n) + 2 + env))
+    head.zero_grad()
+    prob = head(r["obs"])
+    assert torch.equal(prob.detach(), r["prob"])
+    prob.backward(up.cuda())
+    got = _head_grads(head)
+    gates = [(head._kept_relu(j).cpu() > 0).double() for j in range(5)]
+    p64, _us = host.forward(gates)
+    want = host.grads((p64 * up.double()).sum())
+    assert len(want) == 22
+    _check_grads(f"one-hot env {env} {preset} S={img} N={n}", got, want)
+
+
+GUARD = 4096
+
+
+def _guarded(nbytes):
+    """-> (whole, lo): a u8 allocation filled with 0xA5 whose window [lo, lo + nbytes) is 256-byte aligned and has at least
+    GUARD bytes in front of it and behind it."""
+    whole = torch.full((nbytes + 2 * GUARD + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+    lo = GUARD + (-(whole.data_ptr() + GUARD)) % 256
+    return whole, lo
+
+
+def test_no_stale_reads_and_nothing_outside_the_reported_sizes(runs):
+    """The native calls on buffers of exactly the queried sizes, each the middle of a larger allocation that is inspected
+    afterwards; then the backward again after everything it may only write (scratch, the two gradient buffers at the end of
+    the workspace, grad_packed) has been filled with NaNs: the same bits, so nothing read was left over from before."""
+    import ctypes as C
+
+    from occlusionenv_amd import _native as nat
+    from occlusionenv_amd.encoder import FEATURES, decoder_packed_floats
+
+    preset, img, n = SPLIT_CASES[1]
+    r = runs(preset, img, n)
+    enc, obs, up = r["enc"], r["obs"], r["up"].cuda()
+    lib, cfg, st = nat.load(), enc._cfg(img), nat.stream_ptr(obs.device)
+    wsb, scb = C.c_size_t(), C.c_size_t()
+    nat.check(lib.occ_segment_train_workspace_query(C.byref(cfg), n, C.byref(wsb), C.byref(scb)), "occ_segment_train_workspace_query")
+    sizes = dict(ws=int(wsb.value), scratch=int(scb.value), grad_packed=4 * decoder_packed_floats(), prob=4 * n * img * img,
+                 feats=4 * n * FEATURES)
+    assert sizes["scratch"] == decoder_split_model.scratch_bytes(img, n)
+    bufs = {k: _guarded(b) for k, b in sizes.items()}
+    mid = {k: whole[lo:lo + sizes[k]] for k, (whole, lo) in bufs.items()}
+    assert all(m.data_ptr() % 256 == 0 for m in mid.values())
+
+    def backward():
+        nat.check(lib.occ_segment_backward(C.byref(cfg), nat.ptr(enc.dec_packed), n, nat.ptr(mid["ws"]), sizes["ws"], nat.ptr(up),
+                                           nat.ptr(mid["scratch"]), sizes["scratch"], nat.ptr(mid["grad_packed"]), st),
+                  "occ_segment_backward")
+        return mid["grad_packed"].view(torch.float32).clone()
+
+    nat.check(lib.occ_segment_train_forward(C.byref(cfg), nat.ptr(enc.packed), nat.ptr(enc.dec_packed), nat.ptr(obs), n,
+                                            nat.ptr(mid["ws"]), sizes["ws"], nat.ptr(mid["feats"]), nat.ptr(mid["prob"]), st),
+              "occ_segment_train_forward")
+    prob, feats = mid["prob"].clone(), mid["feats"].clone()
+    assert torch.equal(prob.view(torch.float32).view(n, 1, img, img), r["prob"])
+    assert torch.equal(feats.view(torch.float32).view(n, FEATURES), r["feats"])
+    a = backward()
+    lvl = decoder_split_model.level_bytes(img, n)
+    nan = 0x7FC00000
+    assert sizes["scratch"] % 4 == 0
+    mid["scratch"].view(torch.int32).fill_(nan)
+    tail = lvl[4] + lvl[3]  # g0 | g1, the end of the layout in include/occlusionenv_amd.h
+    mid["ws"][sizes["ws"] - tail:].view(torch.int32).fill_(nan)
+    mid["grad_packed"].view(torch.int32).fill_(nan)
+    assert bool(torch.isnan(mid["grad_packed"].view(torch.float32)).all())
+    b = backward()
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(a).all())
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert torch.equal(mid["prob"], prob) and torch.equal(mid["feats"], feats)  # the backward writes neither
+    for k, (whole, lo) in bufs.items():
+        assert lo >= GUARD and whole.numel() - (lo + sizes[k]) >= GUARD
+        assert bool((whole[:lo] == 0xA5).all()), f"bytes in front of {k} were written"
+        assert bool((whole[lo + sizes[k]:] == 0xA5).all()), f"bytes behind {k} were written"
+
+
+@pytest.mark.parametrize("loss", ["dice", "bce"])
+@pytest.mark.parametrize("factor", [64, 512])
+def test_saturated_probabilities(runs, factor, loss):
+    """Classifier weight and bias times ``factor``: the stored f32 p is exactly 1 (and, at 512, exactly 0) on many pixels.
+    The contract is dz = g p (1 - p) from the stored p, so dz = 0 there although BCE's g is of order 1e12 x coef: the oracle
+    takes the GPU's p, g from criterion_model at that p, dz in f64, and back-propagates sum(logit dz) through the host model.
+
+    1 / (1 + expf(-z)) is exactly 1 for z > 17.4 and exactly 0 only once expf overflows, z < -88.8.  This case's logits lie
+    in [-0.262, 1.102], so 64 saturates the upper end only ([-16.8, 70.5]); 512 ([-134, 564]) saturates both."""
+    from occlusionenv_amd import segmentation
+    from occlusionenv_amd.seghead import SegmentationHead
+
+    preset, img, n = "ppo", 64, 3
+    r = runs(preset, img, n)
+    sd, cls = dict(r["sd"]), PRESETS[preset]["classifier"]
+    head = SegmentationHead.from_encoder(r["enc"])
+    with torch.no_grad():
+        for t in ("weight", "bias"):
+            head.get_parameter(cls + t).mul_(float(factor))
+            sd[cls + t] = sd[cls + t] * float(factor)  # a power of two: the same values in f32 and in f64
+    target = r["target"]
+    prob = head(r["obs"])
+    p32 = prob.detach().cpu()
+    one, zero = p32 == 1.0, p32 == 0.0
+    print(f"factor {factor}: {int(one.sum())} pixels with p == 1, {int(zero.sum())} with p == 0, of {p32.numel()}")
+    assert bool((target[one] == 1).any()) and bool((target[one] == 0).any())
+    if factor == 512:
+        assert bool((target[zero] == 1).any()) and bool((target[zero] == 0).any())
+    native = segmentation.binary_dice_loss if loss == "dice" else segmentation.binary_cross_entropy
+    native(prob, target.cuda()).backward()
+    got = _head_grads(head)
+    assert len(got) == 22 and all(bool(torch.isfinite(v).all()) for v in got.values())
+    g = (criterion_model.dice_grad if loss == "dice" else criterion_model.bce_grad)(p32, target)
+    dz = g * p32.double() * (1.0 - p32.double())
+    assert bool((dz[one] == 0).all()) and bool((dz[zero] == 0).all())
+    host = HostModel(sd, preset, r["obs"].double().cpu())
+    gates = [(head._kept_relu(j).cpu() > 0).double() for j in range(5)]
+    logit, _us = host.logit(gates)
+    want = host.grads((logit * dz).sum())
+    _check_grads(f"saturated x{factor} {loss} {preset} S={img} N={n}", got, want)
 
 
 @pytest.fixture(scope="module")
