@@ -449,6 +449,34 @@ int occ_segment_backward(const OccEncoderConfig* cfg, const float* dec_packed, i
                          const float* grad_prob, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream);
 
 /*
+ * Training of the dense encoder through its pooled feature (additive in ABI 12; csrc/occ_encoder_bwd.hpp): what
+ * PredictorNet training (train_predict.py) needs below its Linear(256, 2) head.  Supported: cfg->separable == 0 and
+ * cfg->dilation == 1, cfg->residual 0 or 1, img in [32, 1024] (odd intermediate sides included: they halve with ceiling).
+ * BatchNorm runs with its running statistics: with u = conv(x) + bias, r = relu(u), y = bn_scale r + bn_shift (+ residual),
+ * the parameters that receive a gradient are w, bias, bn_scale, bn_shift of all 16 layers.  No d obs is computed.
+ *
+ * occ_encoder_train_forward is occ_encoder_forward (feats are the same to the bit) that keeps, in ws, every layer's input
+ * and relu output r.  Workspace, every part 256-byte aligned, f32, H_0 = S, H' = ceil(H / 2), c = 8 << lv:
+ *   obs (n,4,S,S) | r_init (n,8,S,S) | per level lv = 0..4: a (n,c,H,H) | r1 | b | r2 | cc | rd (n,2c,H',H') |
+ *   pool partials (n, tiles of the last down, 256) | three gradient buffers of (n,8,S,S)
+ * (a: the block input = the previous down's output; b: Layer 1's output; cc: Layer 2's output plus the residual).
+ * 30.31 MiB per env at 256^2 (128 envs: 3.79 GiB), 121.25 MiB per env at 512^2.  18 launches.
+ *
+ * occ_encoder_backward is the backward of the LATEST occ_encoder_train_forward on ws (same cfg, n_env and packed) for the
+ * upstream gradient grad_feats = d loss / d feats (n_env,256) f32.  grad_packed receives occ_encoder_packed_floats floats
+ * in the layout of packed: per layer dw[ci][ky * 3 + kx][co] | dbias | dbn_scale | dbn_shift; it is OVERWRITTEN, not
+ * accumulated.  The relu gate is the forward's own r > 0.  scratch: device memory of the queried scratch_bytes (block
+ * partials).  No floating-point atomics; block partials are added in a fixed order in f64: every gradient is bitwise the
+ * same from call to call.  79 launches on `stream`, nothing allocated or synchronised.  OCC_ERR_ARG before any launch for
+ * an unsupported cfg, a null pointer, n_env outside [1, 65535], ws or scratch not 16-byte aligned, or a short buffer.
+ */
+int occ_encoder_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes);
+int occ_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env, void* ws,
+                              size_t ws_bytes, float* feats, void* stream);
+int occ_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
+                         const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

@@ -1,0 +1,649 @@
+// occ_encoder_bwd.hpp -- training of the dense (non-separable, dilation 1) encoder through its pooled 256-d feature: a
+// forward that keeps what the backward needs, and the backward with respect to every encoder parameter.  Part of the
+// single translation unit occ_kernels.hip (included inside namespace occ, after occ_encoder.hpp, whose tiling and packed
+// layout it mirrors, and after occ_decoder_bwd.hpp, whose reduction rule and two of whose kernels it reuses).
+//
+// Forward per layer (16 of them: initial, then Layer 1, Layer 2, down per level): u = conv(x) + b, r = relu(u),
+// y = s r + t (+ the block input, Layer 2 of a residual block); feats = mean of the last down's y.  BatchNorm runs with
+// its running statistics (s, t folded by the host).  No d obs is computed.
+//
+//   occ_enc_copy_kernel           obs -> ws (the backward has no obs argument; the initial layer's dW reads the copy).
+//   occ_enc_dense_train_kernel    occ_enc_dense_kernel at dilation 1 with the same FMA order (feats are the same to the
+//                                 bit) which also stores r; POOL (the last down) stores r and the pool partials, no y.
+//   occ_enc_bwd_act_kernel        per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0], written to a buffer of its
+//                                 own (the dY of a residual block's Layer 2 is needed again); POOL: dY = grad_feats[n][c] /
+//                                 (H H), never stored.  f64 block partials of dS = sum dY r, dT = sum dY, dB = sum dU in
+//                                 the layout of occ_dec_bwd_act_kernel; occ_dec_bwd_act_final_kernel adds them in block
+//                                 order.  The gate is the forward's own r > 0.
+//   occ_enc_bwd_dx1_kernel        stride 1: dX[ci][y][x] = sum_co sum_k w[ci][k][co] dU[co][y + 1 - ky][x + 1 - kx] (+ add).
+//                                 A thread owns one pixel for CIG input channels; the (T + 2)^2 dU tile (one-pixel halo,
+//                                 zero outside the image) is staged in LDS 8 output channels at a time; weights are
+//                                 wave-uniform scalar loads of 8 consecutive co.  `add`: the residual's second path.
+//   occ_enc_bwd_dx2_kernel        stride 2: a thread owns the 2 x 2 input quad (2 qy + {0,1}, 2 qx + {0,1}) for 8 input
+//                                 channels and reads dU at (qy + {0,1}, qx + {0,1}): the quad mapping of occ_dec_up_kernel
+//                                 (1, 2, 2 and 4 taps per quad pixel, no zero-stuffed taps, no parity branches).  dU rows /
+//                                 columns >= Ho read as zero; quad pixels >= H are not stored.
+//   occ_enc_bwd_dw_kernel         dW[ci][k][co] = sum_{n,oy,ox} x[ci][s oy - 1 + ky][s ox - 1 + kx] dU[co][oy][ox], a
+//                                 (9 cin) x cout contraction over K = N Ho^2.  A thread owns 1 ci x 9 taps x 8 co (72 f32
+//                                 accumulators); a block owns a CIB x COB tile of (ci, co) and one slice of K (consecutive
+//                                 T x T output-pixel tiles, envs in order); when the tile needs fewer than 256 threads the
+//                                 others take other pixels (P pixel lanes), added inside the wave by __shfl_xor steps in
+//                                 a fixed order.  Every block writes its partial dW (one per wave or pixel lane) to caller
+//                                 scratch; occ_dec_bwd_sum_kernel adds the partials in f64 in a fixed order.
+//
+// Launches: train forward 18 (copy, 16 layers, pool); backward 79 (per layer act, act-final, dW, sum = 64, and the input
+// gradient of the 15 layers above the initial one).  No floating-point atomics; the split of K is a function of
+// (S, N) alone: every gradient is bitwise the same from call to call.  Nothing is allocated or synchronised.
+//
+// Workspace (occ_encoder_train_workspace_query), every part 256-byte aligned, f32, H_0 = S, H_{lv+1} = ceil(H_lv / 2),
+// c = 8 << lv:
+//   obs (n,4,S,S) | r_init (n,8,S,S) |
+//   per level lv: a (n,c,H,H) block input | r1 | b = Layer 1 output | r2 | cc = Layer 2 output (+ a) | rd (n,2c,H',H')
+//                 (a of level lv + 1 is the down's y; the last down stores no y)
+//   | pool partials (n, tiles, 256) | g0 | g1 | g2: three gradient buffers of (n,8,S,S)
+// At 256^2 that is 30.31 MiB per env (1 obs, 23.31 kept activations, 6 gradient): 128 envs take 3.79 GiB.
+
+constexpr int kEncDwBlocks = 512;  // blocks of the weight gradient per layer (K slices x (ci, co) tiles)
+constexpr int kEncDwCot = 8;       // output channels per thread of the weight gradient
+
+__global__ __launch_bounds__(256) void occ_enc_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+}
+
+template <int T, int COG, bool POOL>
+__global__ __launch_bounds__(256) void occ_enc_dense_train_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                  float* __restrict__ rkeep, const float* __restrict__ resid,
+                                                                  const float* __restrict__ w, int cin, int cout, int H,
+                                                                  int Ho, int stride, int tiles_x,
+                                                                  float* __restrict__ partials) {
+    __shared__ float s[kEncLds];
+    constexpr int TT = T * T;
+    const int tid = threadIdx.x;
+    const int p = tid % TT;
+    const int ng = blockDim.x / TT;
+    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
+    const int co0 = (blockIdx.y * ng + g) * COG;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int oy0 = ty * T, ox0 = tx * T;
+    const int py = p / T, px = p % T;
+    const size_t plane = (size_t)H * H;
+    const float* xe = x + (size_t)blockIdx.z * cin * plane;
+    const float* bias = w + (size_t)cin * 9 * cout;
+    const float* bns = bias + cout;
+    const float* bnt = bns + cout;
+    const int R = (T - 1) * stride + 3;
+    const int RR = R * R;
+    const int iy0 = oy0 * stride - 1, ix0 = ox0 * stride - 1;
+
+    float acc[COG];
+#pragma unroll
+    for (int j = 0; j < COG; ++j) acc[j] = 0.f;
+
+    for (int ci0 = 0; ci0 < cin; ci0 += kEncCC) {
+        const int cc = min(kEncCC, cin - ci0);
+        __syncthreads();
+        for (int i = tid; i < cc * RR; i += blockDim.x) {
+            const int c = i / RR, r = i - c * RR;
+            const int ry = r / R, rx = r - ry * R;
+            const int gy = iy0 + ry, gx = ix0 + rx;
+            float v = 0.f;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < H) v = xe[(ci0 + c) * plane + (size_t)gy * H + gx];
+            s[i] = v;
+        }
+        __syncthreads();
+        for (int c = 0; c < cc; ++c) {
+            const int ci = ci0 + c;
+            const float* sc = s + c * RR + (py * stride) * R + px * stride;
+            float in[9];
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) in[ky * 3 + kx] = sc[ky * R + kx];
+            const float* wr = w + (size_t)ci * 9 * cout + co0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k)  // the FMA order of occ_enc_dense_kernel
+#pragma unroll
+                for (int j = 0; j < COG; ++j) acc[j] = fmaf(wr[k * cout + j], in[k], acc[j]);
+        }
+    }
+    const int oy = oy0 + py, ox = ox0 + px;
+    const bool valid = oy < Ho && ox < Ho;
+    const size_t oplane = (size_t)Ho * Ho;
+    const size_t o = (size_t)blockIdx.z * cout * oplane + (size_t)oy * Ho + ox;
+    if constexpr (!POOL) {
+        if (!valid) return;
+#pragma unroll
+        for (int j = 0; j < COG; ++j) {
+            const int co = co0 + j;
+            const float r = fmaxf(acc[j] + bias[co], 0.f);
+            float v = fmaf(r, bns[co], bnt[co]);
+            if (resid) v += resid[o + co * oplane];
+            rkeep[o + co * oplane] = r;
+            y[o + co * oplane] = v;
+        }
+    } else {
+        static_assert(256 * COG <= kEncLds, "the pool stage reuses the LDS stage");
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < COG; ++j) {
+            const int co = co0 + j;
+            const float r = fmaxf(acc[j] + bias[co], 0.f);
+            const float v = fmaf(r, bns[co], bnt[co]);
+            s[(g * COG + j) * TT + p] = valid ? v : 0.f;
+            if (valid) rkeep[o + co * oplane] = r;
+        }
+        __syncthreads();
+        if (tid < ng * COG) {
+            const float* row = s + tid * TT;
+            float sum = 0.f;
+            for (int q = 0; q < TT; ++q) sum += row[q];
+            const int gg = tid / COG, j = tid % COG;
+            const int ntiles = gridDim.x;
+            partials[((size_t)blockIdx.z * ntiles + blockIdx.x) * cout + (blockIdx.y * ng + gg) * COG + j] = sum;
+        }
+    }
+}
+
+// Activation step of one layer.  dy: (n, c, plane) (not read when POOL: dY = gf[env][ch] / count); du: (n, c, plane), may
+// be dy itself.  partials[((ch * n + env) * chunks + chunk) * 3 + k]: k = 0 dS, 1 dT, 2 dB.
+template <bool POOL>
+__global__ __launch_bounds__(256) void occ_enc_bwd_act_kernel(const float* dy, float* du, const float* __restrict__ r,
+                                                              const float* __restrict__ bns, int c, int plane,
+                                                              const float* __restrict__ gf, float count,
+                                                              double* __restrict__ partials) {
+    __shared__ double part[4][3];
+    const int ch = blockIdx.y, env = blockIdx.z;
+    const size_t base = ((size_t)env * c + ch) * plane;
+    const float sc = bns[ch];
+    float pooled = 0.f;
+    if constexpr (POOL) pooled = gf[(size_t)env * c + ch] / count;
+    double sum[3] = {0.0, 0.0, 0.0};
+    const int lo = blockIdx.x * kBwdChunk;
+    for (int j = 0; j < kBwdChunk / 256; ++j) {
+        const int i = lo + (int)threadIdx.x + 256 * j;
+        if (i >= plane) break;
+        const float rv = r[base + i];
+        const float d = POOL ? pooled : dy[base + i];
+        const float u = rv > 0.f ? d * sc : 0.f;
+        sum[0] = fma((double)d, (double)rv, sum[0]);
+        sum[1] += (double)d;
+        sum[2] += (double)u;
+        du[base + i] = u;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sum[k] += __shfl_down(sum[k], d);
+    const int wave = threadIdx.x / 64;
+    if (threadIdx.x % 64 == 0)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) part[wave][k] = sum[k];
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double t = 0.0;
+        for (int k = 0; k < 4; ++k) t += part[k][threadIdx.x];
+        partials[((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * 3 + threadIdx.x] = t;
+    }
+}
+
+// du: (n, cout, H, H); dx, add: (n, cin, H, H); w: the layer's packed w[ci][k][co].  cin % CIG == 0, cout % 8 == 0.
+template <int T, int CIG>
+__global__ __launch_bounds__(256) void occ_enc_bwd_dx1_kernel(const float* __restrict__ du, float* __restrict__ dx,
+                                                              const float* __restrict__ add, const float* __restrict__ w,
+                                                              int cin, int cout, int H, int tiles_x) {
+    constexpr int TT = T * T, R = T + 2, RR = R * R, CC = kBwdDxCC;
+    __shared__ float s[CC * RR];
+    const int tid = threadIdx.x;
+    const int p = tid % TT;
+    const int ng = blockDim.x / TT;
+    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
+    const int ci0 = (blockIdx.y * ng + g) * CIG;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int iy0 = ty * T, ix0 = tx * T;
+    const int py = p / T, px = p % T;
+    const size_t plane = (size_t)H * H;
+    const float* de = du + (size_t)blockIdx.z * cout * plane;
+
+    float acc[CIG];
+#pragma unroll
+    for (int j = 0; j < CIG; ++j) acc[j] = 0.f;
+
+    for (int co0 = 0; co0 < cout; co0 += CC) {
+        __syncthreads();
+        for (int i = tid; i < CC * RR; i += blockDim.x) {
+            const int c = i / RR, r = i - c * RR;
+            const int ry = r / R, rx = r - ry * R;
+            const int gy = iy0 - 1 + ry, gx = ix0 - 1 + rx;
+            float v = 0.f;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < H) v = de[(co0 + c) * plane + (size_t)gy * H + gx];
+            s[i] = v;
+        }
+        __syncthreads();
+        float d[CC][9];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+            const float* sp = s + c * RR + py * R + px;  // staged (y - 1, x - 1); tap k reads dU at (y + 1 - ky, x + 1 - kx)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) d[c][k] = sp[(2 - k / 3) * R + 2 - k % 3];
+        }
+        const float* wr = w + (size_t)ci0 * 9 * cout + co0;
+#pragma unroll
+        for (int j = 0; j < CIG; ++j)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const float* wk = wr + (size_t)(j * 9 + k) * cout;
+#pragma unroll
+                for (int c = 0; c < CC; ++c) acc[j] = fmaf(wk[c], d[c][k], acc[j]);
+            }
+    }
+    const int iy = iy0 + py, ix = ix0 + px;
+    if (iy >= H || ix >= H) return;
+    const size_t o = ((size_t)blockIdx.z * cin + ci0) * plane + (size_t)iy * H + ix;
+#pragma unroll
+    for (int j = 0; j < CIG; ++j) {
+        float v = acc[j];
+        if (add) v += add[o + j * plane];
+        dx[o + j * plane] = v;
+    }
+}
+
+// du: (n, cout, Ho, Ho), Ho = ceil(H / 2); dx: (n, cin, H, H).  cin % 8 == 0, cout % 8 == 0.  A T x T tile of quads.
+template <int T>
+__global__ __launch_bounds__(256) void occ_enc_bwd_dx2_kernel(const float* __restrict__ du, float* __restrict__ dx,
+                                                              const float* __restrict__ w, int cin, int cout, int H, int Ho,
+                                                              int tiles_x) {
+    constexpr int TT = T * T, R = T + 1, RR = R * R, CC = kBwdDxCC, CIG = 8;
+    __shared__ float s[CC * RR];
+    const int tid = threadIdx.x;
+    const int p = tid % TT;
+    const int ng = blockDim.x / TT;
+    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
+    const int ci0 = (blockIdx.y * ng + g) * CIG;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int qy0 = ty * T, qx0 = tx * T;
+    const int py = p / T, px = p % T;
+    const size_t oplane = (size_t)Ho * Ho;
+    const float* de = du + (size_t)blockIdx.z * cout * oplane;
+
+    float acc[4][CIG];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < CIG; ++j) acc[q][j] = 0.f;
+
+    for (int co0 = 0; co0 < cout; co0 += CC) {
+        __syncthreads();
+        for (int i = tid; i < CC * RR; i += blockDim.x) {
+            const int c = i / RR, r = i - c * RR;
+            const int ry = r / R, rx = r - ry * R;
+            const int gy = qy0 + ry, gx = qx0 + rx;
+            float v = 0.f;
+            if (gy < Ho && gx < Ho) v = de[(co0 + c) * oplane + (size_t)gy * Ho + gx];
+            s[i] = v;
+        }
+        __syncthreads();
+        float d[CC][4];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+            const float* sp = s + c * RR + py * R + px;
+            d[c][0] = sp[0], d[c][1] = sp[1], d[c][2] = sp[R], d[c][3] = sp[R + 1];
+        }
+        const float* wr = w + (size_t)ci0 * 9 * cout + co0;
+#pragma unroll
+        for (int j = 0; j < CIG; ++j) {
+            const float* wj = wr + (size_t)j * 9 * cout;  // wj[k * cout + c] = w[ci][k][co0 + c]
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+                const float a = d[c][0], b = d[c][1], cv = d[c][2], dv = d[c][3];
+                // input (2qy + ey, 2qx + ex) meets output (qy + (ey + 1 - ky) / 2, ..) for the taps of matching parity
+                acc[0][j] = fmaf(wj[4 * cout + c], a, acc[0][j]);
+                acc[1][j] = fmaf(wj[3 * cout + c], b, fmaf(wj[5 * cout + c], a, acc[1][j]));
+                acc[2][j] = fmaf(wj[1 * cout + c], cv, fmaf(wj[7 * cout + c], a, acc[2][j]));
+                acc[3][j] = fmaf(wj[0 * cout + c], dv,
+                                 fmaf(wj[2 * cout + c], cv, fmaf(wj[6 * cout + c], b, fmaf(wj[8 * cout + c], a, acc[3][j]))));
+            }
+        }
+    }
+    const int qy = qy0 + py, qx = qx0 + px;
+    const int iy = 2 * qy, ix = 2 * qx;
+    if (iy >= H || ix >= H) return;
+    const size_t plane = (size_t)H * H;
+    float* xe = dx + ((size_t)blockIdx.z * cin + ci0) * plane + (size_t)iy * H + ix;
+    const bool right = ix + 1 < H, below = iy + 1 < H;
+#pragma unroll
+    for (int j = 0; j < CIG; ++j) {
+        xe[j * plane] = acc[0][j];
+        if (right) xe[j * plane + 1] = acc[1][j];
+        if (below) xe[j * plane + H] = acc[2][j];
+        if (right && below) xe[j * plane + H + 1] = acc[3][j];
+    }
+}
+
+// x: (n, cin, H, H); du: (n, cout, Ho, Ho); part: [slice * PB + wave or pixel lane][cin * 9 * cout], PB = 256 / max(Q, 64).
+// A slice is the tiles [blockIdx.x * tps, .. + tps) of the n * tiles_x^2 output-pixel tiles, envs in order.
+template <int T, int CIB, int COB, int STRIDE>
+__global__ __launch_bounds__(256) void occ_enc_bwd_dw_kernel(const float* __restrict__ x, const float* __restrict__ du,
+                                                             float* __restrict__ part, int cin, int cout, int H, int Ho,
+                                                             int tiles_x, int total_tiles, int tps) {
+    constexpr int TT = T * T, R = (T - 1) * STRIDE + 3, RR = R * R, XP = RR | 1, COT = kEncDwCot, Q = CIB * (COB / COT),
+                  P = 256 / Q;
+    static_assert(Q <= 256 && 256 % Q == 0 && (Q >= 64 || 64 % Q == 0) && COB % COT == 0, "thread layout");
+    __shared__ float xs[CIB * XP];
+    __shared__ float ds[COB * TT];
+    const int tid = threadIdx.x;
+    const int q = tid % Q, pl = tid / Q;
+    const int cil = q % CIB, cog = q / CIB;
+    const int nco = cout / COB;
+    const int ci0 = (blockIdx.y / nco) * CIB, co0 = (blockIdx.y % nco) * COB;
+    const size_t plane = (size_t)H * H, oplane = (size_t)Ho * Ho;
+    const int tiles_env = tiles_x * tiles_x;
+
+    float acc[9][COT];
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int j = 0; j < COT; ++j) acc[k][j] = 0.f;
+
+    const int t0 = blockIdx.x * tps, t1 = min(t0 + tps, total_tiles);
+    for (int t = t0; t < t1; ++t) {
+        const int env = t / tiles_env, rem = t - env * tiles_env;
+        const int oy0 = (rem / tiles_x) * T, ox0 = (rem % tiles_x) * T;
+        const float* xe = x + ((size_t)env * cin + ci0) * plane;
+        const float* de = du + ((size_t)env * cout + co0) * oplane;
+        __syncthreads();
+        for (int i = tid; i < CIB * RR; i += 256) {
+            const int c = i / RR, r = i - c * RR;
+            const int ry = r / R, rx = r - ry * R;
+            const int gy = oy0 * STRIDE - 1 + ry, gx = ox0 * STRIDE - 1 + rx;
+            float v = 0.f;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < H) v = xe[c * plane + (size_t)gy * H + gx];
+            xs[c * XP + r] = v;
+        }
+        for (int i = tid; i < COB * TT; i += 256) {
+            const int c = i / TT, p = i - c * TT;
+            const int gy = oy0 + p / T, gx = ox0 + p % T;
+            float v = 0.f;
+            if (gy < Ho && gx < Ho) v = de[c * oplane + (size_t)gy * Ho + gx];
+            ds[i] = v;
+        }
+        __syncthreads();
+        for (int p = pl; p < TT; p += P) {
+            const float* xp = xs + cil * XP + (p / T) * STRIDE * R + (p % T) * STRIDE;
+            float xv[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) xv[k] = xp[(k / 3) * R + k % 3];
+            const float* dp = ds + cog * COT * TT + p;
+#pragma unroll
+            for (int j = 0; j < COT; ++j) {
+                const float d = dp[j * TT];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) acc[k][j] = fmaf(xv[k], d, acc[k][j]);
+            }
+        }
+    }
+    if constexpr (Q < 64) {  // the pixel lanes of a wave, in a fixed order
+#pragma unroll
+        for (int d = Q; d < 64; d <<= 1)
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+#pragma unroll
+                for (int j = 0; j < COT; ++j) acc[k][j] += __shfl_xor(acc[k][j], d);
+        if (tid % 64 >= Q) return;
+    }
+    constexpr int PB = 256 / (Q < 64 ? 64 : Q);
+    const int pb = Q < 64 ? tid / 64 : pl;
+    const size_t nout = (size_t)cin * 9 * cout;
+    float* dst = part + ((size_t)blockIdx.x * PB + pb) * nout + (size_t)(ci0 + cil) * 9 * cout + co0 + cog * COT;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int j = 0; j < COT; ++j) dst[(size_t)k * cout + j] = acc[k][j];
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+// The 16 layers in packed order.
+struct EncLayer {
+    int cin, cout, stride, H, Ho;  // input side, output side
+    long long woff;                // floats into the packed buffer
+};
+
+inline void enc_train_layers(int img, EncLayer* L) {
+    long long off = 0;
+    int H = img, i = 0;
+    auto put = [&](int cin, int cout, int stride) {
+        L[i++] = {cin, cout, stride, H, enc_out_size(H, stride), off};
+        off += enc_layer_floats(cin, cout, false);
+    };
+    put(4, kEncCh, 1);
+    for (int lv = 0; lv < kEncLevels; ++lv) {
+        const int c = kEncCh << lv;
+        put(c, c, 1);
+        put(c, c, 1);
+        put(c, 2 * c, 2);
+        H = enc_out_size(H, 2);
+    }
+}
+
+// The (ci, co) tile, pixel tile and K split of the weight gradient of one layer.
+struct EncDwPlan {
+    int T, cib, cob, pb, grid_y, tiles_x, total_tiles, tps, slices;
+    size_t part_bytes;
+};
+
+inline EncDwPlan enc_dw_plan(int cin, int cout, int Ho, int n) {
+    EncDwPlan p;
+    p.cib = cin < 64 ? cin : 64;
+    p.cob = cout < 32 ? cout : 32;
+    p.T = p.cib == 64 ? 4 : 8;
+    const int q = p.cib * (p.cob / kEncDwCot);
+    p.pb = 256 / (q < 64 ? 64 : q);
+    p.grid_y = (cin / p.cib) * (cout / p.cob);
+    p.tiles_x = (Ho + p.T - 1) / p.T;
+    p.total_tiles = n * p.tiles_x * p.tiles_x;
+    const int want = kEncDwBlocks / p.grid_y;
+    p.tps = (p.total_tiles + want - 1) / want;
+    p.slices = (p.total_tiles + p.tps - 1) / p.tps;
+    p.part_bytes = (size_t)p.slices * p.pb * cin * 9 * cout * sizeof(float);
+    return p;
+}
+
+struct EncTrainWs {
+    size_t obs, r_init, a[kEncLevels], r1[kEncLevels], b[kEncLevels], r2[kEncLevels], cc[kEncLevels], rd[kEncLevels], part, g[3];
+    size_t total, scratch;
+};
+
+inline EncTrainWs enc_train_ws_layout(int img, int n) {
+    EncTrainWs l;
+    size_t at = 0;
+    auto take = [&](size_t floats) {
+        const size_t o = at;
+        at += enc_align(floats * sizeof(float));
+        return o;
+    };
+    const size_t S2 = (size_t)img * img;
+    l.obs = take((size_t)n * 4 * S2);
+    l.r_init = take((size_t)n * kEncCh * S2);
+    int H = img;
+    for (int lv = 0; lv < kEncLevels; ++lv) {
+        const size_t act = (size_t)n * (kEncCh << lv) * H * H;
+        const int Ho = enc_out_size(H, 2);
+        l.a[lv] = take(act);
+        l.r1[lv] = take(act);
+        l.b[lv] = take(act);
+        l.r2[lv] = take(act);
+        l.cc[lv] = take(act);
+        l.rd[lv] = take((size_t)n * (2 * kEncCh << lv) * Ho * Ho);
+        H = Ho;
+    }
+    l.part = take((size_t)n * enc_tiles(H) * kEncFeat);
+    for (int i = 0; i < 3; ++i) l.g[i] = take((size_t)n * kEncCh * S2);
+    l.total = at;
+    l.scratch = 0;
+    EncLayer L[16];
+    enc_train_layers(img, L);
+    for (int i = 0; i < 16; ++i) {
+        const size_t act = (size_t)L[i].cout * n * bwd_chunks(L[i].Ho * L[i].Ho) * 3 * sizeof(double);
+        const size_t dw = enc_dw_plan(L[i].cin, L[i].cout, L[i].Ho, n).part_bytes;
+        l.scratch = act > l.scratch ? act : l.scratch;
+        l.scratch = dw > l.scratch ? dw : l.scratch;
+    }
+    l.scratch = enc_align(l.scratch);
+    return l;
+}
+
+template <int T>
+static void enc_launch_train_t(const float* x, float* y, float* r, const float* resid, const float* w, const EncLayer& L, int n,
+                               float* partials, hipStream_t st) {
+    const int cog = enc_cog(L.cout), ng = enc_groups(T, L.cout);  // the grids of enc_launch_dense_t
+    const int tiles_x = (L.Ho + T - 1) / T;
+    const dim3 grid(tiles_x * tiles_x, L.cout / (cog * ng), n), block(T * T * ng);
+#define OCC_ENC_TRAIN(COG, POOL)                                                                                              \
+    hipLaunchKernelGGL((occ_enc_dense_train_kernel<T, COG, POOL>), grid, block, 0, st, x, y, r, resid, w, L.cin, L.cout, L.H, L.Ho, \
+                       L.stride, tiles_x, partials)
+    if (partials) OCC_ENC_TRAIN(32, true);
+    else if (cog == 8) OCC_ENC_TRAIN(8, false);
+    else if (cog == 16) OCC_ENC_TRAIN(16, false);
+    else OCC_ENC_TRAIN(32, false);
+#undef OCC_ENC_TRAIN
+}
+
+static void enc_launch_train(const float* x, float* y, float* r, const float* resid, const float* w, const EncLayer& L, int n,
+                             float* partials, hipStream_t st) {
+    if (enc_tile(L.Ho) == 16) enc_launch_train_t<16>(x, y, r, resid, w, L, n, partials, st);
+    else enc_launch_train_t<8>(x, y, r, resid, w, L, n, partials, st);
+}
+
+// The dense encoder on n envs with everything kept: 18 launches.
+static void enc_train_forward(int img, bool residual, const float* packed, const float* obs, int n, char* ws, float* feats,
+                              hipStream_t st) {
+    const EncTrainWs l = enc_train_ws_layout(img, n);
+    EncLayer L[16];
+    enc_train_layers(img, L);
+    auto F = [&](size_t off) { return (float*)(ws + off); };
+    const size_t nobs = (size_t)n * 4 * img * img;
+    const size_t cblocks = (nobs + 1023) / 1024;
+    hipLaunchKernelGGL(occ_enc_copy_kernel, dim3((unsigned)(cblocks < 65535 ? cblocks : 65535)), dim3(256), 0, st, obs, F(l.obs),
+                       nobs);
+    enc_launch_train(F(l.obs), F(l.a[0]), F(l.r_init), nullptr, packed + L[0].woff, L[0], n, nullptr, st);
+    for (int lv = 0; lv < kEncLevels; ++lv) {
+        const EncLayer* Ll = L + 1 + 3 * lv;
+        const bool last = lv == kEncLevels - 1;
+        enc_launch_train(F(l.a[lv]), F(l.b[lv]), F(l.r1[lv]), nullptr, packed + Ll[0].woff, Ll[0], n, nullptr, st);
+        enc_launch_train(F(l.b[lv]), F(l.cc[lv]), F(l.r2[lv]), residual ? F(l.a[lv]) : nullptr, packed + Ll[1].woff, Ll[1], n,
+                         nullptr, st);
+        enc_launch_train(F(l.cc[lv]), last ? nullptr : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, packed + Ll[2].woff, Ll[2], n,
+                         last ? F(l.part) : nullptr, st);
+    }
+    const int Hl = L[15].Ho;
+    hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, F(l.part), enc_tiles(Hl), (float)(Hl * Hl), feats);
+}
+
+template <int T, int CIB, int COB, int STRIDE>
+static void enc_launch_dw_t(const EncDwPlan& p, const float* x, const float* du, float* part, const EncLayer& L, hipStream_t st) {
+    hipLaunchKernelGGL((occ_enc_bwd_dw_kernel<T, CIB, COB, STRIDE>), dim3(p.slices, p.grid_y), dim3(256), 0, st, x, du, part, L.cin,
+                       L.cout, L.H, L.Ho, p.tiles_x, p.total_tiles, p.tps);
+}
+
+// The nine (ci, co) tiles of enc_dw_plan: stride 1 has cout = cin (4 -> 8 for the initial layer), stride 2 cout = 2 cin.
+static void enc_launch_dw(const EncDwPlan& p, const float* x, const float* du, float* part, const EncLayer& L, hipStream_t st) {
+    if (L.stride == 1) {
+        if (p.cib == 4) enc_launch_dw_t<8, 4, 8, 1>(p, x, du, part, L, st);
+        else if (p.cib == 8) enc_launch_dw_t<8, 8, 8, 1>(p, x, du, part, L, st);
+        else if (p.cib == 16) enc_launch_dw_t<8, 16, 16, 1>(p, x, du, part, L, st);
+        else if (p.cib == 32) enc_launch_dw_t<8, 32, 32, 1>(p, x, du, part, L, st);
+        else enc_launch_dw_t<4, 64, 32, 1>(p, x, du, part, L, st);
+    } else {
+        if (p.cib == 8) enc_launch_dw_t<8, 8, 16, 2>(p, x, du, part, L, st);
+        else if (p.cib == 16) enc_launch_dw_t<8, 16, 32, 2>(p, x, du, part, L, st);
+        else if (p.cib == 32) enc_launch_dw_t<8, 32, 32, 2>(p, x, du, part, L, st);
+        else enc_launch_dw_t<4, 64, 32, 2>(p, x, du, part, L, st);
+    }
+}
+
+static void enc_launch_dx1(const float* du, float* dx, const float* add, const float* w, const EncLayer& L, int n, hipStream_t st) {
+    const int T = enc_tile(L.H);
+    const int tiles_x = (L.H + T - 1) / T;
+    if (L.cin == 8) {
+        if (T == 16)
+            hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<16, 8>), dim3(tiles_x * tiles_x, 1, n), dim3(256), 0, st, du, dx, add, w, L.cin,
+                               L.cout, L.H, tiles_x);
+        else
+            hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<8, 8>), dim3(tiles_x * tiles_x, 1, n), dim3(64), 0, st, du, dx, add, w, L.cin,
+                               L.cout, L.H, tiles_x);
+        return;
+    }
+    const int groups = L.cin / kBwdDxCIG;
+    if (T == 16) {
+        hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<16, kBwdDxCIG>), dim3(tiles_x * tiles_x, groups, n), dim3(256), 0, st, du, dx, add,
+                           w, L.cin, L.cout, L.H, tiles_x);
+    } else {
+        const int ng = groups < 4 ? groups : 4;
+        hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<8, kBwdDxCIG>), dim3(tiles_x * tiles_x, groups / ng, n), dim3(64 * ng), 0, st, du,
+                           dx, add, w, L.cin, L.cout, L.H, tiles_x);
+    }
+}
+
+static void enc_launch_dx2(const float* du, float* dx, const float* w, const EncLayer& L, int n, hipStream_t st) {
+    const int T = enc_tile(L.Ho);
+    const int tiles_x = (L.Ho + T - 1) / T;
+    const int groups = L.cin / 8;
+    if (T == 16) {
+        hipLaunchKernelGGL((occ_enc_bwd_dx2_kernel<16>), dim3(tiles_x * tiles_x, groups, n), dim3(256), 0, st, du, dx, w, L.cin, L.cout,
+                           L.H, L.Ho, tiles_x);
+    } else {
+        const int ng = groups < 4 ? groups : 4;
+        hipLaunchKernelGGL((occ_enc_bwd_dx2_kernel<8>), dim3(tiles_x * tiles_x, groups / ng, n), dim3(64 * ng), 0, st, du, dx, w, L.cin,
+                           L.cout, L.H, L.Ho, tiles_x);
+    }
+}
+
+// One layer's parameter gradients from its dY (or, pool, from grad_feats): dU is left in `du`.  4 launches.
+static void enc_bwd_layer(const EncLayer& L, const float* packed, float* grad_packed, int n, const float* x, const float* r,
+                          const float* dy, float* du, const float* gf, char* scratch, hipStream_t st) {
+    const int plane = L.Ho * L.Ho, chunks = bwd_chunks(plane);
+    const float* w = packed + L.woff;
+    float* gw = grad_packed + L.woff;
+    float* gbias = gw + 9LL * L.cin * L.cout;
+    const float* bns = w + 9LL * L.cin * L.cout + L.cout;
+    const dim3 agrid(chunks, L.cout, n);
+    if (gf)
+        hipLaunchKernelGGL((occ_enc_bwd_act_kernel<true>), agrid, dim3(256), 0, st, nullptr, du, r, bns, L.cout, plane, gf,
+                           (float)plane, (double*)scratch);
+    else
+        hipLaunchKernelGGL((occ_enc_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, du, r, bns, L.cout, plane, nullptr, 1.f,
+                           (double*)scratch);
+    const BwdActDst dst = {{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
+    hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(L.cout, 3), dim3(64), 0, st, (const double*)scratch, n * chunks, 3, dst);
+    const EncDwPlan p = enc_dw_plan(L.cin, L.cout, L.Ho, n);
+    float* part = (float*)scratch;
+    enc_launch_dw(p, x, du, part, L, st);
+    const int nout = 9 * L.cin * L.cout;
+    hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, part, p.slices * p.pb, nout, gw);
+}
+
+// The backward of the latest enc_train_forward on this workspace, the deepest layer first: 79 launches.  grad_packed is
+// overwritten.  Gradient buffers per level: gA holds the down's dY / dU, gB the dY of Layer 2's output (kept for the
+// residual), gC Layer 2's dU and then the block input's gradient, which is the gA of the level above.
+static void enc_backward(int img, bool residual, const float* packed, int n, char* ws, const float* grad_feats, char* scratch,
+                         float* grad_packed, hipStream_t st) {
+    const EncTrainWs l = enc_train_ws_layout(img, n);
+    EncLayer L[16];
+    enc_train_layers(img, L);
+    auto F = [&](size_t off) { return (float*)(ws + off); };
+    float *gA = F(l.g[0]), *gB = F(l.g[1]), *gC = F(l.g[2]);
+    for (int lv = kEncLevels - 1; lv >= 0; --lv) {
+        const EncLayer* Ll = L + 1 + 3 * lv;
+        const bool last = lv == kEncLevels - 1;
+        enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), gA, gA, last ? grad_feats : nullptr, scratch, st);
+        enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st);
+        enc_bwd_layer(Ll[1], packed, grad_packed, n, F(l.b[lv]), F(l.r2[lv]), gB, gC, nullptr, scratch, st);
+        enc_launch_dx1(gC, gA, nullptr, packed + Ll[1].woff, Ll[1], n, st);
+        enc_bwd_layer(Ll[0], packed, grad_packed, n, F(l.a[lv]), F(l.r1[lv]), gA, gA, nullptr, scratch, st);
+        enc_launch_dx1(gA, gC, residual ? gB : nullptr, packed + Ll[0].woff, Ll[0], n, st);
+        float* t = gA;
+        gA = gC;
+        gC = t;
+    }
+    enc_bwd_layer(L[0], packed, grad_packed, n, F(l.obs), F(l.r_init), gA, gA, nullptr, scratch, st);
+}

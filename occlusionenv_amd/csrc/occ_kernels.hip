@@ -61,6 +61,7 @@ namespace occ {
 #include "occ_encoder.hpp"
 #include "occ_decoder.hpp"
 #include "occ_decoder_bwd.hpp"
+#include "occ_encoder_bwd.hpp"
 #include "occ_criterion.hpp"
 
 }  // namespace occ
@@ -693,6 +694,40 @@ extern "C" int occ_segment_backward(const OccEncoderConfig* cfg, const float* de
     const TrainWs l = train_ws_layout(cfg->img, n_env);
     if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
     seg_backward(cfg->img, dec_packed, n_env, (char*)ws, grad_prob, (char*)scratch, grad_packed, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- encoder training (occ_encoder_bwd.hpp) ------------------------------------------------------------------------------
+static bool enc_train_cfg_ok(const OccEncoderConfig* c, int n_env) {
+    return enc_cfg_ok(c) && c->separable == 0 && c->dilation == 1 && n_env >= 1 && n_env <= 65535;
+}
+
+extern "C" int occ_encoder_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
+    if (!enc_train_cfg_ok(cfg, n_env) || !ws_bytes || !scratch_bytes) return OCC_ERR_ARG;
+    const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env);
+    *ws_bytes = l.total;
+    *scratch_bytes = l.scratch;
+    return OCC_OK;
+}
+
+extern "C" int occ_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env, void* ws,
+                                         size_t ws_bytes, float* feats, void* stream) {
+    if (!enc_train_cfg_ok(cfg, n_env) || !packed || !obs || !ws || !feats) return OCC_ERR_ARG;
+    if (((uintptr_t)ws & 15) != 0 || (((uintptr_t)packed | (uintptr_t)obs | (uintptr_t)feats) & 3) != 0) return OCC_ERR_ARG;
+    if (ws_bytes < enc_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
+    enc_train_forward(cfg->img, cfg->residual != 0, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
+                                    const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream) {
+    if (!enc_train_cfg_ok(cfg, n_env) || !packed || !ws || !grad_feats || !scratch || !grad_packed) return OCC_ERR_ARG;
+    // the block partials are doubles
+    if ((((uintptr_t)ws | (uintptr_t)scratch) & 15) != 0 || (((uintptr_t)packed | (uintptr_t)grad_feats | (uintptr_t)grad_packed) & 3) != 0)
+        return OCC_ERR_ARG;
+    const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env);
+    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
+    enc_backward(cfg->img, cfg->residual != 0, packed, n_env, (char*)ws, grad_feats, (char*)scratch, grad_packed, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

@@ -187,6 +187,22 @@ def decoder_tensors(sd, prefix: str, classifier: str) -> dict:
     return {k: torch.as_tensor(sd[k]).detach().to("cpu").clone() for k in keys}
 
 
+ENCODER_TENSORS = ("conv.weight", "conv.bias", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var")
+
+
+def encoder_tensors(sd, prefix: str, separable: bool, grad_head: Optional[str] = None) -> dict:
+    """The unfolded tensors ``pack_state_dict`` reads, under their full state-dict keys, plus the grad head's when it is
+    there (what ``enctrain.TrainableEncoder`` trains and ``FrozenEncoder.with_encoder`` takes back); call after
+    ``pack_state_dict`` has checked them."""
+    keys = []
+    for stem, _cin, _cout, sep, _stride in layer_plan(separable):
+        conv = ("conv.0.weight", "conv.1.weight", "conv.2.weight", "conv.2.bias") if sep else ENCODER_TENSORS[:2]
+        keys += [prefix + stem + t for t in conv + ENCODER_TENSORS[2:]]
+    if grad_head is not None and grad_head + "weight" in sd:
+        keys += [grad_head + "weight", grad_head + "bias"]
+    return {k: torch.as_tensor(sd[k]).detach().to("cpu").clone() for k in keys}
+
+
 class FrozenEncoder:
     """Native inference of the frozen encoder: ``enc(obs)`` (N,4,S,S) f32 on the GPU -> (N,256) f32 pooled features,
     the callable ``BatchedPPO(encoder=...)`` takes; ``enc.predict_grad(obs)`` -> (N,2) from the grad head.
@@ -196,7 +212,7 @@ class FrozenEncoder:
 
     def __init__(self, packed: np.ndarray, separable: bool, dilation: int, residual: bool, preset: str, grad_head=None,
                  heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None, decoder=None,
-                 decoder_state: Optional[dict] = None):
+                 decoder_state: Optional[dict] = None, encoder_state: Optional[dict] = None):
         if dilation not in (1, 2):
             raise ValueError(f"dilation must be 1 or 2, got {dilation}")
         if int(max_chunk) < 1:
@@ -223,6 +239,7 @@ class FrozenEncoder:
         self._ws = {}  # (kind, chunk size, S) -> workspace
         self.dec_packed_host = self.dec_packed = None
         self.decoder_state = decoder_state  # the decoder's unfolded tensors by state-dict key (None without a decoder)
+        self.encoder_state = encoder_state  # the encoder's (and the grad head's) unfolded tensors by state-dict key
         if decoder is not None:
             self.dec_packed_host = np.ascontiguousarray(decoder, dtype=np.float32)
             if lib.occ_decoder_packed_floats(C.byref(cfg)) != self.dec_packed_host.size:
@@ -264,7 +281,8 @@ class FrozenEncoder:
             if name + "weight" in sd:
                 heads[name[:-1]] = (_get(sd, name + "weight", (rows, FEATURES)), _get(sd, name + "bias", (rows,)))
         return cls(packed, separable, d0 if dilation is None else int(dilation), r0 if residual is None else bool(residual),
-                   preset, grad_head, heads, device, max_chunk, offsets, decoder, decoder_state)
+                   preset, grad_head, heads, device, max_chunk, offsets, decoder, decoder_state,
+                   encoder_tensors(sd, prefix, separable, ghead))
 
     def with_decoder(self, sd) -> "FrozenEncoder":
         """A ``FrozenEncoder`` with this one's encoder (the packed weights are shared, not copied) and the decoder of
@@ -281,6 +299,28 @@ class FrozenEncoder:
         new.dec_packed_host = np.ascontiguousarray(packed, dtype=np.float32)
         new.dec_packed = torch.from_numpy(new.dec_packed_host).to(self.device)
         new.decoder_state = decoder_tensors(sd, dprefix, dcls)
+        return new
+
+    def with_encoder(self, sd) -> "FrozenEncoder":
+        """A ``FrozenEncoder`` with the encoder (and, when its keys are in ``sd``, the grad head) of ``sd``, a state dict
+        under this preset's keys such as ``enctrain.TrainableEncoder.state_dict()`` after training, and this one's dilation,
+        residual flag and decoder.  This encoder is left as it is."""
+        import copy
+
+        prefix, ghead = PRESETS[self.preset][0], PRESETS[self.preset][1]
+        separable, packed, offsets = pack_state_dict(sd, prefix)
+        if separable != self.separable:
+            raise ValueError("with_encoder: the state dict's encoder is " + ("separable" if separable else "dense") +
+                             ", this encoder is not")
+        new = copy.copy(self)
+        new._ws = {}
+        new.packed_host = np.ascontiguousarray(packed, dtype=np.float32)
+        new.packed = torch.from_numpy(new.packed_host).to(self.device)
+        new.layer_offsets = list(offsets)
+        if ghead is not None and ghead + "weight" in sd:
+            new.grad_w = _get(sd, ghead + "weight", (2, FEATURES)).to(self.device, torch.float32).contiguous()
+            new.grad_b = _get(sd, ghead + "bias", (2,)).to(self.device, torch.float32).contiguous()
+        new.encoder_state = encoder_tensors(sd, prefix, separable, ghead)
         return new
 
     @classmethod

@@ -11,6 +11,8 @@
     every step renders anyway.
   * ``finetune_segmentation`` -- the learning half of the same loop (pretrainer.py:91,120-141): every step's occlusion image is
     the target of one AdamW step on the segmentation head (``seghead.SegmentationHead``), the encoder frozen.
+  * ``train_predictor`` -- train_predict.py:38-69 on the batched env: random actions, the engine's action gradient as the
+    target of the gradient predictor, MSE and AdamW on the dense encoder and its head (``enctrain.TrainableEncoder``).
   * ``validate_pretrained`` -- pretrainer.py:162-204 (``val``) itself, on a stored dataset: Loss / Dice / MSE / Accuracy /
     IoU as the means of the per-batch values.
 """
@@ -144,6 +146,43 @@ def finetune_segmentation(venv, enc_or_head, steps: int, lr: float = 1e-3, weigh
             action = policy(pooled)[0].detach()
     host = torch.stack(rows).cpu().tolist() if rows else []
     return dict(head=head, losses=[r[0] for r in host], accuracy=[r[1] for r in host], iou=[r[2] for r in host], steps=len(host))
+
+
+def train_predictor(venv, enc_or_net, steps: int, lr: float = 1e-4, weight_decay: float = 1e-2, reset_every: int = 10):
+    """train_predict.py:38-69 on the batched env: every ``reset_every`` steps (the reference's episode length) the envs are
+    reset; every step draws ``action = randn(N, 2)``, steps, takes ``rewards.sum().backward()`` for the engine's action
+    gradient, skips the step if that gradient has a NaN (line 53), normalises it per env as on line 58
+    (``g / sqrt(sum g^2 + 1e-7)``) and applies ``F.mse_loss(net.predict_grad(obs), target)``, ``backward`` and one
+    ``torch.optim.AdamW`` step (``weight_decay``: torch's default, as in the reference) to the encoder and its head.
+    ``enc_or_net``: an ``enctrain.TrainableEncoder``, or a dense ``FrozenEncoder`` with a grad head (preset "predictor"),
+    from which one is made.  BatchNorm keeps its running statistics (``enctrain``).  Returns ``net``, the per-step ``losses``
+    of the steps that learned (floats) and ``skipped``, the number of NaN steps; one host sync per step, for the NaN test
+    the reference makes there too."""
+    from .enctrain import TrainableEncoder
+
+    net = enc_or_net if isinstance(enc_or_net, TrainableEncoder) else TrainableEncoder.from_encoder(enc_or_net)
+    opt = torch.optim.AdamW(net.parameters(), lr=lr, weight_decay=weight_decay)
+    losses, skipped = [], 0
+    obs = None
+    for i in range(int(steps)):
+        if obs is None or (reset_every and i % int(reset_every) == 0):
+            obs = venv.reset()
+        n = int(obs.shape[0])
+        action = torch.randn(n, 2, device=obs.device).requires_grad_(True)
+        opt.zero_grad(set_to_none=True)
+        obs, rewards, _dones, _infos = venv.step(action)
+        rewards.sum().backward()
+        if bool(torch.isnan(action.grad).any()):
+            skipped += 1
+            continue
+        frame = (obs[:, 0] if obs.dim() == 5 else obs).detach()
+        target = action.grad / torch.sqrt((action.grad ** 2).sum(dim=1, keepdim=True) + 1e-7)
+        loss = torch.nn.functional.mse_loss(net.predict_grad(frame), target.detach())
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+    host = torch.stack(losses).cpu().tolist() if losses else []
+    return dict(net=net, losses=host, skipped=skipped, steps=len(host))
 
 
 @torch.no_grad()
