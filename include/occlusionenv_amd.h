@@ -426,7 +426,8 @@ int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, co
  * Training of the decoder and the classifier with the encoder frozen (additive in ABI 12; csrc/occ_decoder_bwd.hpp).  The
  * decoder's BatchNorm runs with its running statistics, as in inference: with u = convT(x_j) + bias, r = relu(u),
  * y_j = bn_scale r + bn_shift + skip, the parameters that receive a gradient are w, bias, bn_scale, bn_shift of every up
- * layer and cls_w, cls_b.  Neither d obs, d skip nor any encoder gradient is computed.
+ * layer and cls_w, cls_b.  Neither d obs, d skip nor any encoder gradient is computed here (occ_fullnet_backward below
+ * joins this backward with the encoder's).
  *
  * occ_segment_train_forward is occ_segment_forward (feats and prob are the same to the bit) that keeps, in ws, every level's
  * input x_j, its relu output r_j, the decoder feature y_4 and prob.  Workspace, every part 256-byte aligned: the
@@ -475,6 +476,45 @@ int occ_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, 
                               size_t ws_bytes, float* feats, void* stream);
 int occ_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
                          const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream);
+
+/*
+ * Joint training of the dense encoder, the decoder and the classifier (additive in ABI 12; csrc/occ_fullnet_bwd.hpp): one
+ * step of pretrainer.py below its losses, for two upstream gradients at once.  Supported: cfg->separable == 0,
+ * cfg->dilation == 1, cfg->residual 0 or 1, cfg->img % 32 == 0 in [32, 1024].  BatchNorm runs with its running statistics
+ * in all 21 layers; the parameters that receive a gradient are those of occ_encoder_backward and of occ_segment_backward.
+ * No d obs is computed.
+ *
+ * occ_fullnet_train_forward runs the encoder ONCE, as occ_encoder_train_forward does, with the last down also storing its
+ * output, then the five up layers of occ_segment_train_forward on that output and on the level tensors cc (the skips, not
+ * copied).  feats is bitwise what occ_encoder_forward writes, prob (8-byte aligned) what occ_segment_forward writes.
+ * Workspace, every part 256-byte aligned, f32:
+ *   the workspace of occ_encoder_train_forward, three gradient buffers g0 | g1 | g2 included |
+ *   last (n,256,S/32,S/32) | for j = 0..4: y_j | r_j, each (n, 128 >> j, S/16 << j, S/16 << j) | prob (n,S,S) |
+ *   dlast (n,256,S/32,S/32) | dskip_lv for lv = 1..4, (n, 8 << lv, S >> lv, S >> lv)
+ * 23 launches.
+ *
+ * occ_fullnet_backward is the backward of the LATEST occ_fullnet_train_forward on ws (same cfg, n_env and packed buffers)
+ * for grad_feats = d loss / d feats (n_env,256) and grad_prob = d loss / d prob (n_env,1,S,S; 16-byte aligned), both
+ * required (zeros for an absent one).  The decoder runs first, the full-resolution level first, then the encoder, the
+ * deepest level first.  Every decoder level's dY is the d skip of an encoder level: for lv >= 1 it is kept in dskip_lv (the
+ * decoder's activation step writes dU to g0 instead of over dY) and added in the epilogue of the encoder's stride-2 input
+ * gradient; for lv = 0 it is not stored but rebuilt there as grad_prob p (1 - p) cls_w[c] (0.94 buffers of (n,8,S,S) kept
+ * instead of 1.94).  The deepest decoder level's input gradient goes to dlast and is added to grad_feats / (H H) in the
+ * last down's activation step.  No join is a launch of its own.  grad_enc_packed (occ_encoder_packed_floats floats) and
+ * grad_dec_packed (occ_decoder_packed_floats floats) are OVERWRITTEN, not accumulated, in the layouts of enc_packed and
+ * dec_packed.  scratch: the queried scratch_bytes (16-byte aligned), the larger of the two single passes' scratch.  No
+ * floating-point atomics; block partials are added in a fixed order in f64: every gradient is bitwise the same from call
+ * to call, grad_dec_packed is bitwise what occ_segment_backward gives for the same grad_prob, and with grad_prob = 0
+ * grad_enc_packed equals what occ_encoder_backward gives.  104 launches (decoder 25, encoder 79) on `stream`, nothing
+ * allocated or synchronised.  OCC_ERR_ARG before any launch for an unsupported cfg, a null pointer, n_env outside
+ * [1, 65535], a misaligned or a short buffer.
+ */
+int occ_fullnet_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes);
+int occ_fullnet_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                              int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, void* stream);
+int occ_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env, void* ws,
+                         size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch, size_t scratch_bytes,
+                         float* grad_enc_packed, float* grad_dec_packed, void* stream);
 
 /*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,

@@ -8,7 +8,8 @@
 //
 //   occ_dec_up_train_kernel     occ_dec_up_kernel with the same FMA order (prob and the pooled feature are the same to
 //                               the bit), which also stores r_j and, at the last level, y_4 and a second copy of p.
-//   occ_dec_bwd_act_kernel      per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0] written over dY, with dY = dz
+//   occ_dec_bwd_act_kernel      per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0] written over dY (to a buffer of its
+//                               own in the joint training of occ_fullnet_bwd.hpp, which reads dY again), with dY = dz
 //                               cls_w[c], dz = g p (1 - p) at the last level; f64 block partials of dS = sum dY r, dT = sum
 //                               dY, dB = sum dU (and sum dz y_4[c], sum dz at the last level).  The gate is the forward's
 //                               own r > 0.
@@ -18,7 +19,7 @@
 //                               of the forward's quad mapping.  A thread owns one input pixel for 16 input channels; the
 //                               (2 T + 1)^2 dU tile is staged in LDS 8 output channels at a time (row / column -1 and 2 H
 //                               read as zero); weights are wave-uniform scalar loads of 8 consecutive co.  Not launched for
-//                               level 0: the encoder is frozen.
+//                               level 0 while the encoder is frozen; the joint training launches it there too.
 //   occ_dec_bwd_dw_kernel       dW[ci][k][co] = sum_{n,iy,ix} x[ci][iy][ix] dU[co][2 iy - 1 + ky][2 ix - 1 + kx], a
 //                               (2c) x (9c) contraction over K = N H^2.  A thread owns 16 ci x 9 taps x 1 co (144 f32
 //                               accumulators); a block owns a CIB x COB tile of (ci, co) and one slice of K (consecutive
@@ -137,11 +138,12 @@ __global__ __launch_bounds__(256) void occ_dec_up_train_kernel(const float* __re
     }
 }
 
-// Activation step of one level.  g: (n, c, plane) dY on entry (not read when LAST), dU on exit.  r: the forward's relu(u).
+// Activation step of one level.  dy: (n, c, plane) (not read when LAST); du: (n, c, plane), may be dy itself (the decoder
+// alone; the joint training of occ_fullnet_bwd.hpp keeps dY, the level's d skip).  r: the forward's relu(u).
 // LAST: gp = d loss / d prob and prob are (n, plane), y4 (n, c, plane), clsw[c].
 // partials[((ch * n + env) * chunks + chunk) * NS + k], NS = LAST ? 5 : 3: k = 0 dS, 1 dT, 2 dB, 3 sum dz y4[ch], 4 sum dz.
 template <bool LAST>
-__global__ __launch_bounds__(256) void occ_dec_bwd_act_kernel(float* __restrict__ g, const float* __restrict__ r,
+__global__ __launch_bounds__(256) void occ_dec_bwd_act_kernel(const float* dyp, float* dup, const float* __restrict__ r,
                                                               const float* __restrict__ bns, int c, int plane,
                                                               const float* __restrict__ gp, const float* __restrict__ prob,
                                                               const float* __restrict__ y4, const float* __restrict__ clsw,
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(256) void occ_dec_bwd_act_kernel(float* __restrict_
                 dy[q] = dz[q] * cw;
             }
         } else {
-            const float4 d4 = *reinterpret_cast<const float4*>(g + base + i);
+            const float4 d4 = *reinterpret_cast<const float4*>(dyp + base + i);
             dy[0] = d4.x, dy[1] = d4.y, dy[2] = d4.z, dy[3] = d4.w;
         }
 #pragma unroll
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(256) void occ_dec_bwd_act_kernel(float* __restrict_
                 sum[4] += (double)dz[q];
             }
         }
-        *reinterpret_cast<float4*>(g + base + i) = make_float4(du[0], du[1], du[2], du[3]);
+        *reinterpret_cast<float4*>(dup + base + i) = make_float4(du[0], du[1], du[2], du[3]);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1)
@@ -482,16 +484,8 @@ static void dec_launch_up_train(const float* x, float* y, float* r, const float*
     }
 }
 
-// Encoder (17 launches) + decoder (5 launches), every decoder activation kept.
-static void seg_train_forward(int img, int dil, bool residual, bool separable, const float* enc_packed, const float* dec_packed,
-                              const float* obs, int n, char* ws, float* feats, float* prob, hipStream_t st) {
-    const TrainWs l = train_ws_layout(img, n);
-    const TrainPtrs t = train_ptrs(l, ws);
-    EncKeep keep;
-    for (int lv = 0; lv < kEncLevels; ++lv) keep.skip[lv] = t.skip[lv];
-    keep.last = t.last;
-    enc_forward(img, dil, residual, separable, enc_packed, obs, n, ws, feats, st, &keep);
-
+// The five up levels on t.last and t.skip, keeping y_j, r_j and p: 5 launches.
+static void dec_train_forward(int img, const float* dec_packed, int n, const TrainPtrs& t, float* prob, hipStream_t st) {
     const float* w = dec_packed;
     const float* cls = dec_packed + dec_packed_floats() - (kEncCh + 1);
     const float* x = t.last;
@@ -507,6 +501,18 @@ static void seg_train_forward(int img, int dil, bool residual, bool separable, c
     }
 }
 
+// Encoder (17 launches) + decoder (5 launches), every decoder activation kept.
+static void seg_train_forward(int img, int dil, bool residual, bool separable, const float* enc_packed, const float* dec_packed,
+                              const float* obs, int n, char* ws, float* feats, float* prob, hipStream_t st) {
+    const TrainWs l = train_ws_layout(img, n);
+    const TrainPtrs t = train_ptrs(l, ws);
+    EncKeep keep;
+    for (int lv = 0; lv < kEncLevels; ++lv) keep.skip[lv] = t.skip[lv];
+    keep.last = t.last;
+    enc_forward(img, dil, residual, separable, enc_packed, obs, n, ws, feats, st, &keep);
+    dec_train_forward(img, dec_packed, n, t, prob, st);
+}
+
 template <int T, int CIB, int COB>
 static void bwd_launch_dw(const BwdDwPlan& p, const float* x, const float* du, float* part, int cin, int cout, int H,
                           hipStream_t st) {
@@ -514,12 +520,19 @@ static void bwd_launch_dw(const BwdDwPlan& p, const float* x, const float* du, f
                        p.tiles_x, p.total_tiles, p.tps);
 }
 
-// The backward of the latest seg_train_forward on this workspace: per level, last first, the activation step (2 launches),
-// the weight gradient (2 launches) and, above level 0, the input gradient: 24 launches.  grad_packed is overwritten.
-static void seg_backward(int img, const float* dec_packed, int n, char* ws, const float* grad_prob, char* scratch,
-                         float* grad_packed, hipStream_t st) {
-    const TrainWs l = train_ws_layout(img, n);
-    const TrainPtrs t = train_ptrs(l, ws);
+// Where the joint training (occ_fullnet_bwd.hpp) keeps the decoder's gradients that the encoder's backward reads.
+struct DecJoin {
+    float* dlast;              // (n, 256, S/32, S/32): the input gradient of level 0
+    float* dskip[kEncLevels];  // dskip[lv], lv >= 1: the dY of level 4 - lv, which is d skip[lv]; dskip[0] is not stored
+    float* du;                 // every level's dU, the size of y_4
+};
+
+// The backward of the latest forward on the tensors of t: per level, last first, the activation step (2 launches), the
+// weight gradient (2 launches) and, above level 0, the input gradient: 24 launches.  grad_packed is overwritten.  Without
+// join dY and dU alternate in t.g, dU written over dY.  With join the activation step is out of place and level 0 has an
+// input gradient too: 25 launches.
+static void dec_backward(int img, const float* dec_packed, int n, const TrainPtrs& t, const float* grad_prob, char* scratch,
+                         float* grad_packed, hipStream_t st, const DecJoin* join = nullptr) {
     long long woff[kEncLevels];
     long long off = 0;
     for (int j = 0; j < kEncLevels; ++j) {
@@ -536,16 +549,18 @@ static void seg_backward(int img, const float* dec_packed, int n, char* ws, cons
         const float* w = dec_packed + woff[j];
         float* gw = grad_packed + woff[j];
         float* gbias = gw + 9LL * cin * c;
-        float* g = t.g[(kEncLevels - 1 - j) % 2];
+        const int lv = kEncLevels - 1 - j;
+        float* g = join ? join->du : t.g[lv % 2];
+        const float* dy = join ? join->dskip[lv] : g;
         const float* x = j == 0 ? t.last : t.y[j - 1];
         const int chunks = bwd_chunks(plane);
         const dim3 agrid(chunks, c, n);
         const BwdActDst dst = {{gbias + c, gbias + 2 * c, gbias, gcls, gcls + kEncCh}};
         if (last)
-            hipLaunchKernelGGL((occ_dec_bwd_act_kernel<true>), agrid, dim3(256), 0, st, g, t.r[j], w + 9LL * cin * c + c, c, plane,
+            hipLaunchKernelGGL((occ_dec_bwd_act_kernel<true>), agrid, dim3(256), 0, st, nullptr, g, t.r[j], w + 9LL * cin * c + c, c, plane,
                                grad_prob, t.p, t.y[j], cls, (double*)scratch);
         else
-            hipLaunchKernelGGL((occ_dec_bwd_act_kernel<false>), agrid, dim3(256), 0, st, g, t.r[j], w + 9LL * cin * c + c, c, plane,
+            hipLaunchKernelGGL((occ_dec_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, g, t.r[j], w + 9LL * cin * c + c, c, plane,
                                nullptr, nullptr, nullptr, nullptr, (double*)scratch);
         hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(c, last ? 5 : 3), dim3(64), 0, st, (const double*)scratch, n * chunks,
                            last ? 5 : 3, dst);
@@ -557,8 +572,8 @@ static void seg_backward(int img, const float* dec_packed, int n, char* ws, cons
         else bwd_launch_dw<8, 16, 8>(p, x, g, part, cin, c, H, st);
         const int nout = 9 * cin * c;
         hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, part, p.slices * p.pb, nout, gw);
-        if (j > 0) {
-            float* dx = t.g[(kEncLevels - j) % 2];  // dY of level j - 1
+        if (j > 0 || join) {
+            float* dx = !join ? t.g[(kEncLevels - j) % 2] : j > 0 ? join->dskip[lv + 1] : join->dlast;  // dY of level j - 1
             const int T = H >= 16 ? 16 : 8;
             const int tiles_x = (H + T - 1) / T;
             if (T == 16) {
@@ -571,4 +586,10 @@ static void seg_backward(int img, const float* dec_packed, int n, char* ws, cons
             }
         }
     }
+}
+
+static void seg_backward(int img, const float* dec_packed, int n, char* ws, const float* grad_prob, char* scratch,
+                         float* grad_packed, hipStream_t st) {
+    const TrainWs l = train_ws_layout(img, n);
+    dec_backward(img, dec_packed, n, train_ptrs(l, ws), grad_prob, scratch, grad_packed, st);
 }

@@ -9,7 +9,8 @@
 //
 //   occ_enc_copy_kernel           obs -> ws (the backward has no obs argument; the initial layer's dW reads the copy).
 //   occ_enc_dense_train_kernel    occ_enc_dense_kernel at dilation 1 with the same FMA order (feats are the same to the
-//                                 bit) which also stores r; POOL (the last down) stores r and the pool partials, no y.
+//                                 bit) which also stores r; POOL (the last down) stores r and the pool partials, and y
+//                                 only for the joint training (occ_fullnet_bwd.hpp), whose decoder reads it.
 //   occ_enc_bwd_act_kernel        per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0], written to a buffer of its
 //                                 own (the dY of a residual block's Layer 2 is needed again); POOL: dY = grad_feats[n][c] /
 //                                 (H H), never stored.  f64 block partials of dS = sum dY r, dT = sum dY, dB = sum dU in
@@ -23,6 +24,8 @@
 //                                 channels and reads dU at (qy + {0,1}, qx + {0,1}): the quad mapping of occ_dec_up_kernel
 //                                 (1, 2, 2 and 4 taps per quad pixel, no zero-stuffed taps, no parity branches).  dU rows /
 //                                 columns >= Ho read as zero; quad pixels >= H are not stored.
+//                                 JOIN (the joint training): the decoder's d skip of the level is added in the epilogue,
+//                                 read from a kept tensor or, at level 0, rebuilt as gp p (1 - p) cls_w[ci].
 //   occ_enc_bwd_dw_kernel         dW[ci][k][co] = sum_{n,oy,ox} x[ci][s oy - 1 + ky][s ox - 1 + kx] dU[co][oy][ox], a
 //                                 (9 cin) x cout contraction over K = N Ho^2.  A thread owns 1 ci x 9 taps x 8 co (72 f32
 //                                 accumulators); a block owns a CIB x COB tile of (ci, co) and one slice of K (consecutive
@@ -130,7 +133,10 @@ __global__ __launch_bounds__(256) void occ_enc_dense_train_kernel(const float* _
             const float r = fmaxf(acc[j] + bias[co], 0.f);
             const float v = fmaf(r, bns[co], bnt[co]);
             s[(g * COG + j) * TT + p] = valid ? v : 0.f;
-            if (valid) rkeep[o + co * oplane] = r;
+            if (valid) {
+                rkeep[o + co * oplane] = r;
+                if (y) y[o + co * oplane] = v;  // the joint training's decoder reads the last down's output
+            }
         }
         __syncthreads();
         if (tid < ng * COG) {
@@ -144,8 +150,9 @@ __global__ __launch_bounds__(256) void occ_enc_dense_train_kernel(const float* _
     }
 }
 
-// Activation step of one layer.  dy: (n, c, plane) (not read when POOL: dY = gf[env][ch] / count); du: (n, c, plane), may
-// be dy itself.  partials[((ch * n + env) * chunks + chunk) * 3 + k]: k = 0 dS, 1 dT, 2 dB.
+// Activation step of one layer.  dy: (n, c, plane); du: (n, c, plane), may be dy itself.  POOL: dY = gf[env][ch] / count, plus
+// dy when dy is not null (the decoder's gradient of the last down's output, occ_fullnet_bwd.hpp).
+// partials[((ch * n + env) * chunks + chunk) * 3 + k]: k = 0 dS, 1 dT, 2 dB.
 template <bool POOL>
 __global__ __launch_bounds__(256) void occ_enc_bwd_act_kernel(const float* dy, float* du, const float* __restrict__ r,
                                                               const float* __restrict__ bns, int c, int plane,
@@ -163,7 +170,9 @@ __global__ __launch_bounds__(256) void occ_enc_bwd_act_kernel(const float* dy, f
         const int i = lo + (int)threadIdx.x + 256 * j;
         if (i >= plane) break;
         const float rv = r[base + i];
-        const float d = POOL ? pooled : dy[base + i];
+        float d;
+        if constexpr (POOL) d = dy ? pooled + dy[base + i] : pooled;
+        else d = dy[base + i];
         const float u = rv > 0.f ? d * sc : 0.f;
         sum[0] = fma((double)d, (double)rv, sum[0]);
         sum[1] += (double)d;
@@ -247,11 +256,20 @@ __global__ __launch_bounds__(256) void occ_enc_bwd_dx1_kernel(const float* __res
     }
 }
 
+// What the joint training (occ_fullnet_bwd.hpp) adds to the stride-2 input gradient: the decoder's d skip of the level.
+struct EncSkipGrad {
+    const float* add;   // JOIN 1: (n, cin, H, H), the kept dY of the decoder level that read this skip
+    const float* gp;    // JOIN 2 (level 0): d loss / d prob (n, H, H); d skip[ci] = gp p (1 - p) clsw[ci] is rebuilt here
+    const float* prob;  //         the forward's kept prob (n, H, H)
+    const float* clsw;  //         cls_w[cin]
+};
+
 // du: (n, cout, Ho, Ho), Ho = ceil(H / 2); dx: (n, cin, H, H).  cin % 8 == 0, cout % 8 == 0.  A T x T tile of quads.
-template <int T>
+// JOIN 0: dx = the input gradient; 1 and 2: plus the d skip of EncSkipGrad, added in the epilogue.
+template <int T, int JOIN = 0>
 __global__ __launch_bounds__(256) void occ_enc_bwd_dx2_kernel(const float* __restrict__ du, float* __restrict__ dx,
                                                               const float* __restrict__ w, int cin, int cout, int H, int Ho,
-                                                              int tiles_x) {
+                                                              int tiles_x, EncSkipGrad sk) {
     constexpr int TT = T * T, R = T + 1, RR = R * R, CC = kBwdDxCC, CIG = 8;
     __shared__ float s[CC * RR];
     const int tid = threadIdx.x;
@@ -308,14 +326,33 @@ __global__ __launch_bounds__(256) void occ_enc_bwd_dx2_kernel(const float* __res
     const int iy = 2 * qy, ix = 2 * qx;
     if (iy >= H || ix >= H) return;
     const size_t plane = (size_t)H * H;
-    float* xe = dx + ((size_t)blockIdx.z * cin + ci0) * plane + (size_t)iy * H + ix;
+    const size_t xo = ((size_t)blockIdx.z * cin + ci0) * plane + (size_t)iy * H + ix;
+    float* xe = dx + xo;
     const bool right = ix + 1 < H, below = iy + 1 < H;
+    const bool in[4] = {true, right, below, right && below};
+    const size_t qoff[4] = {0, 1, (size_t)H, (size_t)H + 1};
+    float dz[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (JOIN == 2) {  // dz as occ_dec_bwd_act_kernel<true> forms it
+        const size_t po = (size_t)blockIdx.z * plane + (size_t)iy * H + ix;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (in[q]) {
+                const float pv = sk.prob[po + qoff[q]];
+                dz[q] = sk.gp[po + qoff[q]] * (pv * (1.f - pv));
+            }
+    }
 #pragma unroll
     for (int j = 0; j < CIG; ++j) {
-        xe[j * plane] = acc[0][j];
-        if (right) xe[j * plane + 1] = acc[1][j];
-        if (below) xe[j * plane + H] = acc[2][j];
-        if (right && below) xe[j * plane + H + 1] = acc[3][j];
+        float cw = 0.f;
+        if constexpr (JOIN == 2) cw = sk.clsw[ci0 + j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!in[q]) continue;
+            float v = acc[q][j];
+            if constexpr (JOIN == 1) v += sk.add[xo + j * plane + qoff[q]];
+            if constexpr (JOIN == 2) v += dz[q] * cw;
+            xe[j * plane + qoff[q]] = v;
+        }
     }
 }
 
@@ -515,8 +552,9 @@ static void enc_launch_train(const float* x, float* y, float* r, const float* re
 }
 
 // The dense encoder on n envs with everything kept: 18 launches.
+// last_y: where the last down also stores its output (n, 256, H_5, H_5), or null.
 static void enc_train_forward(int img, bool residual, const float* packed, const float* obs, int n, char* ws, float* feats,
-                              hipStream_t st) {
+                              hipStream_t st, float* last_y = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n);
     EncLayer L[16];
     enc_train_layers(img, L);
@@ -532,7 +570,7 @@ static void enc_train_forward(int img, bool residual, const float* packed, const
         enc_launch_train(F(l.a[lv]), F(l.b[lv]), F(l.r1[lv]), nullptr, packed + Ll[0].woff, Ll[0], n, nullptr, st);
         enc_launch_train(F(l.b[lv]), F(l.cc[lv]), F(l.r2[lv]), residual ? F(l.a[lv]) : nullptr, packed + Ll[1].woff, Ll[1], n,
                          nullptr, st);
-        enc_launch_train(F(l.cc[lv]), last ? nullptr : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, packed + Ll[2].woff, Ll[2], n,
+        enc_launch_train(F(l.cc[lv]), last ? last_y : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, packed + Ll[2].woff, Ll[2], n,
                          last ? F(l.part) : nullptr, st);
     }
     const int Hl = L[15].Ho;
@@ -584,21 +622,28 @@ static void enc_launch_dx1(const float* du, float* dx, const float* add, const f
     }
 }
 
-static void enc_launch_dx2(const float* du, float* dx, const float* w, const EncLayer& L, int n, hipStream_t st) {
+// sk: null, or the d skip to add (sk->add, or sk->gp at level 0, where Ho = S / 2 >= 16).
+static void enc_launch_dx2(const float* du, float* dx, const float* w, const EncLayer& L, int n, hipStream_t st,
+                           const EncSkipGrad* sk = nullptr) {
     const int T = enc_tile(L.Ho);
     const int tiles_x = (L.Ho + T - 1) / T;
     const int groups = L.cin / 8;
-    if (T == 16) {
-        hipLaunchKernelGGL((occ_enc_bwd_dx2_kernel<16>), dim3(tiles_x * tiles_x, groups, n), dim3(256), 0, st, du, dx, w, L.cin, L.cout,
-                           L.H, L.Ho, tiles_x);
-    } else {
-        const int ng = groups < 4 ? groups : 4;
-        hipLaunchKernelGGL((occ_enc_bwd_dx2_kernel<8>), dim3(tiles_x * tiles_x, groups / ng, n), dim3(64 * ng), 0, st, du, dx, w, L.cin,
-                           L.cout, L.H, L.Ho, tiles_x);
-    }
+    const int ng = groups < 4 ? groups : 4;
+    const dim3 grid = T == 16 ? dim3(tiles_x * tiles_x, groups, n) : dim3(tiles_x * tiles_x, groups / ng, n);
+    const dim3 block(T == 16 ? 256 : 64 * ng);
+    const EncSkipGrad s = sk ? *sk : EncSkipGrad{nullptr, nullptr, nullptr, nullptr};
+#define OCC_ENC_DX2(TT, JOIN) \
+    hipLaunchKernelGGL((occ_enc_bwd_dx2_kernel<TT, JOIN>), grid, block, 0, st, du, dx, w, L.cin, L.cout, L.H, L.Ho, tiles_x, s)
+    if (s.gp) OCC_ENC_DX2(16, 2);
+    else if (s.add && T == 16) OCC_ENC_DX2(16, 1);
+    else if (s.add) OCC_ENC_DX2(8, 1);
+    else if (T == 16) OCC_ENC_DX2(16, 0);
+    else OCC_ENC_DX2(8, 0);
+#undef OCC_ENC_DX2
 }
 
-// One layer's parameter gradients from its dY (or, pool, from grad_feats): dU is left in `du`.  4 launches.
+// One layer's parameter gradients from its dY (or, pool, from grad_feats and, when not null, dy): dU is left in `du`.
+// 4 launches.
 static void enc_bwd_layer(const EncLayer& L, const float* packed, float* grad_packed, int n, const float* x, const float* r,
                           const float* dy, float* du, const float* gf, char* scratch, hipStream_t st) {
     const int plane = L.Ho * L.Ho, chunks = bwd_chunks(plane);
@@ -608,7 +653,7 @@ static void enc_bwd_layer(const EncLayer& L, const float* packed, float* grad_pa
     const float* bns = w + 9LL * L.cin * L.cout + L.cout;
     const dim3 agrid(chunks, L.cout, n);
     if (gf)
-        hipLaunchKernelGGL((occ_enc_bwd_act_kernel<true>), agrid, dim3(256), 0, st, nullptr, du, r, bns, L.cout, plane, gf,
+        hipLaunchKernelGGL((occ_enc_bwd_act_kernel<true>), agrid, dim3(256), 0, st, dy, du, r, bns, L.cout, plane, gf,
                            (float)plane, (double*)scratch);
     else
         hipLaunchKernelGGL((occ_enc_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, du, r, bns, L.cout, plane, nullptr, 1.f,
@@ -625,8 +670,15 @@ static void enc_bwd_layer(const EncLayer& L, const float* packed, float* grad_pa
 // The backward of the latest enc_train_forward on this workspace, the deepest layer first: 79 launches.  grad_packed is
 // overwritten.  Gradient buffers per level: gA holds the down's dY / dU, gB the dY of Layer 2's output (kept for the
 // residual), gC Layer 2's dU and then the block input's gradient, which is the gA of the level above.
+// join (occ_fullnet_bwd.hpp): the decoder's gradients that meet the encoder's: dlast joins the pool backward in the last
+// down's activation step, skip[lv] joins the dY of cc[lv] in the epilogue of the down's input gradient.
+struct EncJoin {
+    const float* dlast;             // (n, 256, H_5, H_5)
+    EncSkipGrad skip[kEncLevels];
+};
+
 static void enc_backward(int img, bool residual, const float* packed, int n, char* ws, const float* grad_feats, char* scratch,
-                         float* grad_packed, hipStream_t st) {
+                         float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n);
     EncLayer L[16];
     enc_train_layers(img, L);
@@ -635,8 +687,9 @@ static void enc_backward(int img, bool residual, const float* packed, int n, cha
     for (int lv = kEncLevels - 1; lv >= 0; --lv) {
         const EncLayer* Ll = L + 1 + 3 * lv;
         const bool last = lv == kEncLevels - 1;
-        enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), gA, gA, last ? grad_feats : nullptr, scratch, st);
-        enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st);
+        enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), last ? (join ? join->dlast : nullptr) : gA, gA,
+                      last ? grad_feats : nullptr, scratch, st);
+        enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st, join ? &join->skip[lv] : nullptr);
         enc_bwd_layer(Ll[1], packed, grad_packed, n, F(l.b[lv]), F(l.r2[lv]), gB, gC, nullptr, scratch, st);
         enc_launch_dx1(gC, gA, nullptr, packed + Ll[1].woff, Ll[1], n, st);
         enc_bwd_layer(Ll[0], packed, grad_packed, n, F(l.a[lv]), F(l.r1[lv]), gA, gA, nullptr, scratch, st);

@@ -62,6 +62,7 @@ namespace occ {
 #include "occ_decoder.hpp"
 #include "occ_decoder_bwd.hpp"
 #include "occ_encoder_bwd.hpp"
+#include "occ_fullnet_bwd.hpp"
 #include "occ_criterion.hpp"
 
 }  // namespace occ
@@ -728,6 +729,48 @@ extern "C" int occ_encoder_backward(const OccEncoderConfig* cfg, const float* pa
     const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env);
     if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
     enc_backward(cfg->img, cfg->residual != 0, packed, n_env, (char*)ws, grad_feats, (char*)scratch, grad_packed, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- joint training of encoder, decoder and classifier (occ_fullnet_bwd.hpp) ---------------------------------------------
+static bool full_train_cfg_ok(const OccEncoderConfig* c, int n_env) { return enc_train_cfg_ok(c, n_env) && c->img % 32 == 0; }
+
+extern "C" int occ_fullnet_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
+    if (!full_train_cfg_ok(cfg, n_env) || !ws_bytes || !scratch_bytes) return OCC_ERR_ARG;
+    const FullTrainWs l = full_train_ws_layout(cfg->img, n_env);
+    *ws_bytes = l.total;
+    *scratch_bytes = l.scratch;
+    return OCC_OK;
+}
+
+extern "C" int occ_fullnet_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
+                                         const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
+                                         void* stream) {
+    if (!full_train_cfg_ok(cfg, n_env) || !enc_packed || !dec_packed || !obs || !ws || !feats || !prob) return OCC_ERR_ARG;
+    // the quad rows are stored as float2
+    if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)prob & 7) != 0 ||
+        (((uintptr_t)enc_packed | (uintptr_t)dec_packed | (uintptr_t)obs | (uintptr_t)feats) & 3) != 0)
+        return OCC_ERR_ARG;
+    if (ws_bytes < full_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
+    full_train_forward(cfg->img, cfg->residual != 0, enc_packed, dec_packed, obs, n_env, (char*)ws, feats, prob, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env,
+                                    void* ws, size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch,
+                                    size_t scratch_bytes, float* grad_enc_packed, float* grad_dec_packed, void* stream) {
+    if (!full_train_cfg_ok(cfg, n_env) || !enc_packed || !dec_packed || !ws || !grad_feats || !grad_prob || !scratch ||
+        !grad_enc_packed || !grad_dec_packed)
+        return OCC_ERR_ARG;
+    // the planes are read as float4, the partials are doubles
+    if ((((uintptr_t)ws | (uintptr_t)scratch | (uintptr_t)grad_prob) & 15) != 0 ||
+        (((uintptr_t)enc_packed | (uintptr_t)dec_packed | (uintptr_t)grad_feats | (uintptr_t)grad_enc_packed |
+          (uintptr_t)grad_dec_packed) & 3) != 0)
+        return OCC_ERR_ARG;
+    const FullTrainWs l = full_train_ws_layout(cfg->img, n_env);
+    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
+    full_backward(cfg->img, cfg->residual != 0, enc_packed, dec_packed, n_env, (char*)ws, grad_feats, grad_prob, (char*)scratch,
+                  grad_enc_packed, grad_dec_packed, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

@@ -323,6 +323,10 @@ class FrozenEncoder:
         new.encoder_state = encoder_tensors(sd, prefix, separable, ghead)
         return new
 
+    def with_state(self, sd) -> "FrozenEncoder":
+        """``with_encoder(sd).with_decoder(sd)``: the whole trained network of ``fullnet.TrainableFullNetwork.state_dict()``."""
+        return self.with_encoder(sd).with_decoder(sd)
+
     @classmethod
     def from_module(cls, m, device="cuda", max_chunk: int = 256) -> "FrozenEncoder":
         """A ``FullNetwork``, ``PredictorNet`` or ``Segmenter`` module: dilation and residual are read from the module

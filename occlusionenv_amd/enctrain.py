@@ -15,8 +15,8 @@ The parameters sit under the checkpoint's keys, so ``net.state_dict()`` drops ba
 Limits: dense 3x3 convs only (a separable checkpoint raises) at dilation 1.  Deviation from train_predict.py, which trains
 in train mode: BatchNorm keeps its running statistics (buffers here); only its affine parameters train.  A training call is
 one chunk (``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of an earlier forward
-raises.  The gradient reaches the encoder through the pooled feature only: using a ``TrainableEncoder`` under
-``seghead.SegmentationHead`` needs the decoder's skip and input gradients to join the encoder's, which is not built.
+raises.  The gradient reaches the encoder through the pooled feature only; where the segmentation loss trains the encoder
+too (the pretrainer's step), the decoder's skip and input gradients join the encoder's in ``fullnet.TrainableFullNetwork``.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 
 from . import _native as nat
 from .encoder import FEATURES, PRESETS, FrozenEncoder, layer_plan, packed_floats
-from .seghead import bn_param_grads, fold_bn_vectors
+from .seghead import bn_param_grads, fold_bn_vectors, register_under_key
 
 
 def pack_encoder_buffer(layers) -> torch.Tensor:
@@ -130,16 +130,7 @@ class TrainableEncoder(torch.nn.Module):
 
     def _register(self, key: str, t: torch.Tensor, buffer: bool):
         """Register ``t`` under the dotted state-dict key, creating the container modules on the way."""
-        *path, leaf = key.split(".")
-        m = self
-        for name in path:
-            if name not in m._modules:
-                m.add_module(name, torch.nn.Module())
-            m = m._modules[name]
-        if buffer:
-            m.register_buffer(leaf, t.clone())
-        else:
-            m.register_parameter(leaf, torch.nn.Parameter(t.clone()))
+        register_under_key(self, key, t, buffer)
 
     def _cfg(self, img: int):
         return self.enc._cfg(img)

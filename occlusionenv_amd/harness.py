@@ -15,6 +15,8 @@
     target of the gradient predictor, MSE and AdamW on the dense encoder and its head (``enctrain.TrainableEncoder``).
   * ``validate_pretrained`` -- pretrainer.py:162-204 (``val``) itself, on a stored dataset: Loss / Dice / MSE / Accuracy /
     IoU as the means of the per-batch values.
+  * ``pretrain_epoch`` -- pretrainer.py:112-159 (``train``) on a stored dataset: the summed segmentation and gradient loss
+    back-propagated through decoder, skips and encoder at once (``fullnet.TrainableFullNetwork``), AdamW.
 """
 from __future__ import annotations
 
@@ -183,6 +185,55 @@ def train_predictor(venv, enc_or_net, steps: int, lr: float = 1e-4, weight_decay
         losses.append(loss.detach())
     host = torch.stack(losses).cpu().tolist() if losses else []
     return dict(net=net, losses=host, skipped=skipped, steps=len(host))
+
+
+def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = False, lr: float = 1e-3, weight_decay: float = 1e-5,
+                   optimizer=None) -> dict:
+    """One epoch of ``PreTrainer.train()`` (pretrainer.py:112-159) on the device: ``batches`` is any iterable of
+    ``(img, occlusion, grad, _)`` as for ``validate_pretrained``.  Every batch goes through ``net(img)``
+    (``fullnet.TrainableFullNetwork``: one native forward of encoder, decoder and classifier, the grad head in torch), takes
+    ``segmentation.binary_dice_loss`` (``use_dice``) or ``binary_cross_entropy`` of the map plus ``nn.MSELoss()`` or
+    ``nn.SmoothL1Loss(beta=0.01)`` (``use_l1``) of the gradient prediction, runs ``backward`` (one native joint backward)
+    and one ``torch.optim.AdamW`` step (pretrainer.py:91; ``optimizer``: one to carry over epochs, made here when None).
+    ``net_or_enc``: a ``TrainableFullNetwork``, or a dense "ppo" ``FrozenEncoder`` with decoder and grad head, from which one
+    is made.  BatchNorm keeps its running statistics (``fullnet``).  Returned are ``net``, ``optimizer`` and the five numbers
+    the reference prints, computed its way: ``loss``, ``segm_loss``, ``grad_loss`` = the mean over batches of the per-batch
+    losses, ``accuracy`` and ``iou`` = the mean over batches of the per-batch ratios x 100 of the prediction the step learned
+    from (``segmentation.seg_criterion``'s counts); also the pooled ``correct``, ``intersection``, ``union``, ``pixels``
+    and ``batches``.  One host sync, at the end."""
+    from . import segmentation
+    from .fullnet import TrainableFullNetwork
+
+    net = net_or_enc if isinstance(net_or_enc, TrainableFullNetwork) else TrainableFullNetwork.from_encoder(net_or_enc)
+    if not net.has_grad_head or net.enc.preset != "ppo":
+        raise ValueError("pretrain_epoch needs a FullNetwork checkpoint (preset 'ppo') with its gradPredictor head")
+    opt = optimizer if optimizer is not None else torch.optim.AdamW(net.parameters(), lr=lr, weight_decay=weight_decay)
+    dev = net.enc.device
+    rows, totals, pixels = [], None, 0
+    for img, occlusion, grad, *_ in batches:
+        img, occlusion, grad = img.to(dev), occlusion.to(dev), grad.to(dev, torch.float32)
+        opt.zero_grad(set_to_none=True)
+        _pooled, segm, grad_pred = net(img)
+        segm_loss = segmentation.binary_dice_loss(segm, occlusion) if use_dice else segmentation.binary_cross_entropy(segm, occlusion)
+        grad_loss = (torch.nn.functional.smooth_l1_loss(grad_pred, grad, beta=0.01) if use_l1
+                     else torch.nn.functional.mse_loss(grad_pred, grad))
+        loss = grad_loss + segm_loss
+        loss.backward()
+        opt.step()
+        c = segmentation.seg_criterion(segm, occlusion)
+        t = torch.stack([c["correct"].sum(), c["intersection"].sum(), c["union"].sum()])
+        td = t.double()
+        rows.append(torch.stack([loss.detach().double(), segm_loss.detach().double(), grad_loss.detach().double(),
+                                 td[0] / float(segm.numel()), td[1] / td[2]]))
+        totals = t if totals is None else totals + t
+        pixels += segm.numel()
+    if not rows:
+        raise ValueError("pretrain_epoch: no batches")
+    host = torch.cat([torch.stack(rows).mean(0), totals.double()]).cpu().tolist()
+    loss, segm_loss, grad_loss, acc, iou = host[:5]
+    correct, inter, union = (int(x) for x in host[5:])
+    return dict(net=net, optimizer=opt, loss=loss, segm_loss=segm_loss, grad_loss=grad_loss, accuracy=100.0 * acc, iou=100.0 * iou,
+                correct=correct, intersection=inter, union=union, pixels=pixels, batches=len(rows))
 
 
 @torch.no_grad()

@@ -67,6 +67,22 @@ def _align(b: int) -> int:
     return (b + 255) & ~255
 
 
+def register_under_key(module: torch.nn.Module, key: str, t: torch.Tensor, buffer: bool) -> None:
+    """Register a copy of ``t`` on ``module`` under the dotted state-dict key, as a buffer or a parameter, creating the
+    container modules on the way (shared by ``SegmentationHead``, ``enctrain.TrainableEncoder`` and
+    ``fullnet.TrainableFullNetwork``, whose parameters sit under the checkpoint's keys)."""
+    *path, leaf = key.split(".")
+    m = module
+    for name in path:
+        if name not in m._modules:
+            m.add_module(name, torch.nn.Module())
+        m = m._modules[name]
+    if buffer:
+        m.register_buffer(leaf, t.clone())
+    else:
+        m.register_parameter(leaf, torch.nn.Parameter(t.clone()))
+
+
 class _TrainStep(torch.autograd.Function):
     """(obs, head, 22 parameters) -> (prob, pooled features); the gradient goes to the parameters only."""
 
@@ -138,16 +154,7 @@ class SegmentationHead(torch.nn.Module):
 
     def _register(self, key: str, t: torch.Tensor, buffer: bool):
         """Register ``t`` under the dotted state-dict key, creating the container modules on the way."""
-        *path, leaf = key.split(".")
-        m = self
-        for name in path:
-            if name not in m._modules:
-                m.add_module(name, torch.nn.Module())
-            m = m._modules[name]
-        if buffer:
-            m.register_buffer(leaf, t.clone())
-        else:
-            m.register_parameter(leaf, torch.nn.Parameter(t.clone()))
+        register_under_key(self, key, t, buffer)
 
     def _stats(self, j: int):
         stem = f"{self.decoder_prefix}{j}.up.bn."

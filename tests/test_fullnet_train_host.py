@@ -1,0 +1,200 @@
+"""Host-side checks of the joint training path (csrc/occ_fullnet_bwd.hpp, occlusionenv_amd/fullnet.py): the three entry points
+are exported and reject what they do not support before anything is launched, the workspace query is the restated layout,
+the packed layouts round-trip from a whole checkpoint, and the f64 model of tests/fullnet_train_model.py is the composition of
+the encoder's and the decoder's models, its joint gradient the sum of the gradients of its two losses.  No GPU."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from occlusionenv_amd import _native as nat
+from tests import decoder_split_model as dsm
+from tests import encoder_model, segmenter_model
+from tests import encoder_train_model as etm
+from tests import fullnet_train_model as m
+
+SYMBOLS = ("occ_fullnet_train_workspace_query", "occ_fullnet_train_forward", "occ_fullnet_backward")
+P16 = C.c_void_p(4096)  # never dereferenced: every call below is rejected before a launch
+
+
+def _cfg(img=64, dilation=1, residual=1, separable=0):
+    cfg = nat.OccEncoderConfig()
+    cfg.img, cfg.dilation, cfg.residual, cfg.separable = img, dilation, residual, separable
+    return cfg
+
+
+def _query(lib, img, n, **kw):
+    ws, sc = C.c_size_t(), C.c_size_t()
+    rc = lib.occ_fullnet_train_workspace_query(C.byref(_cfg(img, **kw)), n, C.byref(ws), C.byref(sc))
+    return rc, int(ws.value), int(sc.value)
+
+
+def test_symbols_exported_and_abi_stays_12():
+    lib = C.CDLL(nat.LIB_PATH)
+    for name in SYMBOLS:
+        assert hasattr(lib, name) and name in nat.SYMBOLS
+    assert nat.load().occ_abi_version() == 12 == nat.ABI_VERSION
+
+
+def test_workspace_query_is_the_restated_layout():
+    lib = nat.load()
+    pairs = {(s, n) for _p, _r, s, n in m.GRAD_CASES + m.SPLIT_CASES} | {(64, 4), (64, 1), (128, 16), (256, 128), (512, 64), (1024, 1)}
+    assert {(32, 2), (64, 3), (96, 2), (32, 129), (96, 65)} <= pairs
+    for img, n in sorted(pairs):
+        for residual in (0, 1):
+            rc, ws_b, sc_b = _query(lib, img, n, residual=residual)
+            assert rc == 0
+            assert ws_b == m.ws_bytes(img, n), (img, n)
+            assert sc_b == m.scratch_bytes(img, n), (img, n)
+            assert ws_b % 256 == 0
+        # the joint workspace starts with the encoder's, whose size the encoder's own query gives
+        e_ws, e_sc = C.c_size_t(), C.c_size_t()
+        assert lib.occ_encoder_train_workspace_query(C.byref(_cfg(img)), n, C.byref(e_ws), C.byref(e_sc)) == 0
+        assert int(e_ws.value) == m.encoder_ws_bytes(img, n)
+        d_ws, d_sc = C.c_size_t(), C.c_size_t()
+        assert lib.occ_segment_train_workspace_query(C.byref(_cfg(img)), n, C.byref(d_ws), C.byref(d_sc)) == 0
+        assert sc_b == max(int(e_sc.value), int(d_sc.value))
+        # less than the two single workspaces together: one encoder pass, 0.94 kept d skip buffers
+        assert ws_b < int(e_ws.value) + int(d_ws.value)
+    # the d skip of level 0 is not stored: dlast and levels 1..4 only
+    lvl = dsm.level_bytes(256, 8)
+    kept = m.ws_bytes(256, 8) - m.encoder_ws_bytes(256, 8) - 2 * sum(lvl) - dsm.align(4 * 8 * 256 * 256) - 2 * dsm.align(4 * 8 * 256 * 64)
+    assert kept == sum(lvl[:4]) and abs(kept / lvl[4] - 0.9375) < 1e-9
+
+
+def test_query_rejects_what_is_not_supported():
+    lib = nat.load()
+    assert _query(lib, 64, 2)[0] == 0 and _query(lib, 64, 2, residual=0)[0] == 0
+    assert _query(lib, 64, 2, separable=1)[0] == 1
+    assert _query(lib, 64, 2, dilation=2)[0] == 1
+    assert _query(lib, 48, 2)[0] == 1  # S % 32
+    assert _query(lib, 64, 0)[0] == 1 and _query(lib, 64, 65536)[0] == 1 and _query(lib, 32, 65535)[0] == 0
+    assert _query(lib, 0, 2)[0] == 1 and _query(lib, 1056, 2)[0] == 1
+    ws, sc = C.c_size_t(), C.c_size_t()
+    assert lib.occ_fullnet_train_workspace_query(None, 2, C.byref(ws), C.byref(sc)) == 1
+    assert lib.occ_fullnet_train_workspace_query(C.byref(_cfg()), 2, None, C.byref(sc)) == 1
+    assert lib.occ_fullnet_train_workspace_query(C.byref(_cfg()), 2, C.byref(ws), None) == 1
+
+
+def test_argument_checks_need_no_gpu():
+    lib = nat.load()
+    good = _cfg(64)
+    big = 1 << 40
+    _rc, need_ws, need_sc = _query(lib, 64, 2)
+    bad_cfgs = (_cfg(64, separable=1), _cfg(64, dilation=2), _cfg(48), _cfg(64, residual=2))
+    # occ_fullnet_train_forward(cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, stream)
+    full = [C.byref(good), P16, P16, P16, 2, P16, big, P16, P16, None]
+    for i in (0, 1, 2, 3, 5, 7, 8):
+        args = list(full)
+        args[i] = None
+        assert lib.occ_fullnet_train_forward(*args) == 1, i
+    for bad in bad_cfgs:
+        assert lib.occ_fullnet_train_forward(C.byref(bad), *full[1:]) == 1
+    for n in (0, 65536):
+        assert lib.occ_fullnet_train_forward(*full[:4], n, *full[5:]) == 1
+    assert lib.occ_fullnet_train_forward(*full[:6], need_ws - 1, *full[7:]) == 1
+    assert lib.occ_fullnet_train_forward(*full[:5], C.c_void_p(4096 + 8), *full[6:]) == 1  # ws not 16-byte aligned
+    assert lib.occ_fullnet_train_forward(*full[:8], C.c_void_p(4096 + 4), None) == 1  # prob not 8-byte aligned
+    # occ_fullnet_backward(cfg, enc_packed, dec_packed, n_env, ws, ws_bytes, grad_feats, grad_prob, scratch, scratch_bytes,
+    #                      grad_enc_packed, grad_dec_packed, stream)
+    full = [C.byref(good), P16, P16, 2, P16, big, P16, P16, P16, big, P16, P16, None]
+    for i in (0, 1, 2, 4, 6, 7, 8, 10, 11):
+        args = list(full)
+        args[i] = None
+        assert lib.occ_fullnet_backward(*args) == 1, i
+    for bad in bad_cfgs:
+        assert lib.occ_fullnet_backward(C.byref(bad), *full[1:]) == 1
+    for n in (0, 65536):
+        assert lib.occ_fullnet_backward(*full[:3], n, *full[4:]) == 1
+    for i, short in ((5, need_ws - 1), (9, need_sc - 1)):
+        args = list(full)
+        args[i] = short
+        assert lib.occ_fullnet_backward(*args) == 1, i
+    for i in (4, 7, 8):  # ws, grad_prob, scratch: 16-byte aligned
+        args = list(full)
+        args[i] = C.c_void_p(4096 + 8)
+        assert lib.occ_fullnet_backward(*args) == 1, i
+
+
+def test_pack_round_trips_from_a_whole_checkpoint():
+    """Folding and packing the tensors ``TrainableFullNetwork`` holds gives the buffers ``FrozenEncoder`` packs from the
+    same checkpoint, and unpacking gives the tensors back."""
+    from occlusionenv_amd.encoder import DECODER_KEYS, pack_decoder, pack_state_dict
+    from occlusionenv_amd.enctrain import pack_encoder_buffer, unpack_encoder_buffer
+    from occlusionenv_amd.seghead import fold_bn_vectors, pack_decoder_buffer, unpack_decoder_buffer
+
+    for preset in m.PRESETS:
+        sd = {k: v.float() for k, v in m.state_dict(preset, 12).items()}
+        assert set(m.enc_keys(preset) + m.dec_keys(preset) + m.head_keys(preset)) <= set(sd)
+        assert len(m.enc_keys(preset)) == 64 and len(m.dec_keys(preset)) == 22
+
+        def folded(stems):
+            out = []
+            for st in stems:
+                scale, shift, _ = fold_bn_vectors(sd[st + "bn.weight"], sd[st + "bn.bias"], sd[st + "bn.running_mean"],
+                                                  sd[st + "bn.running_var"])
+                out.append((sd[st + "conv.weight"], sd[st + "conv.bias"], scale, shift))
+            return out
+
+        separable, want, _off = pack_state_dict(sd, "encoder.")
+        assert not separable
+        enc = folded(["encoder." + stem for stem, _ci, _co, _s in etm.layers()])
+        got = pack_encoder_buffer(enc)
+        assert np.array_equal(got.numpy(), want)
+        assert all(torch.equal(b[0], f[0]) and torch.equal(b[1], f[1]) for b, f in zip(unpack_encoder_buffer(got), enc))
+        dp, dc = DECODER_KEYS[preset]
+        dec = folded([f"{dp}{j}.up." for j in range(5)])
+        got = pack_decoder_buffer(dec, sd[dc + "weight"], sd[dc + "bias"])
+        assert np.array_equal(got.numpy(), pack_decoder(sd, dp, dc))
+        levels, cw, cb = unpack_decoder_buffer(got)
+        assert all(torch.equal(b[0], f[0]) and torch.equal(b[1], f[1]) for b, f in zip(levels, dec))
+        assert torch.equal(cw, sd[dc + "weight"]) and torch.equal(cb, sd[dc + "bias"])
+
+
+def test_model_is_the_composition_of_the_two_models():
+    """Without gates: pooled is encoder_train_model.encode_gated, the map segmenter_model.decode on segmenter_model.
+    encode_full, bitwise; with its own gates it is the same function up to rounding."""
+    obs = encoder_model.make_obs(41, 2, 64)
+    for preset in m.PRESETS:
+        for residual in (1, 0):
+            sd = m.state_dict(preset)  # the seed of the GPU tests: the liveness below is about them
+            p = segmenter_model.PRESETS[preset]
+            us = []
+            pooled, logit = m.forward_gated(sd, obs, preset, residual, None, us)
+            assert len(us) == 21 and [u.shape[-1] for u in us[16:]] == [4, 8, 16, 32, 64] and us[15].shape[1:] == (256, 2, 2)
+            x_last, skips = segmenter_model.encode_full(sd, obs, p["prefix"], False, 1, bool(residual))
+            feats = segmenter_model.decode(sd, x_last, skips, p["decoder"])
+            want = torch.nn.functional.conv2d(feats, sd[p["classifier"] + "weight"], sd[p["classifier"] + "bias"])
+            assert torch.equal(logit, want) and torch.equal(pooled, x_last.mean(dim=(2, 3)))
+            if residual:  # encode_gated has the preset's residual flag
+                assert torch.equal(pooled, etm.encode_gated(sd, obs, "ppo"))
+            gates = [(u > 0).double() for u in us]
+            pooled_g, logit_g = m.forward_gated(sd, obs, preset, residual, gates)
+            assert torch.allclose(pooled_g, pooled, rtol=1e-12, atol=1e-14) and torch.allclose(logit_g, logit, rtol=1e-12, atol=1e-14)
+            # the fixture's decoder is alive on the dense encoder: every level has open and closed gates, the map both classes
+            assert all(0.02 < float(g.mean()) < 0.98 for g in gates), [float(g.mean()) for g in gates]
+            assert 0.02 < float((logit > 0).double().mean()) < 0.98
+
+
+def test_joint_gradient_is_the_sum_of_the_two():
+    obs = encoder_model.make_obs(43, 2, 32)
+    gen = torch.Generator().manual_seed(44)
+    gf = torch.randn(2, 256, generator=gen, dtype=torch.float64)
+    gp = torch.randn(2, 1, 32, 32, generator=gen, dtype=torch.float64)
+    for preset in m.PRESETS:
+        host = m.HostModel(m.state_dict(preset, 14), preset, 1, obs)
+        us = []
+        host.forward(None, us)
+        gates = [(u > 0).double() for u in us]
+        pooled, prob, _pred = host.forward(gates)
+        joint = host.grads((pooled * gf).sum() + (prob * gp).sum())
+        pooled, prob, _pred = host.forward(gates)
+        a = host.grads((pooled * gf).sum())
+        pooled, prob, _pred = host.forward(gates)
+        b = host.grads((prob * gp).sum())
+        assert len(joint) == 86
+        for k, w in joint.items():
+            assert torch.allclose(a[k] + b[k], w, rtol=1e-11, atol=1e-13 * float(w.abs().max())), k
+        # the pooled feature's loss does not reach the decoder; the map's loss reaches every encoder layer (the join)
+        assert all(float(a[k].abs().max()) == 0.0 for k in m.dec_keys(preset))
+        assert all(float(b[k].abs().max()) > 0.0 for k in m.enc_keys(preset))
