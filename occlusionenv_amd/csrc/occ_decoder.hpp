@@ -206,22 +206,18 @@ inline SegWs seg_ws_layout(int img, int n) {
 
 static void dec_launch_up(const float* x, float* y, const float* skip, const float* w, int cin, int cout, int H, int n,
                           const float* cls, float* prob, float* logit, hipStream_t st) {
-    const int T = H >= 16 ? 16 : 8;
-    const int tiles_x = (H + T - 1) / T;
-    if (cls) {  // the last level: cout = 8, H = S / 2 >= 16
-        hipLaunchKernelGGL((occ_dec_up_kernel<16, 8, true>), dim3(tiles_x * tiles_x, 1, n), dim3(256), 0, st, x, y, skip, w, cin, cout,
-                           H, tiles_x, cls, prob, logit);
-        return;
-    }
-    constexpr int COG = 16;  // 64 accumulators per thread; cout = 128, 64, 32, 16 here
-    if (T == 16) {
-        hipLaunchKernelGGL((occ_dec_up_kernel<16, COG, false>), dim3(tiles_x * tiles_x, cout / COG, n), dim3(256), 0, st, x, y, skip,
-                           w, cin, cout, H, tiles_x, nullptr, nullptr, nullptr);
-    } else {
-        const int ng = cout / COG < 4 ? cout / COG : 4;
-        hipLaunchKernelGGL((occ_dec_up_kernel<8, COG, false>), dim3(tiles_x * tiles_x, cout / (COG * ng), n), dim3(64 * ng), 0, st, x,
-                           y, skip, w, cin, cout, H, tiles_x, nullptr, nullptr, nullptr);
-    }
+    constexpr int COG = 16;  // 64 accumulators per thread; cout = 128, 64, 32, 16 below the last level
+    const int T = enc_tile(H);
+    const TileLaunch l = tile_launch(T, H, cls ? 1 : cout / COG, n);
+    if (cls)  // the last level: cout = 8, H = S / 2 >= 16
+        hipLaunchKernelGGL((occ_dec_up_kernel<16, 8, true>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, cls, prob,
+                           logit);
+    else if (T == 16)
+        hipLaunchKernelGGL((occ_dec_up_kernel<16, COG, false>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, nullptr,
+                           nullptr, nullptr);
+    else
+        hipLaunchKernelGGL((occ_dec_up_kernel<8, COG, false>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, nullptr,
+                           nullptr, nullptr);
 }
 
 // Encoder (17 launches, keeping the skips) + decoder (5 launches): 22 launches.  img % 32 == 0.

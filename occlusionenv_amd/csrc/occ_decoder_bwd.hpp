@@ -32,6 +32,10 @@
 //
 // No floating-point atomics; the split of K is a function of (S, N) alone: every gradient is bitwise the same from call to
 // call.  f32 chains: a thread's accumulator sees at most tiles-per-slice x T^2 / P products before the f64 stage.
+//
+// Host side, shared with occ_encoder_bwd.hpp: DwPlan / dw_split (the K split of a weight gradient) and bwd_layer_tail (what
+// follows a layer's activation step); the grids of the up layers and of the input gradient come from tile_launch
+// (occ_encoder.hpp).
 
 constexpr int kBwdChunk = 4096;   // pixels of one (env, channel) plane per block of the activation step
 constexpr int kBwdDxCC = 8;       // output channels of dU staged per step of the input gradient
@@ -383,29 +387,38 @@ __global__ __launch_bounds__(256) void occ_dec_bwd_sum_kernel(const float* __res
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-// The (ci, co) tile, pixel tile and K split of the weight gradient of decoder level j (cout = 128 >> j).
-struct BwdDwPlan {
+// The (ci, co) tile, pixel tile and K split of one weight gradient, the decoder's (bwd_dw_plan) or the encoder's
+// (enc_dw_plan, occ_encoder_bwd.hpp).
+struct DwPlan {
     int T, cib, cob, pb, grid_y, tiles_x, total_tiles, tps, slices;
     size_t part_bytes;
 };
 
-inline BwdDwPlan bwd_dw_plan(int j, int H, int n) {
-    const int cout = kEncCh << (kEncLevels - 1 - j), cin = 2 * cout;
-    BwdDwPlan p;
-    if (cout >= 64) p.T = 4, p.cib = 64, p.cob = 64;
-    else if (cout == 32) p.T = 4, p.cib = 64, p.cob = 32;
-    else if (cout == 16) p.T = 8, p.cib = 32, p.cob = 16;
-    else p.T = 8, p.cib = 16, p.cob = 8;
-    const int q = (p.cib / 16) * p.cob;
+// The K split for a cib x cob tile of (ci, co) whose one pixel takes q threads, over the T x T tiles of n planes of
+// side x side pixels, aiming at `blocks` blocks per launch: a function of the shapes alone.
+inline DwPlan dw_split(int cib, int cob, int T, int q, int cin, int cout, int side, int n, int blocks) {
+    DwPlan p;
+    p.T = T, p.cib = cib, p.cob = cob;
     p.pb = 256 / (q < 64 ? 64 : q);
-    p.grid_y = (cin / p.cib) * (cout / p.cob);
-    p.tiles_x = (H + p.T - 1) / p.T;
+    p.grid_y = (cin / cib) * (cout / cob);
+    p.tiles_x = (side + T - 1) / T;
     p.total_tiles = n * p.tiles_x * p.tiles_x;
-    const int want = kBwdDwBlocks / p.grid_y;
+    const int want = blocks / p.grid_y;
     p.tps = (p.total_tiles + want - 1) / want;
     p.slices = (p.total_tiles + p.tps - 1) / p.tps;
     p.part_bytes = (size_t)p.slices * p.pb * cin * 9 * cout * sizeof(float);
     return p;
+}
+
+// Decoder level j (cout = 128 >> j): a thread owns 16 ci x 1 co.
+inline DwPlan bwd_dw_plan(int j, int H, int n) {
+    const int cout = kEncCh << (kEncLevels - 1 - j);
+    int T, cib, cob;
+    if (cout >= 64) T = 4, cib = 64, cob = 64;
+    else if (cout == 32) T = 4, cib = 64, cob = 32;
+    else if (cout == 16) T = 8, cib = 32, cob = 16;
+    else T = 8, cib = 16, cob = 8;
+    return dw_split(cib, cob, T, (cib / 16) * cob, 2 * cout, cout, H, n, kBwdDwBlocks);
 }
 
 inline int bwd_chunks(int plane) { return (plane + kBwdChunk - 1) / kBwdChunk; }
@@ -466,22 +479,18 @@ inline TrainPtrs train_ptrs(const TrainWs& l, char* ws) {
 
 static void dec_launch_up_train(const float* x, float* y, float* r, const float* skip, const float* w, int cin, int cout, int H,
                                 int n, const float* cls, float* prob, float* pkeep, hipStream_t st) {
-    const int T = H >= 16 ? 16 : 8;  // the grids of dec_launch_up
-    const int tiles_x = (H + T - 1) / T;
-    if (cls) {
-        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, 8, true>), dim3(tiles_x * tiles_x, 1, n), dim3(256), 0, st, x, y, r, skip, w,
-                           cin, cout, H, tiles_x, cls, prob, pkeep);
-        return;
-    }
     constexpr int COG = 16;
-    if (T == 16) {
-        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, COG, false>), dim3(tiles_x * tiles_x, cout / COG, n), dim3(256), 0, st, x, y, r,
-                           skip, w, cin, cout, H, tiles_x, nullptr, nullptr, nullptr);
-    } else {
-        const int ng = cout / COG < 4 ? cout / COG : 4;
-        hipLaunchKernelGGL((occ_dec_up_train_kernel<8, COG, false>), dim3(tiles_x * tiles_x, cout / (COG * ng), n), dim3(64 * ng), 0,
-                           st, x, y, r, skip, w, cin, cout, H, tiles_x, nullptr, nullptr, nullptr);
-    }
+    const int T = enc_tile(H);
+    const TileLaunch l = tile_launch(T, H, cls ? 1 : cout / COG, n);  // the grids of dec_launch_up
+    if (cls)
+        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, 8, true>), l.grid, l.block, 0, st, x, y, r, skip, w, cin, cout, H, l.tiles_x,
+                           cls, prob, pkeep);
+    else if (T == 16)
+        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, COG, false>), l.grid, l.block, 0, st, x, y, r, skip, w, cin, cout, H, l.tiles_x,
+                           nullptr, nullptr, nullptr);
+    else
+        hipLaunchKernelGGL((occ_dec_up_train_kernel<8, COG, false>), l.grid, l.block, 0, st, x, y, r, skip, w, cin, cout, H, l.tiles_x,
+                           nullptr, nullptr, nullptr);
 }
 
 // The five up levels on t.last and t.skip, keeping y_j, r_j and p: 5 launches.
@@ -514,10 +523,39 @@ static void seg_train_forward(int img, int dil, bool residual, bool separable, c
 }
 
 template <int T, int CIB, int COB>
-static void bwd_launch_dw(const BwdDwPlan& p, const float* x, const float* du, float* part, int cin, int cout, int H,
+static void bwd_launch_dw(const DwPlan& p, const float* x, const float* du, float* part, int cin, int cout, int H,
                           hipStream_t st) {
     hipLaunchKernelGGL((occ_dec_bwd_dw_kernel<T, CIB, COB>), dim3(p.slices, p.grid_y), dim3(256), 0, st, x, du, part, cin, cout, H,
                        p.tiles_x, p.total_tiles, p.tps);
+}
+
+// The four (ci, co) tiles of bwd_dw_plan.
+static void dec_launch_dw(const DwPlan& p, const float* x, const float* du, float* part, int cin, int cout, int H, hipStream_t st) {
+    if (p.cob == 64) bwd_launch_dw<4, 64, 64>(p, x, du, part, cin, cout, H, st);
+    else if (p.cob == 32) bwd_launch_dw<4, 64, 32>(p, x, du, part, cin, cout, H, st);
+    else if (p.cob == 16) bwd_launch_dw<8, 32, 16>(p, x, du, part, cin, cout, H, st);
+    else bwd_launch_dw<8, 16, 8>(p, x, du, part, cin, cout, H, st);
+}
+
+// The input gradient of one level: dx (n, cin, H, H) from du (n, cout, 2H, 2H).
+static void dec_launch_dx(const float* du, float* dx, const float* w, int cin, int cout, int H, int n, hipStream_t st) {
+    const int T = enc_tile(H);
+    const TileLaunch l = tile_launch(T, H, cin / kBwdDxCIG, n);
+    if (T == 16) hipLaunchKernelGGL((occ_dec_bwd_dx_kernel<16>), l.grid, l.block, 0, st, du, dx, w, cin, cout, H, l.tiles_x);
+    else hipLaunchKernelGGL((occ_dec_bwd_dx_kernel<8>), l.grid, l.block, 0, st, du, dx, w, cin, cout, H, l.tiles_x);
+}
+
+// What follows the activation step of one layer, the decoder's or the encoder's: the block partials of its `sums`
+// per-channel sums (in scratch, n_part per sum and channel) added into dst, then the weight gradient from the layer's input
+// and dU: launch_dw(part) writes the partials of plan p to scratch, which are added into gw.  3 launches.
+template <class LaunchDw>
+static void bwd_layer_tail(const DwPlan& p, int cin, int cout, int n_part, int sums, const BwdActDst& dst, char* scratch, float* gw,
+                           hipStream_t st, LaunchDw launch_dw) {
+    hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(cout, sums), dim3(64), 0, st, (const double*)scratch, n_part, sums, dst);
+    float* part = (float*)scratch;
+    launch_dw(part);
+    const int nout = 9 * cin * cout;
+    hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, part, p.slices * p.pb, nout, gw);
 }
 
 // Where the joint training (occ_fullnet_bwd.hpp) keeps the decoder's gradients that the encoder's backward reads.
@@ -562,29 +600,11 @@ static void dec_backward(int img, const float* dec_packed, int n, const TrainPtr
         else
             hipLaunchKernelGGL((occ_dec_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, g, t.r[j], w + 9LL * cin * c + c, c, plane,
                                nullptr, nullptr, nullptr, nullptr, (double*)scratch);
-        hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(c, last ? 5 : 3), dim3(64), 0, st, (const double*)scratch, n * chunks,
-                           last ? 5 : 3, dst);
-        const BwdDwPlan p = bwd_dw_plan(j, H, n);
-        float* part = (float*)scratch;
-        if (c >= 64) bwd_launch_dw<4, 64, 64>(p, x, g, part, cin, c, H, st);
-        else if (c == 32) bwd_launch_dw<4, 64, 32>(p, x, g, part, cin, c, H, st);
-        else if (c == 16) bwd_launch_dw<8, 32, 16>(p, x, g, part, cin, c, H, st);
-        else bwd_launch_dw<8, 16, 8>(p, x, g, part, cin, c, H, st);
-        const int nout = 9 * cin * c;
-        hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, part, p.slices * p.pb, nout, gw);
-        if (j > 0 || join) {
-            float* dx = !join ? t.g[(kEncLevels - j) % 2] : j > 0 ? join->dskip[lv + 1] : join->dlast;  // dY of level j - 1
-            const int T = H >= 16 ? 16 : 8;
-            const int tiles_x = (H + T - 1) / T;
-            if (T == 16) {
-                hipLaunchKernelGGL((occ_dec_bwd_dx_kernel<16>), dim3(tiles_x * tiles_x, cin / kBwdDxCIG, n), dim3(256), 0, st, g, dx, w,
-                                   cin, c, H, tiles_x);
-            } else {
-                const int ng = cin / kBwdDxCIG < 4 ? cin / kBwdDxCIG : 4;
-                hipLaunchKernelGGL((occ_dec_bwd_dx_kernel<8>), dim3(tiles_x * tiles_x, cin / (kBwdDxCIG * ng), n), dim3(64 * ng), 0, st,
-                                   g, dx, w, cin, c, H, tiles_x);
-            }
-        }
+        const DwPlan p = bwd_dw_plan(j, H, n);
+        bwd_layer_tail(p, cin, c, n * chunks, last ? 5 : 3, dst, scratch, gw, st,
+                       [&](float* part) { dec_launch_dw(p, x, g, part, cin, c, H, st); });
+        if (j > 0 || join)  // into the dY of level j - 1
+            dec_launch_dx(g, !join ? t.g[(kEncLevels - j) % 2] : j > 0 ? join->dskip[lv + 1] : join->dlast, w, cin, c, H, n, st);
     }
 }
 

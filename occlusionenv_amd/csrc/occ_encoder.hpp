@@ -237,6 +237,18 @@ inline int enc_groups(int T, int cout) {  // channel groups per block: 256 threa
     const int ng = cout / enc_cog(cout);
     return ng < 4 ? ng : 4;
 }
+// Grid and block of the kernels whose thread owns one pixel (or quad) of a T x T tile for one of `groups` channel groups
+// (the decoder's up layers and every input gradient): T == 16: one group per block, 256 threads; T == 8: up to 4 groups,
+// 64 ng threads.  The conv forwards differ (enc_groups: the groups depend on COG).
+struct TileLaunch {
+    int tiles_x;
+    dim3 grid, block;
+};
+inline TileLaunch tile_launch(int T, int side, int groups, int n) {
+    const int tiles_x = (side + T - 1) / T;
+    const int ng = T == 16 ? 1 : groups < 4 ? groups : 4;
+    return {tiles_x, dim3(tiles_x * tiles_x, groups / ng, n), dim3(T == 16 ? 256 : 64 * ng)};
+}
 inline int enc_tiles(int ho) {
     const int T = enc_tile(ho);
     const int t = (ho + T - 1) / T;

@@ -37,6 +37,8 @@
 // Launches: train forward 18 (copy, 16 layers, pool); backward 79 (per layer act, act-final, dW, sum = 64, and the input
 // gradient of the 15 layers above the initial one).  No floating-point atomics; the split of K is a function of
 // (S, N) alone: every gradient is bitwise the same from call to call.  Nothing is allocated or synchronised.
+// Host side: the K split (DwPlan, dw_split) and the per-layer tail (bwd_layer_tail) are those of occ_decoder_bwd.hpp, the
+// grids of the two input gradients come from tile_launch (occ_encoder.hpp).
 //
 // Workspace (occ_encoder_train_workspace_query), every part 256-byte aligned, f32, H_0 = S, H_{lv+1} = ceil(H_lv / 2),
 // c = 8 << lv:
@@ -462,27 +464,11 @@ inline void enc_train_layers(int img, EncLayer* L) {
     }
 }
 
-// The (ci, co) tile, pixel tile and K split of the weight gradient of one layer.
-struct EncDwPlan {
-    int T, cib, cob, pb, grid_y, tiles_x, total_tiles, tps, slices;
-    size_t part_bytes;
-};
-
-inline EncDwPlan enc_dw_plan(int cin, int cout, int Ho, int n) {
-    EncDwPlan p;
-    p.cib = cin < 64 ? cin : 64;
-    p.cob = cout < 32 ? cout : 32;
-    p.T = p.cib == 64 ? 4 : 8;
-    const int q = p.cib * (p.cob / kEncDwCot);
-    p.pb = 256 / (q < 64 ? 64 : q);
-    p.grid_y = (cin / p.cib) * (cout / p.cob);
-    p.tiles_x = (Ho + p.T - 1) / p.T;
-    p.total_tiles = n * p.tiles_x * p.tiles_x;
-    const int want = kEncDwBlocks / p.grid_y;
-    p.tps = (p.total_tiles + want - 1) / want;
-    p.slices = (p.total_tiles + p.tps - 1) / p.tps;
-    p.part_bytes = (size_t)p.slices * p.pb * cin * 9 * cout * sizeof(float);
-    return p;
+// The (ci, co) tile, pixel tile and K split (dw_split, occ_decoder_bwd.hpp) of the weight gradient of one layer: a thread
+// owns 1 ci x 8 co.
+inline DwPlan enc_dw_plan(int cin, int cout, int Ho, int n) {
+    const int cib = cin < 64 ? cin : 64, cob = cout < 32 ? cout : 32;
+    return dw_split(cib, cob, cib == 64 ? 4 : 8, cib * (cob / kEncDwCot), cin, cout, Ho, n, kEncDwBlocks);
 }
 
 struct EncTrainWs {
@@ -578,13 +564,13 @@ static void enc_train_forward(int img, bool residual, const float* packed, const
 }
 
 template <int T, int CIB, int COB, int STRIDE>
-static void enc_launch_dw_t(const EncDwPlan& p, const float* x, const float* du, float* part, const EncLayer& L, hipStream_t st) {
+static void enc_launch_dw_t(const DwPlan& p, const float* x, const float* du, float* part, const EncLayer& L, hipStream_t st) {
     hipLaunchKernelGGL((occ_enc_bwd_dw_kernel<T, CIB, COB, STRIDE>), dim3(p.slices, p.grid_y), dim3(256), 0, st, x, du, part, L.cin,
                        L.cout, L.H, L.Ho, p.tiles_x, p.total_tiles, p.tps);
 }
 
 // The nine (ci, co) tiles of enc_dw_plan: stride 1 has cout = cin (4 -> 8 for the initial layer), stride 2 cout = 2 cin.
-static void enc_launch_dw(const EncDwPlan& p, const float* x, const float* du, float* part, const EncLayer& L, hipStream_t st) {
+static void enc_launch_dw(const DwPlan& p, const float* x, const float* du, float* part, const EncLayer& L, hipStream_t st) {
     if (L.stride == 1) {
         if (p.cib == 4) enc_launch_dw_t<8, 4, 8, 1>(p, x, du, part, L, st);
         else if (p.cib == 8) enc_launch_dw_t<8, 8, 8, 1>(p, x, du, part, L, st);
@@ -601,39 +587,24 @@ static void enc_launch_dw(const EncDwPlan& p, const float* x, const float* du, f
 
 static void enc_launch_dx1(const float* du, float* dx, const float* add, const float* w, const EncLayer& L, int n, hipStream_t st) {
     const int T = enc_tile(L.H);
-    const int tiles_x = (L.H + T - 1) / T;
-    if (L.cin == 8) {
-        if (T == 16)
-            hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<16, 8>), dim3(tiles_x * tiles_x, 1, n), dim3(256), 0, st, du, dx, add, w, L.cin,
-                               L.cout, L.H, tiles_x);
-        else
-            hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<8, 8>), dim3(tiles_x * tiles_x, 1, n), dim3(64), 0, st, du, dx, add, w, L.cin,
-                               L.cout, L.H, tiles_x);
-        return;
-    }
-    const int groups = L.cin / kBwdDxCIG;
-    if (T == 16) {
-        hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<16, kBwdDxCIG>), dim3(tiles_x * tiles_x, groups, n), dim3(256), 0, st, du, dx, add,
-                           w, L.cin, L.cout, L.H, tiles_x);
-    } else {
-        const int ng = groups < 4 ? groups : 4;
-        hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<8, kBwdDxCIG>), dim3(tiles_x * tiles_x, groups / ng, n), dim3(64 * ng), 0, st, du,
-                           dx, add, w, L.cin, L.cout, L.H, tiles_x);
-    }
+    const TileLaunch l = tile_launch(T, L.H, L.cin == 8 ? 1 : L.cin / kBwdDxCIG, n);
+#define OCC_ENC_DX1(TT, CIG) \
+    hipLaunchKernelGGL((occ_enc_bwd_dx1_kernel<TT, CIG>), l.grid, l.block, 0, st, du, dx, add, w, L.cin, L.cout, L.H, l.tiles_x)
+    if (L.cin == 8 && T == 16) OCC_ENC_DX1(16, 8);
+    else if (L.cin == 8) OCC_ENC_DX1(8, 8);
+    else if (T == 16) OCC_ENC_DX1(16, kBwdDxCIG);
+    else OCC_ENC_DX1(8, kBwdDxCIG);
+#undef OCC_ENC_DX1
 }
 
 // sk: null, or the d skip to add (sk->add, or sk->gp at level 0, where Ho = S / 2 >= 16).
 static void enc_launch_dx2(const float* du, float* dx, const float* w, const EncLayer& L, int n, hipStream_t st,
                            const EncSkipGrad* sk = nullptr) {
     const int T = enc_tile(L.Ho);
-    const int tiles_x = (L.Ho + T - 1) / T;
-    const int groups = L.cin / 8;
-    const int ng = groups < 4 ? groups : 4;
-    const dim3 grid = T == 16 ? dim3(tiles_x * tiles_x, groups, n) : dim3(tiles_x * tiles_x, groups / ng, n);
-    const dim3 block(T == 16 ? 256 : 64 * ng);
+    const TileLaunch l = tile_launch(T, L.Ho, L.cin / 8, n);
     const EncSkipGrad s = sk ? *sk : EncSkipGrad{nullptr, nullptr, nullptr, nullptr};
 #define OCC_ENC_DX2(TT, JOIN) \
-    hipLaunchKernelGGL((occ_enc_bwd_dx2_kernel<TT, JOIN>), grid, block, 0, st, du, dx, w, L.cin, L.cout, L.H, L.Ho, tiles_x, s)
+    hipLaunchKernelGGL((occ_enc_bwd_dx2_kernel<TT, JOIN>), l.grid, l.block, 0, st, du, dx, w, L.cin, L.cout, L.H, L.Ho, l.tiles_x, s)
     if (s.gp) OCC_ENC_DX2(16, 2);
     else if (s.add && T == 16) OCC_ENC_DX2(16, 1);
     else if (s.add) OCC_ENC_DX2(8, 1);
@@ -659,12 +630,8 @@ static void enc_bwd_layer(const EncLayer& L, const float* packed, float* grad_pa
         hipLaunchKernelGGL((occ_enc_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, du, r, bns, L.cout, plane, nullptr, 1.f,
                            (double*)scratch);
     const BwdActDst dst = {{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
-    hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(L.cout, 3), dim3(64), 0, st, (const double*)scratch, n * chunks, 3, dst);
-    const EncDwPlan p = enc_dw_plan(L.cin, L.cout, L.Ho, n);
-    float* part = (float*)scratch;
-    enc_launch_dw(p, x, du, part, L, st);
-    const int nout = 9 * L.cin * L.cout;
-    hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, part, p.slices * p.pb, nout, gw);
+    const DwPlan p = enc_dw_plan(L.cin, L.cout, L.Ho, n);
+    bwd_layer_tail(p, L.cin, L.cout, n * chunks, 3, dst, scratch, gw, st, [&](float* part) { enc_launch_dw(p, x, du, part, L, st); });
 }
 
 // The backward of the latest enc_train_forward on this workspace, the deepest layer first: 79 launches.  grad_packed is

@@ -2,7 +2,7 @@
 // pretrainer.py below its losses): a forward that keeps what the backward needs, and the backward with respect to every
 // encoder and decoder parameter for two upstream gradients at once, d loss / d feats and d loss / d prob.  Part of the single
 // translation unit occ_kernels.hip (included inside namespace occ, after occ_decoder_bwd.hpp and occ_encoder_bwd.hpp, whose
-// kernels it launches; it has no kernel of its own).
+// kernels it launches; it has no kernel and no launcher of its own: both passes go through dec_backward and enc_backward).
 //
 // Forward: enc_train_forward with the last down also storing its output (18 launches), then dec_train_forward on that
 // output and on the encoder's level tensors cc[lv] as the skips, which are not copied (5 launches): 23 launches.  The FMA

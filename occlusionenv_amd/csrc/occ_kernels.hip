@@ -663,22 +663,44 @@ extern "C" int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 
-// ---- decoder training (occ_decoder_bwd.hpp) ------------------------------------------------------------------------------
-extern "C" int occ_segment_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
-    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || n_env <= 0 || n_env > 65535 || !ws_bytes || !scratch_bytes) return OCC_ERR_ARG;
-    const TrainWs l = train_ws_layout(cfg->img, n_env);
+// ---- training (occ_decoder_bwd.hpp, occ_encoder_bwd.hpp, occ_fullnet_bwd.hpp): the argument checks ----------------------
+static bool seg_train_cfg_ok(const OccEncoderConfig* c, int n_env) {
+    return enc_cfg_ok(c) && c->img % 32 == 0 && n_env >= 1 && n_env <= 65535;
+}
+static bool enc_train_cfg_ok(const OccEncoderConfig* c, int n_env) {
+    return enc_cfg_ok(c) && c->separable == 0 && c->dilation == 1 && n_env >= 1 && n_env <= 65535;
+}
+static bool full_train_cfg_ok(const OccEncoderConfig* c, int n_env) { return enc_train_cfg_ok(c, n_env) && c->img % 32 == 0; }
+
+template <class... P>
+static bool non_null(P... p) {
+    return (... && (p != nullptr));
+}
+// every pointer a multiple of `bytes` (a power of two): 16 where planes are read as float4 or partials are doubles, 8 where
+// quad rows are stored as float2, 4 for plain f32
+template <class... P>
+static bool aligned(uintptr_t bytes, P... p) {
+    return ((... | (uintptr_t)p) & (bytes - 1)) == 0;
+}
+// the answer of the three workspace queries
+template <class Layout>
+static int train_sizes(const Layout& l, size_t* ws_bytes, size_t* scratch_bytes) {
     *ws_bytes = l.total;
     *scratch_bytes = l.scratch;
     return OCC_OK;
 }
 
+// ---- decoder training (occ_decoder_bwd.hpp) ------------------------------------------------------------------------------
+extern "C" int occ_segment_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
+    if (!seg_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    return train_sizes(train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
+}
+
 extern "C" int occ_segment_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
                                          const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
                                          void* stream) {
-    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || !enc_packed || !dec_packed || !obs || n_env <= 0 || n_env > 65535 || !ws ||
-        !feats || !prob)
-        return OCC_ERR_ARG;
-    if ((((uintptr_t)ws & 15) | ((uintptr_t)prob & 7)) != 0) return OCC_ERR_ARG;
+    if (!seg_train_cfg_ok(cfg, n_env) || !non_null(enc_packed, dec_packed, obs, ws, feats, prob)) return OCC_ERR_ARG;
+    if (!aligned(16, ws) || !aligned(8, prob)) return OCC_ERR_ARG;
     if (ws_bytes < train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
     seg_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, obs, n_env,
                       (char*)ws, feats, prob, (hipStream_t)stream);
@@ -687,11 +709,8 @@ extern "C" int occ_segment_train_forward(const OccEncoderConfig* cfg, const floa
 
 extern "C" int occ_segment_backward(const OccEncoderConfig* cfg, const float* dec_packed, int n_env, void* ws, size_t ws_bytes,
                                     const float* grad_prob, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream) {
-    if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || !dec_packed || n_env <= 0 || n_env > 65535 || !ws || !grad_prob || !scratch ||
-        !grad_packed)
-        return OCC_ERR_ARG;
-    // the planes are read as float4, the partials are doubles
-    if ((((uintptr_t)ws | (uintptr_t)grad_prob) & 15) != 0 || ((uintptr_t)scratch & 15) != 0) return OCC_ERR_ARG;
+    if (!seg_train_cfg_ok(cfg, n_env) || !non_null(dec_packed, ws, grad_prob, scratch, grad_packed)) return OCC_ERR_ARG;
+    if (!aligned(16, ws, grad_prob, scratch)) return OCC_ERR_ARG;
     const TrainWs l = train_ws_layout(cfg->img, n_env);
     if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
     seg_backward(cfg->img, dec_packed, n_env, (char*)ws, grad_prob, (char*)scratch, grad_packed, (hipStream_t)stream);
@@ -699,22 +718,15 @@ extern "C" int occ_segment_backward(const OccEncoderConfig* cfg, const float* de
 }
 
 // ---- encoder training (occ_encoder_bwd.hpp) ------------------------------------------------------------------------------
-static bool enc_train_cfg_ok(const OccEncoderConfig* c, int n_env) {
-    return enc_cfg_ok(c) && c->separable == 0 && c->dilation == 1 && n_env >= 1 && n_env <= 65535;
-}
-
 extern "C" int occ_encoder_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
-    if (!enc_train_cfg_ok(cfg, n_env) || !ws_bytes || !scratch_bytes) return OCC_ERR_ARG;
-    const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env);
-    *ws_bytes = l.total;
-    *scratch_bytes = l.scratch;
-    return OCC_OK;
+    if (!enc_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    return train_sizes(enc_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
 }
 
 extern "C" int occ_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env, void* ws,
                                          size_t ws_bytes, float* feats, void* stream) {
-    if (!enc_train_cfg_ok(cfg, n_env) || !packed || !obs || !ws || !feats) return OCC_ERR_ARG;
-    if (((uintptr_t)ws & 15) != 0 || (((uintptr_t)packed | (uintptr_t)obs | (uintptr_t)feats) & 3) != 0) return OCC_ERR_ARG;
+    if (!enc_train_cfg_ok(cfg, n_env) || !non_null(packed, obs, ws, feats)) return OCC_ERR_ARG;
+    if (!aligned(16, ws) || !aligned(4, packed, obs, feats)) return OCC_ERR_ARG;
     if (ws_bytes < enc_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
     enc_train_forward(cfg->img, cfg->residual != 0, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
@@ -722,10 +734,8 @@ extern "C" int occ_encoder_train_forward(const OccEncoderConfig* cfg, const floa
 
 extern "C" int occ_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
                                     const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream) {
-    if (!enc_train_cfg_ok(cfg, n_env) || !packed || !ws || !grad_feats || !scratch || !grad_packed) return OCC_ERR_ARG;
-    // the block partials are doubles
-    if ((((uintptr_t)ws | (uintptr_t)scratch) & 15) != 0 || (((uintptr_t)packed | (uintptr_t)grad_feats | (uintptr_t)grad_packed) & 3) != 0)
-        return OCC_ERR_ARG;
+    if (!enc_train_cfg_ok(cfg, n_env) || !non_null(packed, ws, grad_feats, scratch, grad_packed)) return OCC_ERR_ARG;
+    if (!aligned(16, ws, scratch) || !aligned(4, packed, grad_feats, grad_packed)) return OCC_ERR_ARG;
     const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env);
     if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
     enc_backward(cfg->img, cfg->residual != 0, packed, n_env, (char*)ws, grad_feats, (char*)scratch, grad_packed, (hipStream_t)stream);
@@ -733,24 +743,16 @@ extern "C" int occ_encoder_backward(const OccEncoderConfig* cfg, const float* pa
 }
 
 // ---- joint training of encoder, decoder and classifier (occ_fullnet_bwd.hpp) ---------------------------------------------
-static bool full_train_cfg_ok(const OccEncoderConfig* c, int n_env) { return enc_train_cfg_ok(c, n_env) && c->img % 32 == 0; }
-
 extern "C" int occ_fullnet_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
-    if (!full_train_cfg_ok(cfg, n_env) || !ws_bytes || !scratch_bytes) return OCC_ERR_ARG;
-    const FullTrainWs l = full_train_ws_layout(cfg->img, n_env);
-    *ws_bytes = l.total;
-    *scratch_bytes = l.scratch;
-    return OCC_OK;
+    if (!full_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    return train_sizes(full_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
 }
 
 extern "C" int occ_fullnet_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
                                          const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
                                          void* stream) {
-    if (!full_train_cfg_ok(cfg, n_env) || !enc_packed || !dec_packed || !obs || !ws || !feats || !prob) return OCC_ERR_ARG;
-    // the quad rows are stored as float2
-    if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)prob & 7) != 0 ||
-        (((uintptr_t)enc_packed | (uintptr_t)dec_packed | (uintptr_t)obs | (uintptr_t)feats) & 3) != 0)
-        return OCC_ERR_ARG;
+    if (!full_train_cfg_ok(cfg, n_env) || !non_null(enc_packed, dec_packed, obs, ws, feats, prob)) return OCC_ERR_ARG;
+    if (!aligned(16, ws) || !aligned(8, prob) || !aligned(4, enc_packed, dec_packed, obs, feats)) return OCC_ERR_ARG;
     if (ws_bytes < full_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
     full_train_forward(cfg->img, cfg->residual != 0, enc_packed, dec_packed, obs, n_env, (char*)ws, feats, prob, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
@@ -759,13 +761,10 @@ extern "C" int occ_fullnet_train_forward(const OccEncoderConfig* cfg, const floa
 extern "C" int occ_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env,
                                     void* ws, size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch,
                                     size_t scratch_bytes, float* grad_enc_packed, float* grad_dec_packed, void* stream) {
-    if (!full_train_cfg_ok(cfg, n_env) || !enc_packed || !dec_packed || !ws || !grad_feats || !grad_prob || !scratch ||
-        !grad_enc_packed || !grad_dec_packed)
+    if (!full_train_cfg_ok(cfg, n_env) ||
+        !non_null(enc_packed, dec_packed, ws, grad_feats, grad_prob, scratch, grad_enc_packed, grad_dec_packed))
         return OCC_ERR_ARG;
-    // the planes are read as float4, the partials are doubles
-    if ((((uintptr_t)ws | (uintptr_t)scratch | (uintptr_t)grad_prob) & 15) != 0 ||
-        (((uintptr_t)enc_packed | (uintptr_t)dec_packed | (uintptr_t)grad_feats | (uintptr_t)grad_enc_packed |
-          (uintptr_t)grad_dec_packed) & 3) != 0)
+    if (!aligned(16, ws, scratch, grad_prob) || !aligned(4, enc_packed, dec_packed, grad_feats, grad_enc_packed, grad_dec_packed))
         return OCC_ERR_ARG;
     const FullTrainWs l = full_train_ws_layout(cfg->img, n_env);
     if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;

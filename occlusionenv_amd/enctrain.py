@@ -17,93 +17,28 @@ in train mode: BatchNorm keeps its running statistics (buffers here); only its a
 one chunk (``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of an earlier forward
 raises.  The gradient reaches the encoder through the pooled feature only; where the segmentation loss trains the encoder
 too (the pretrainer's step), the decoder's skip and input gradients join the encoder's in ``fullnet.TrainableFullNetwork``.
+
+The host path (fold, packed layout, parameters under the checkpoint's keys, workspace, the autograd function) is
+``nettrain.TrainableNet``'s, shared with ``seghead`` and ``fullnet``; here are the guards, the native symbols, the grad head
+and the view of the kept activations.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _native as nat
-from .encoder import FEATURES, PRESETS, FrozenEncoder, layer_plan, packed_floats
-from .seghead import bn_param_grads, fold_bn_vectors, register_under_key
+from .encoder import PRESETS, FrozenEncoder
+from .nettrain import TrainableNet, align256, encoder_part
+from .nettrain import pack_encoder_buffer, unpack_encoder_buffer  # noqa: F401  (the encoder's packed layout, importable here)
 
 
-def pack_encoder_buffer(layers) -> torch.Tensor:
-    """layers: sixteen (w (cout,cin,3,3), bias, scale, shift) -> the packed f32 buffer of the dense encoder:
-    w[ci][ky * 3 + kx][co] | bias | scale | shift per layer (``encoder.pack_state_dict``)."""
-    parts = []
-    for w, b, s, t in layers:
-        parts += [w.permute(1, 2, 3, 0).reshape(-1), b.reshape(-1), s.reshape(-1), t.reshape(-1)]
-    buf = torch.cat([p.to(torch.float32) for p in parts])
-    assert buf.numel() == packed_floats(False)
-    return buf
-
-
-def unpack_encoder_buffer(buf: torch.Tensor):
-    """The inverse of ``pack_encoder_buffer`` -> [(w (cout,cin,3,3), bias, scale, shift)] x 16, views of ``buf``."""
-    if buf.numel() != packed_floats(False):
-        raise ValueError(f"packed dense encoder buffer has {buf.numel()} floats, expected {packed_floats(False)}")
-    layers, off = [], 0
-    for _stem, cin, cout, _sep, _stride in layer_plan(False):
-        w = buf[off:off + 9 * cin * cout].reshape(cin, 3, 3, cout).permute(3, 0, 1, 2)
-        off += 9 * cin * cout
-        layers.append((w, buf[off:off + cout], buf[off + cout:off + 2 * cout], buf[off + 2 * cout:off + 3 * cout]))
-        off += 3 * cout
-    return layers
-
-
-def _align(b: int) -> int:
-    return (b + 255) & ~255
-
-
-class _EncStep(torch.autograd.Function):
-    """(obs, net, 64 parameters) -> pooled features; the gradient goes to the parameters only."""
-
-    @staticmethod
-    def forward(ctx, obs, net, *params):
-        layers = []
-        for i in range(len(net.stems)):
-            w, b, gamma, beta = params[4 * i:4 * i + 4]
-            scale, shift, _rstd = fold_bn_vectors(gamma, beta, *net._stats(i))
-            layers.append((w, b, scale, shift))
-        packed = pack_encoder_buffer(layers).contiguous()
-        n, img = int(obs.shape[0]), int(obs.shape[2])
-        ws, _scratch = net._train_buffers(n, img)
-        feats = torch.empty(n, FEATURES, dtype=torch.float32, device=obs.device)
-        net._version += 1
-        net._latest = (n, img)
-        nat.check(nat.load().occ_encoder_train_forward(C.byref(net._cfg(img)), nat.ptr(packed), nat.ptr(obs), n, nat.ptr(ws),
-                                                       ws.numel(), nat.ptr(feats), nat.stream_ptr(obs.device)),
-                  "occ_encoder_train_forward")
-        ctx.net, ctx.packed, ctx.version, ctx.shape = net, packed, net._version, (n, img)
-        return feats
-
-    @staticmethod
-    def backward(ctx, grad_feats):
-        net = ctx.net
-        if ctx.version != net._version:
-            raise RuntimeError("TrainableEncoder: backward of a forward that a later forward has superseded; the kept "
-                               "activations belong to the latest forward (call backward before the next net(obs))")
-        n, img = ctx.shape
-        ws, scratch = net._train_buffers(n, img)
-        g = grad_feats.to(torch.float32).contiguous()
-        gp = torch.empty(packed_floats(False), dtype=torch.float32, device=g.device)
-        nat.check(nat.load().occ_encoder_backward(C.byref(net._cfg(img)), nat.ptr(ctx.packed), n, nat.ptr(ws), ws.numel(), nat.ptr(g),
-                                                  nat.ptr(scratch), scratch.numel(), nat.ptr(gp), nat.stream_ptr(g.device)),
-                  "occ_encoder_backward")
-        grads = []
-        for i, (dw, db, dscale, dshift) in enumerate(unpack_encoder_buffer(gp)):
-            dgamma, dbeta = bn_param_grads(dscale, dshift, *net._stats(i))
-            grads += [dw.contiguous(), db.clone(), dgamma.to(torch.float32), dbeta.to(torch.float32)]
-        return (None, None, *grads)
-
-
-class TrainableEncoder(torch.nn.Module):
+class TrainableEncoder(TrainableNet):
     """The trainable dense encoder (and grad head) of a ``FrozenEncoder``; see the module docstring."""
 
+    SYMBOLS = ("occ_encoder_train_workspace_query", "occ_encoder_train_forward", "occ_encoder_backward")
+    RETURNS = DIFFERENTIABLE = ("feats",)
+    RUNS_DECODER = False
+
     def __init__(self, enc: FrozenEncoder):
-        super().__init__()
         if not isinstance(enc, FrozenEncoder):
             raise ValueError("TrainableEncoder needs a FrozenEncoder")
         if enc.separable:
@@ -112,58 +47,15 @@ class TrainableEncoder(torch.nn.Module):
             raise ValueError(f"the native encoder backward covers dilation 1 only, this encoder has dilation {enc.dilation}")
         if enc.encoder_state is None:
             raise ValueError("this FrozenEncoder keeps no unfolded encoder tensors (build it with from_state_dict)")
-        self.enc = enc  # a plain attribute: the source of the preset, the flags, the device and max_chunk
-        self.prefix, self.grad_prefix = PRESETS[enc.preset][0], PRESETS[enc.preset][1]
-        self.stems = [self.prefix + stem for stem, _ci, _co, _sep, _stride in layer_plan(False)]
-        for key, t in enc.encoder_state.items():
-            t = t.to(enc.device, torch.float32)
-            self._register(key, t, buffer=key.endswith(("running_mean", "running_var")))
+        super().__init__(enc, [encoder_part(enc.preset)], enc.encoder_state)
+        self.stems = self.parts[0].stems
+        self.grad_prefix = PRESETS[enc.preset][1]
         self.has_grad_head = self.grad_prefix is not None and self.grad_prefix + "weight" in enc.encoder_state
         self.grad_tanh = enc.grad_tanh
-        self._version = 0
-        self._latest = None
-        self._bufs = {}
-
-    @classmethod
-    def from_encoder(cls, enc: FrozenEncoder) -> "TrainableEncoder":
-        return cls(enc)
-
-    def _register(self, key: str, t: torch.Tensor, buffer: bool):
-        """Register ``t`` under the dotted state-dict key, creating the container modules on the way."""
-        register_under_key(self, key, t, buffer)
-
-    def _cfg(self, img: int):
-        return self.enc._cfg(img)
-
-    def _stats(self, i: int):
-        return self.get_buffer(self.stems[i] + "bn.running_mean"), self.get_buffer(self.stems[i] + "bn.running_var")
-
-    def ordered_parameters(self):
-        """The 64 encoder parameters in packed order: per layer conv.weight, conv.bias, bn.weight, bn.bias."""
-        names = [stem + t for stem in self.stems for t in ("conv.weight", "conv.bias", "bn.weight", "bn.bias")]
-        return [(k, self.get_parameter(k)) for k in names]
-
-    def _train_buffers(self, n: int, img: int):
-        key = (n, img)
-        if key not in self._bufs:
-            wsb, scb = C.c_size_t(), C.c_size_t()
-            nat.check(nat.load().occ_encoder_train_workspace_query(C.byref(self._cfg(img)), n, C.byref(wsb), C.byref(scb)),
-                      "occ_encoder_train_workspace_query")
-            dev = self.enc.device
-            self._bufs[key] = (torch.empty(int(wsb.value), dtype=torch.uint8, device=dev),
-                               torch.empty(max(int(scb.value), 16), dtype=torch.uint8, device=dev))
-        return self._bufs[key]
 
     def forward(self, obs: torch.Tensor) -> torch.Tensor:
         """The pooled feature (N,256) f32 of the encoder with its current parameters."""
-        self.enc._check_obs(obs, False)
-        n = int(obs.shape[0])
-        if n > self.enc.max_chunk:
-            raise ValueError(f"a training call is one chunk: N = {n} > max_chunk = {self.enc.max_chunk}")
-        if n < 1:
-            raise ValueError("a training call needs at least one env")
-        obs = obs.detach().to(torch.float32).contiguous()
-        return _EncStep.apply(obs, self, *[p for _k, p in self.ordered_parameters()])
+        return self._step(obs)
 
     def predict_grad(self, obs: torch.Tensor) -> torch.Tensor:
         """(N,2): the grad head on ``self(obs)`` in torch: ``FullNetwork.gradPredictor`` (no tanh, model.py:164) or
@@ -183,17 +75,17 @@ class TrainableEncoder(torch.nn.Module):
         def view(off, c, side):
             return ws[off:off + 4 * n * c * side * side].view(torch.float32).view(n, c, side, side)
 
-        off = _align(4 * n * 4 * img * img)  # obs
+        off = align256(4 * n * 4 * img * img)  # obs
         if i == 0:
             return view(off, 8, img)
-        off += _align(4 * n * 8 * img * img)
+        off += align256(4 * n * 8 * img * img)
         side = img
         for lv in range(5):
             c, half = 8 << lv, (side + 1) // 2
-            act = _align(4 * n * c * side * side)
+            act = align256(4 * n * c * side * side)
             r = {1: (off + act, c, side), 2: (off + 3 * act, c, side), 3: (off + 5 * act, 2 * c, half)}
             if (i - 1) // 3 == lv:
                 return view(*r[(i - 1) % 3 + 1])
-            off += 5 * act + _align(4 * n * 2 * c * half * half)
+            off += 5 * act + align256(4 * n * 2 * c * half * half)
             side = half
         raise ValueError(f"layer {i} outside [0, 16)")

@@ -1,0 +1,273 @@
+"""The one host path of the three native training wrappers: ``seghead.SegmentationHead`` (decoder and classifier),
+``enctrain.TrainableEncoder`` (dense encoder) and ``fullnet.TrainableFullNetwork`` (both).  Each of them is a
+``TrainableNet`` over one or two ``Part``s, and one ``torch.autograd.Function`` runs all three: forward folds the current
+BatchNorm parameters on the device in f64, packs every part in the library's layout and runs the native train forward;
+backward runs the native backward and maps each part's packed gradient back to the parameters.
+
+BatchNorm keeps its running statistics (buffers); only its affine parameters train.  A training call is one chunk
+(``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of an earlier forward raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Callable, NamedTuple, Tuple
+
+import torch
+
+from . import _native as nat
+from .encoder import (BN_EPS, CH, DECODER_KEYS, FEATURES, PRESETS, FrozenEncoder, decoder_packed_floats, decoder_plan, layer_plan,
+                      packed_floats)
+
+LEAVES = ("conv.weight", "conv.bias", "bn.weight", "bn.bias")  # the four parameters of a layer, in packed order
+ENCODER_PERM, DECODER_PERM = (1, 2, 3, 0), (0, 2, 3, 1)  # conv (cout,cin,3,3) / transposed conv (cin,cout,3,3) -> (cin,3,3,cout)
+
+
+# ---- the BatchNorm fold and the packed layout, as pure functions of tensors on any device ----------------------------------
+def fold_bn_vectors(gamma, beta, mean, var):
+    """-> (scale, shift, rstd) in f64: y = relu(.) * scale + shift (``encoder.fold_bn`` on c-vectors)."""
+    rstd = 1.0 / torch.sqrt(var.double() + BN_EPS)
+    scale = gamma.double() * rstd
+    return scale, beta.double() - mean.double() * scale, rstd
+
+
+def bn_param_grads(dscale, dshift, mean, var):
+    """(dgamma, dbeta) in f64 from the gradients of the folded affine: scale = gamma rstd, shift = beta - mean gamma rstd."""
+    rstd = 1.0 / torch.sqrt(var.double() + BN_EPS)
+    return (dscale.double() - mean.double() * dshift.double()) * rstd, dshift.double()
+
+
+def pack_layers(layers, perm, tail=()) -> torch.Tensor:
+    """layers: (w, bias, scale, shift) each, ``w.permute(perm)`` being (cin,3,3,cout) -> the packed f32 buffer
+    w[ci][ky * 3 + kx][co] | bias | scale | shift per layer, then the ``tail`` tensors."""
+    parts = []
+    for w, b, s, t in layers:
+        parts += [w.permute(*perm).reshape(-1), b.reshape(-1), s.reshape(-1), t.reshape(-1)]
+    parts += [x.reshape(-1) for x in tail]
+    return torch.cat([p.to(torch.float32) for p in parts])
+
+
+def unpack_layers(buf: torch.Tensor, plan, perm):
+    """The inverse of ``pack_layers`` for layers of ``plan`` = [(cin, cout)] -> ([(w, bias, scale, shift)], views of ``buf``;
+    the offset of the tail)."""
+    inverse = [perm.index(d) for d in range(4)]
+    layers, off = [], 0
+    for cin, cout in plan:
+        w = buf[off:off + 9 * cin * cout].reshape(cin, 3, 3, cout).permute(*inverse)
+        off += 9 * cin * cout
+        layers.append((w, buf[off:off + cout], buf[off + cout:off + 2 * cout], buf[off + 2 * cout:off + 3 * cout]))
+        off += 3 * cout
+    return layers, off
+
+
+def _encoder_plan():
+    return [(cin, cout) for _stem, cin, cout, _sep, _stride in layer_plan(False)]
+
+
+def pack_encoder_buffer(layers) -> torch.Tensor:
+    """layers: sixteen (w (cout,cin,3,3), bias, scale, shift) -> the packed f32 buffer of the dense encoder
+    (``encoder.pack_state_dict``)."""
+    buf = pack_layers(layers, ENCODER_PERM)
+    assert buf.numel() == packed_floats(False)
+    return buf
+
+
+def unpack_encoder_buffer(buf: torch.Tensor):
+    """The inverse of ``pack_encoder_buffer`` -> [(w (cout,cin,3,3), bias, scale, shift)] x 16, views of ``buf``."""
+    if buf.numel() != packed_floats(False):
+        raise ValueError(f"packed dense encoder buffer has {buf.numel()} floats, expected {packed_floats(False)}")
+    return unpack_layers(buf, _encoder_plan(), ENCODER_PERM)[0]
+
+
+def pack_decoder_buffer(levels, cls_w, cls_b) -> torch.Tensor:
+    """levels: five (w (2c,c,3,3), bias, scale, shift) -> the packed f32 buffer of the decoder, then cls_w[8] | cls_b
+    (``encoder.pack_decoder``)."""
+    buf = pack_layers(levels, DECODER_PERM, (cls_w, cls_b))
+    assert buf.numel() == decoder_packed_floats()
+    return buf
+
+
+def unpack_decoder_buffer(buf: torch.Tensor):
+    """The inverse of ``pack_decoder_buffer`` -> ([(w (2c,c,3,3), bias, scale, shift)] x 5, cls_w (1,8,1,1), cls_b (1,))."""
+    if buf.numel() != decoder_packed_floats():
+        raise ValueError(f"packed decoder buffer has {buf.numel()} floats, expected {decoder_packed_floats()}")
+    levels, off = unpack_layers(buf, [(cin, cout) for _j, cin, cout in decoder_plan()], DECODER_PERM)
+    return levels, buf[off:off + CH].reshape(1, CH, 1, 1), buf[off + CH:off + CH + 1]
+
+
+def align256(b: int) -> int:
+    """The 256-byte alignment of every part of a native workspace (include/occlusionenv_amd.h)."""
+    return (b + 255) & ~255
+
+
+def register_under_key(module: torch.nn.Module, key: str, t: torch.Tensor, buffer: bool) -> None:
+    """Register a copy of ``t`` on ``module`` under the dotted state-dict key, as a buffer or a parameter, creating the
+    container modules on the way (the parameters of a ``TrainableNet`` sit under the checkpoint's keys)."""
+    *path, leaf = key.split(".")
+    m = module
+    for name in path:
+        if name not in m._modules:
+            m.add_module(name, torch.nn.Module())
+        m = m._modules[name]
+    if buffer:
+        m.register_buffer(leaf, t.clone())
+    else:
+        m.register_parameter(leaf, torch.nn.Parameter(t.clone()))
+
+
+# ---- a trainable part: where its tensors sit in the checkpoint and how they are packed -------------------------------------
+class Part(NamedTuple):
+    stems: Tuple[str, ...]  # per layer in packed order: stem + LEAVES are its parameters, stem + "bn.running_*" its statistics
+    tail: Tuple[str, ...]   # the parameters packed after the layers
+    floats: int             # of the packed buffer
+    pack: Callable          # (layers, tail tensors) -> packed buffer
+    unpack: Callable        # packed buffer -> (layers, tail tensors)
+
+
+def encoder_part(preset: str) -> Part:
+    """The 16 layers of the dense encoder under ``PRESETS[preset]``'s prefix."""
+    stems = tuple(PRESETS[preset][0] + stem for stem, _ci, _co, _sep, _stride in layer_plan(False))
+    return Part(stems, (), packed_floats(False), lambda layers, _tail: pack_encoder_buffer(layers),
+                lambda buf: (unpack_encoder_buffer(buf), ()))
+
+
+def decoder_part(preset: str) -> Part:
+    """The 5 up levels of the decoder and the 1x1 classifier under ``DECODER_KEYS[preset]``'s prefixes."""
+    prefix, classifier = DECODER_KEYS[preset]
+    stems = tuple(f"{prefix}{j}.up." for j, _ci, _co in decoder_plan())
+
+    def unpack(buf):
+        levels, cls_w, cls_b = unpack_decoder_buffer(buf)
+        return levels, (cls_w, cls_b)
+
+    return Part(stems, (classifier + "weight", classifier + "bias"), decoder_packed_floats(),
+                lambda levels, tail: pack_decoder_buffer(levels, *tail), unpack)
+
+
+# ---- the module and its autograd function ------------------------------------------------------------------------------------
+class TrainableNet(torch.nn.Module):
+    """The trainable ``parts`` of a ``FrozenEncoder``: their tensors (``state``) as parameters, and as buffers for the
+    running statistics, under the checkpoint's keys.  A subclass names its three native entry points (``SYMBOLS``: workspace
+    query, train forward, backward), says which of (feats, prob) its step returns and which of them carry a gradient, and
+    checks its checkpoint before it calls this constructor."""
+
+    SYMBOLS: Tuple[str, str, str]
+    RETURNS: Tuple[str, ...]           # of "feats" (N,256) and "prob" (N,1,S,S), in the order of the step's outputs
+    DIFFERENTIABLE: Tuple[str, ...]    # those the native backward takes a gradient for, in its argument order
+    RUNS_DECODER = True                # the decoder needs S a multiple of 32
+
+    def __init__(self, enc: FrozenEncoder, parts, state):
+        super().__init__()
+        self.enc = enc  # a plain attribute, not part of the state dict: the preset, the flags, the device and max_chunk
+        self.parts = tuple(parts)
+        for key, t in state.items():
+            register_under_key(self, key, t.to(enc.device, torch.float32), buffer=key.endswith(("running_mean", "running_var")))
+        self._version = 0
+        self._latest = None
+        self._bufs = {}
+
+    @classmethod
+    def from_encoder(cls, enc: FrozenEncoder):
+        return cls(enc)
+
+    def _cfg(self, img: int):
+        return self.enc._cfg(img)
+
+    def _stats(self, stem: str):
+        return self.get_buffer(stem + "bn.running_mean"), self.get_buffer(stem + "bn.running_var")
+
+    def ordered_parameters(self):
+        """[(key, parameter)] in packed order, part by part: per layer conv.weight, conv.bias, bn.weight, bn.bias, then the
+        part's tail (the classifier's weight, bias).  A grad head is not among them."""
+        names = []
+        for part in self.parts:
+            names += [stem + leaf for stem in part.stems for leaf in LEAVES]
+            names += part.tail
+        return [(k, self.get_parameter(k)) for k in names]
+
+    def _train_buffers(self, n: int, img: int):
+        """(workspace, scratch) of a training call on n envs of side img, kept per shape."""
+        key = (n, img)
+        if key not in self._bufs:
+            wsb, scb = C.c_size_t(), C.c_size_t()
+            query = self.SYMBOLS[0]
+            nat.check(getattr(nat.load(), query)(C.byref(self._cfg(img)), n, C.byref(wsb), C.byref(scb)), query)
+            dev = self.enc.device
+            self._bufs[key] = (torch.empty(int(wsb.value), dtype=torch.uint8, device=dev),
+                               torch.empty(max(int(scb.value), 16), dtype=torch.uint8, device=dev))
+        return self._bufs[key]
+
+    def _native_forward(self, img, packed, obs, n, ws, outs):
+        """The native train forward on the packed parts; ``outs``: feats and, when the step has one, prob."""
+        name = self.SYMBOLS[1]
+        nat.check(getattr(nat.load(), name)(C.byref(self._cfg(img)), *[nat.ptr(p) for p in packed], nat.ptr(obs), n, nat.ptr(ws),
+                                            ws.numel(), *[nat.ptr(o) for o in outs], nat.stream_ptr(obs.device)), name)
+
+    def _native_backward(self, img, packed, n, ws, grads_in, scratch, grads_out):
+        """The native backward of the latest forward: upstream ``grads_in`` -> one packed gradient per part."""
+        name = self.SYMBOLS[2]
+        nat.check(getattr(nat.load(), name)(C.byref(self._cfg(img)), *[nat.ptr(p) for p in packed], n, nat.ptr(ws), ws.numel(),
+                                            *[nat.ptr(g) for g in grads_in], nat.ptr(scratch), scratch.numel(),
+                                            *[nat.ptr(g) for g in grads_out], nat.stream_ptr(grads_in[0].device)), name)
+
+    def _step(self, obs: torch.Tensor):
+        """The checks of a training call and the autograd function on it -> the outputs named by ``RETURNS``."""
+        self.enc._check_obs(obs, self.RUNS_DECODER)
+        n = int(obs.shape[0])
+        if n > self.enc.max_chunk:
+            raise ValueError(f"a training call is one chunk: N = {n} > max_chunk = {self.enc.max_chunk}")
+        if n < 1:
+            raise ValueError("a training call needs at least one env")
+        obs = obs.detach().to(torch.float32).contiguous()
+        return _NetStep.apply(obs, self, *[p for _k, p in self.ordered_parameters()])
+
+
+class _NetStep(torch.autograd.Function):
+    """(obs, net, the parameters of ``net.ordered_parameters()``) -> the outputs ``net.RETURNS``; the gradient goes to the
+    parameters only."""
+
+    @staticmethod
+    def forward(ctx, obs, net, *params):
+        folded, at = [], 0
+        for part in net.parts:
+            layers = []
+            for stem in part.stems:
+                w, b, gamma, beta = params[at:at + 4]
+                scale, shift, _rstd = fold_bn_vectors(gamma, beta, *net._stats(stem))
+                layers.append((w, b, scale, shift))
+                at += 4
+            folded.append((layers, params[at:at + len(part.tail)]))
+            at += len(part.tail)
+        packed = [part.pack(layers, tail).contiguous() for part, (layers, tail) in zip(net.parts, folded)]
+        n, img = int(obs.shape[0]), int(obs.shape[2])
+        ws, _scratch = net._train_buffers(n, img)
+        out = {"feats": torch.empty(n, FEATURES, dtype=torch.float32, device=obs.device)}
+        if "prob" in net.RETURNS:
+            out["prob"] = torch.empty(n, 1, img, img, dtype=torch.float32, device=obs.device)
+        net._version += 1
+        net._latest = (n, img)
+        net._native_forward(img, packed, obs, n, ws, list(out.values()))
+        ctx.net, ctx.packed, ctx.version, ctx.shape = net, packed, net._version, (n, img)
+        if len(net.DIFFERENTIABLE) < len(net.RETURNS):
+            ctx.mark_non_differentiable(*[out[k] for k in net.RETURNS if k not in net.DIFFERENTIABLE])
+        return out[net.RETURNS[0]] if len(net.RETURNS) == 1 else tuple(out[k] for k in net.RETURNS)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        net = ctx.net
+        if ctx.version != net._version:
+            raise RuntimeError(f"{type(net).__name__}: backward of a forward that a later forward has superseded; the kept "
+                               "activations belong to the latest forward (call backward before the next forward)")
+        n, img = ctx.shape
+        ws, scratch = net._train_buffers(n, img)
+        upstream = dict(zip(net.RETURNS, grads))
+        grads_in = [upstream[k].to(torch.float32).contiguous() for k in net.DIFFERENTIABLE]
+        grads_out = [torch.empty(part.floats, dtype=torch.float32, device=grads_in[0].device) for part in net.parts]
+        net._native_backward(img, ctx.packed, n, ws, grads_in, scratch, grads_out)
+        result = [None, None]
+        for part, gp in zip(net.parts, grads_out):
+            layers, tail = part.unpack(gp)
+            for stem, (dw, db, dscale, dshift) in zip(part.stems, layers):
+                dgamma, dbeta = bn_param_grads(dscale, dshift, *net._stats(stem))
+                result += [dw.contiguous(), db.clone(), dgamma.to(torch.float32), dbeta.to(torch.float32)]
+            result += [t.clone() for t in tail]
+        return tuple(result)

@@ -42,6 +42,8 @@ import torch.nn.functional as F
 from tests import criterion_model, decoder_split_model
 from tests.encoder_model import make_obs
 from tests.segmenter_model import PRESETS, encode_full, golden_seg_state_dict, up_conv
+from tests.train_utils import GUARD, bce64, dice64
+from tests.train_utils import guarded as _guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -112,16 +114,6 @@ class HostModel:
             v.grad = None
         loss.backward()
         return {k: v.grad.clone() for k, v in self.params.items()}
-
-
-def dice64(p, t):
-    p, t = p.reshape(p.shape[0], -1), t.reshape(t.shape[0], -1).double()
-    return (1.0 - ((p * t).sum(1) + 1.0) / ((p * p).sum(1) + (t * t).sum(1) + 1.0)).mean()
-
-
-def bce64(p, t):
-    t = t.reshape(p.shape).double()
-    return (-(t * torch.log(p).clamp_min(-100.0) + (1.0 - t) * torch.log(1.0 - p).clamp_min(-100.0))).mean()
 
 
 def _head_grads(head):
@@ -283,17 +275,6 @@ def test_gradients_of_one_env(runs, env):
     want = host.grads((p64 * up.double()).sum())
     assert len(want) == 22
     _check_grads(f"one-hot env {env} {preset} S={img} N={n}", got, want)
-
-
-GUARD = 4096
-
-
-def _guarded(nbytes):
-    """-> (whole, lo): a u8 allocation filled with 0xA5 whose window [lo, lo + nbytes) is 256-byte aligned and has at least
-    GUARD bytes in front of it and behind it."""
-    whole = torch.full((nbytes + 2 * GUARD + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-    lo = GUARD + (-(whole.data_ptr() + GUARD)) % 256
-    return whole, lo
 
 
 def test_no_stale_reads_and_nothing_outside_the_reported_sizes(runs):

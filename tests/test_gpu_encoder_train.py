@@ -37,6 +37,9 @@ import torch.nn.functional as F
 
 from tests import encoder_train_model as m
 from tests.encoder_model import make_obs
+from tests.train_utils import GUARD
+from tests.train_utils import grads as _grads
+from tests.train_utils import guarded as _guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -62,10 +65,6 @@ def nets():
         kw = dict(dilation=1, residual=True) if preset == "ppo" else {}
         out[preset] = (sd32, sd64, FrozenEncoder.from_state_dict(sd32, preset=preset, **kw))
     return out
-
-
-def _grads(net):
-    return {k: p.grad.detach().clone() for k, p in net.named_parameters() if p.grad is not None}
 
 
 @pytest.fixture(scope="module")
@@ -194,17 +193,6 @@ def test_reproducible_and_accumulating(runs):
     net(obs).backward(up)  # without zero_grad the second pass accumulates as torch does: g + g, exact
     assert all(torch.equal(v, once[k] + once[k]) for k, v in _grads(net).items())
     net.zero_grad()
-
-
-GUARD = 4096
-
-
-def _guarded(nbytes):
-    """-> (whole, lo): a u8 allocation filled with 0xA5 whose window [lo, lo + nbytes) is 256-byte aligned and has at least
-    GUARD bytes in front of it and behind it."""
-    whole = torch.full((nbytes + 2 * GUARD + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-    lo = GUARD + (-(whole.data_ptr() + GUARD)) % 256
-    return whole, lo
 
 
 @pytest.mark.parametrize("preset,img,n", [SPLIT, ("predictor", 40, 3)], ids=[IDS[6], IDS[2]])

@@ -24,6 +24,11 @@ from tests import decoder_split_model as dsm
 from tests import encoder_train_model as etm
 from tests import fullnet_train_model as m
 from tests.encoder_model import make_obs
+from tests.train_utils import GUARD
+from tests.train_utils import bce64 as _bce64
+from tests.train_utils import dice64 as _dice64
+from tests.train_utils import grads as _grads
+from tests.train_utils import guarded as _guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -48,10 +53,6 @@ def nets():
         for residual in (1, 0):
             out[preset, residual] = (sd32, sd64, FrozenEncoder.from_state_dict(sd32, preset=preset, dilation=1, residual=bool(residual)))
     return out
-
-
-def _grads(net):
-    return {k: p.grad.detach().clone() for k, p in net.named_parameters() if p.grad is not None}
 
 
 def _gates(net):
@@ -130,16 +131,6 @@ def test_gradients_against_f64_autograd(runs, preset, residual, img, n):
     want = host.grads((pooled * r["gf"].double()).sum() + (prob * r["gp"].double()).sum())
     assert len(want) == 86 and set(want) <= set(r["grads"])
     _check_grads(f"{preset} res{residual} S={img} N={n}", preset, r["grads"], want)
-
-
-def _dice64(p, t):
-    p, t = p.reshape(p.shape[0], -1), t.reshape(t.shape[0], -1).double()
-    return (1.0 - ((p * t).sum(1) + 1.0) / ((p * p).sum(1) + (t * t).sum(1) + 1.0)).mean()
-
-
-def _bce64(p, t):
-    t = t.reshape(p.shape).double()
-    return (-(t * torch.log(p).clamp_min(-100.0) + (1.0 - t) * torch.log(1.0 - p).clamp_min(-100.0))).mean()
 
 
 @pytest.mark.parametrize("losses", ["dice+mse", "bce+smoothl1"])
@@ -235,17 +226,6 @@ def test_bitwise_against_the_two_single_passes(runs, preset, residual, img, n):
     torch.autograd.backward([feats, prob], [r["gf"].cuda(), r["gp"].cuda()])
     again = _grads(net)
     assert len(again) >= 86 and all(torch.equal(v.cpu(), r["grads"][k]) for k, v in again.items())
-
-
-GUARD = 4096
-
-
-def _guarded(nbytes):
-    """-> (whole, lo): a u8 allocation filled with 0xA5 whose window [lo, lo + nbytes) is 256-byte aligned and has at least
-    GUARD bytes in front of it and behind it."""
-    whole = torch.full((nbytes + 2 * GUARD + 256,), 0xA5, dtype=torch.uint8, device="cuda")
-    lo = GUARD + (-(whole.data_ptr() + GUARD)) % 256
-    return whole, lo
 
 
 @pytest.mark.parametrize("preset,residual,img,n", [("ppo", 1, 96, 2), ("ppo", 1, 32, 129)])
