@@ -478,6 +478,44 @@ int occ_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n
                          const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream);
 
 /*
+ * Training of the separable encoder through its pooled feature (additive in ABI 12; csrc/occ_sepenc_bwd.hpp): the
+ * counterpart of the three entry points above for cfg->separable == 1, what training FullNetwork(8, dilation=2,
+ * separable=True)'s encoder (PPO.py:47) or PredictorNet(8, separable=True) (pred_train.py:35) needs below the Linear(256, 2)
+ * head.  Supported: cfg->separable == 1, cfg->dilation 1 or 2, cfg->residual 0 or 1, img in [32, 1024] (odd intermediate
+ * sides included), n_env in [1, 65535].  A separable layer (initial at dilation 1; Layer 1 and Layer 2 of every level at
+ * cfg->dilation) computes h = dw_h(dw_v(x)), u = pw h + bias, r = relu(u), y = bn_scale r + bn_shift (+ residual); the downs
+ * are dense stride-2 convs at dilation 1.  BatchNorm runs with its running statistics.  The parameters that receive a
+ * gradient are wv, wh, pw, bias, bn_scale, bn_shift of the 11 separable layers and w, bias, bn_scale, bn_shift of the 5
+ * downs.  No d obs is computed.
+ *
+ * occ_sep_encoder_train_forward is occ_encoder_forward (feats are the same to the bit) that keeps, in ws, every layer's
+ * input and relu output r.  The workspace is that of occ_encoder_train_workspace_query, part by part (the same tensors
+ * are kept; h is rebuilt from x in the backward): every part 256-byte aligned, f32, H_0 = S, H' = ceil(H / 2), c = 8 << lv:
+ *   obs (n,4,S,S) | r_init (n,8,S,S) | per level lv = 0..4: a (n,c,H,H) | r1 | b | r2 | cc | rd (n,2c,H',H') |
+ *   pool partials (n, tiles of the last down, 256) | three gradient buffers g0 | g1 | g2 of (n,8,S,S)
+ * 30.31 MiB per env at 256^2, 121.25 MiB per env at 512^2.  18 launches.
+ *
+ * occ_sep_encoder_backward is the backward of the LATEST occ_sep_encoder_train_forward on ws (same cfg, n_env and packed)
+ * for grad_feats = d loss / d feats (n_env,256) f32.  packed and grad_packed use the separable layout of
+ * occ_encoder_packed_floats (separable = 1): per separable layer dwv[ci][3] | dwh[ci][3] | dpw[ci][co] | dbias | dbn_scale
+ * | dbn_shift, per down dw[ci][ky * 3 + kx][co] | dbias | dbn_scale | dbn_shift; grad_packed is OVERWRITTEN, not
+ * accumulated.  The relu gate is the forward's own r > 0.  Within a level the gradient buffers rotate: the down's dY / dU
+ * and then dH = pw^T dU of both layers in one, the dY of Layer 2's output (kept for the residual) in the second, Layer 2's
+ * dU, Layer 1's dY / dU and the block input's gradient in the third.  scratch: device memory of the queried scratch_bytes:
+ * the largest, over the layers, of the activation step's f64 block partials, the partial weight gradients of the K split
+ * (pointwise: at most 1024 blocks per layer) and the f64 block partials of the nine depthwise correlation sums per input
+ * channel.  No floating-point atomics; block partials are added in a fixed order in f64: every gradient is bitwise the same
+ * from call to call.  112 launches on `stream`, nothing allocated or synchronised.  OCC_ERR_ARG before any launch for an
+ * unsupported cfg (separable == 0 included), a null pointer, n_env outside [1, 65535], ws or scratch not 16-byte aligned,
+ * or a short buffer.
+ */
+int occ_sep_encoder_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes);
+int occ_sep_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env, void* ws,
+                                  size_t ws_bytes, float* feats, void* stream);
+int occ_sep_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
+                             const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream);
+
+/*
  * Joint training of the dense encoder, the decoder and the classifier (additive in ABI 12; csrc/occ_fullnet_bwd.hpp): one
  * step of pretrainer.py below its losses, for two upstream gradients at once.  Supported: cfg->separable == 0,
  * cfg->dilation == 1, cfg->residual 0 or 1, cfg->img % 32 == 0 in [32, 1024].  BatchNorm runs with its running statistics

@@ -217,6 +217,12 @@ SYMBOLS = {
                                             C.c_void_p, C.c_void_p]),
     "occ_encoder_backward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "occ_sep_encoder_train_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t),
+                                                       C.POINTER(C.c_size_t)]),
+    "occ_sep_encoder_train_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_size_t, C.c_void_p, C.c_void_p]),
+    "occ_sep_encoder_backward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "occ_fullnet_train_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t),
                                                    C.POINTER(C.c_size_t)]),
     "occ_fullnet_train_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

@@ -62,6 +62,7 @@ namespace occ {
 #include "occ_decoder.hpp"
 #include "occ_decoder_bwd.hpp"
 #include "occ_encoder_bwd.hpp"
+#include "occ_sepenc_bwd.hpp"
 #include "occ_fullnet_bwd.hpp"
 #include "occ_criterion.hpp"
 
@@ -671,6 +672,9 @@ static bool enc_train_cfg_ok(const OccEncoderConfig* c, int n_env) {
     return enc_cfg_ok(c) && c->separable == 0 && c->dilation == 1 && n_env >= 1 && n_env <= 65535;
 }
 static bool full_train_cfg_ok(const OccEncoderConfig* c, int n_env) { return enc_train_cfg_ok(c, n_env) && c->img % 32 == 0; }
+static bool sep_train_cfg_ok(const OccEncoderConfig* c, int n_env) {
+    return enc_cfg_ok(c) && c->separable == 1 && n_env >= 1 && n_env <= 65535;
+}
 
 template <class... P>
 static bool non_null(P... p) {
@@ -739,6 +743,34 @@ extern "C" int occ_encoder_backward(const OccEncoderConfig* cfg, const float* pa
     const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env);
     if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
     enc_backward(cfg->img, cfg->residual != 0, packed, n_env, (char*)ws, grad_feats, (char*)scratch, grad_packed, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- separable encoder training (occ_sepenc_bwd.hpp) -------------------------------------------------------------------
+extern "C" int occ_sep_encoder_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes,
+                                                     size_t* scratch_bytes) {
+    if (!sep_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    return train_sizes(sep_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
+}
+
+extern "C" int occ_sep_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env, void* ws,
+                                             size_t ws_bytes, float* feats, void* stream) {
+    if (!sep_train_cfg_ok(cfg, n_env) || !non_null(packed, obs, ws, feats)) return OCC_ERR_ARG;
+    if (!aligned(16, ws) || !aligned(4, packed, obs, feats)) return OCC_ERR_ARG;
+    if (ws_bytes < sep_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
+    sep_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_sep_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
+                                        const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed,
+                                        void* stream) {
+    if (!sep_train_cfg_ok(cfg, n_env) || !non_null(packed, ws, grad_feats, scratch, grad_packed)) return OCC_ERR_ARG;
+    if (!aligned(16, ws, scratch) || !aligned(4, packed, grad_feats, grad_packed)) return OCC_ERR_ARG;
+    const EncTrainWs l = sep_train_ws_layout(cfg->img, n_env);
+    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
+    sep_backward(cfg->img, cfg->dilation, cfg->residual != 0, packed, n_env, (char*)ws, grad_feats, (char*)scratch, grad_packed,
+                 (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

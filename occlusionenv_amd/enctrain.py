@@ -12,7 +12,8 @@ optimizer works on ``net.parameters()``.
 The parameters sit under the checkpoint's keys, so ``net.state_dict()`` drops back into the checkpoint it came from and
 ``enc.with_encoder(net.state_dict())`` is the trained network for inference.
 
-Limits: dense 3x3 convs only (a separable checkpoint raises) at dilation 1.  Deviation from train_predict.py, which trains
+Limits: dense 3x3 convs only (a separable checkpoint raises) at dilation 1; the separable encoder, at dilation 1 or 2,
+trains through ``septrain.TrainableSeparableEncoder``.  Deviation from train_predict.py, which trains
 in train mode: BatchNorm keeps its running statistics (buffers here); only its affine parameters train.  A training call is
 one chunk (``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of an earlier forward
 raises.  The gradient reaches the encoder through the pooled feature only; where the segmentation loss trains the encoder
@@ -31,23 +32,18 @@ from .nettrain import TrainableNet, align256, encoder_part
 from .nettrain import pack_encoder_buffer, unpack_encoder_buffer  # noqa: F401  (the encoder's packed layout, importable here)
 
 
-class TrainableEncoder(TrainableNet):
-    """The trainable dense encoder (and grad head) of a ``FrozenEncoder``; see the module docstring."""
+class PooledFeatureNet(TrainableNet):
+    """What the encoder-only nets share (``TrainableEncoder`` here, ``septrain.TrainableSeparableEncoder``): one encoder
+    part whose step returns the pooled feature, the grad head in torch, and the view of the kept activations (both native
+    paths keep them in the same workspace layout)."""
 
-    SYMBOLS = ("occ_encoder_train_workspace_query", "occ_encoder_train_forward", "occ_encoder_backward")
     RETURNS = DIFFERENTIABLE = ("feats",)
     RUNS_DECODER = False
 
-    def __init__(self, enc: FrozenEncoder):
-        if not isinstance(enc, FrozenEncoder):
-            raise ValueError("TrainableEncoder needs a FrozenEncoder")
-        if enc.separable:
-            raise ValueError("the native encoder backward covers dense 3x3 convs only: this checkpoint is separable")
-        if enc.dilation != 1:
-            raise ValueError(f"the native encoder backward covers dilation 1 only, this encoder has dilation {enc.dilation}")
+    def __init__(self, enc: FrozenEncoder, part):
         if enc.encoder_state is None:
             raise ValueError("this FrozenEncoder keeps no unfolded encoder tensors (build it with from_state_dict)")
-        super().__init__(enc, [encoder_part(enc.preset)], enc.encoder_state)
+        super().__init__(enc, [part], enc.encoder_state)
         self.stems = self.parts[0].stems
         self.grad_prefix = PRESETS[enc.preset][1]
         self.has_grad_head = self.grad_prefix is not None and self.grad_prefix + "weight" in enc.encoder_state
@@ -89,3 +85,18 @@ class TrainableEncoder(TrainableNet):
             off += 5 * act + align256(4 * n * 2 * c * half * half)
             side = half
         raise ValueError(f"layer {i} outside [0, 16)")
+
+
+class TrainableEncoder(PooledFeatureNet):
+    """The trainable dense encoder (and grad head) of a ``FrozenEncoder``; see the module docstring."""
+
+    SYMBOLS = ("occ_encoder_train_workspace_query", "occ_encoder_train_forward", "occ_encoder_backward")
+
+    def __init__(self, enc: FrozenEncoder):
+        if not isinstance(enc, FrozenEncoder):
+            raise ValueError("TrainableEncoder needs a FrozenEncoder")
+        if enc.separable:
+            raise ValueError("the native encoder backward covers dense 3x3 convs only: this checkpoint is separable")
+        if enc.dilation != 1:
+            raise ValueError(f"the native encoder backward covers dilation 1 only, this encoder has dilation {enc.dilation}")
+        super().__init__(enc, encoder_part(enc.preset))

@@ -156,13 +156,20 @@ def train_predictor(venv, enc_or_net, steps: int, lr: float = 1e-4, weight_decay
     gradient, skips the step if that gradient has a NaN (line 53), normalises it per env as on line 58
     (``g / sqrt(sum g^2 + 1e-7)``) and applies ``F.mse_loss(net.predict_grad(obs), target)``, ``backward`` and one
     ``torch.optim.AdamW`` step (``weight_decay``: torch's default, as in the reference) to the encoder and its head.
-    ``enc_or_net``: an ``enctrain.TrainableEncoder``, or a dense ``FrozenEncoder`` with a grad head (preset "predictor"),
-    from which one is made.  BatchNorm keeps its running statistics (``enctrain``).  Returns ``net``, the per-step ``losses``
+    ``enc_or_net``: an ``enctrain.TrainableEncoder`` or a ``septrain.TrainableSeparableEncoder``, or a ``FrozenEncoder`` with
+    a grad head, from which the one for its form (dense or separable) is made.  BatchNorm keeps its running statistics
+    (``enctrain``).  Returns ``net``, the per-step ``losses``
     of the steps that learned (floats) and ``skipped``, the number of NaN steps; one host sync per step, for the NaN test
     the reference makes there too."""
-    from .enctrain import TrainableEncoder
+    from .enctrain import PooledFeatureNet, TrainableEncoder
+    from .septrain import TrainableSeparableEncoder
 
-    net = enc_or_net if isinstance(enc_or_net, TrainableEncoder) else TrainableEncoder.from_encoder(enc_or_net)
+    if isinstance(enc_or_net, PooledFeatureNet):
+        net = enc_or_net
+    elif getattr(enc_or_net, "separable", False):
+        net = TrainableSeparableEncoder.from_encoder(enc_or_net)
+    else:
+        net = TrainableEncoder.from_encoder(enc_or_net)
     opt = torch.optim.AdamW(net.parameters(), lr=lr, weight_decay=weight_decay)
     losses, skipped = [], 0
     obs = None

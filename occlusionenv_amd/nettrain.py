@@ -1,6 +1,7 @@
-"""The one host path of the three native training wrappers: ``seghead.SegmentationHead`` (decoder and classifier),
-``enctrain.TrainableEncoder`` (dense encoder) and ``fullnet.TrainableFullNetwork`` (both).  Each of them is a
-``TrainableNet`` over one or two ``Part``s, and one ``torch.autograd.Function`` runs all three: forward folds the current
+"""The one host path of the native training wrappers: ``seghead.SegmentationHead`` (decoder and classifier),
+``enctrain.TrainableEncoder`` (dense encoder), ``septrain.TrainableSeparableEncoder`` (separable encoder) and
+``fullnet.TrainableFullNetwork`` (dense encoder and decoder).  Each of them is a ``TrainableNet`` over one or two ``Part``s,
+and one ``torch.autograd.Function`` runs them all: forward folds the current
 BatchNorm parameters on the device in f64, packs every part in the library's layout and runs the native train forward;
 backward runs the native backward and maps each part's packed gradient back to the parameters.
 
@@ -10,7 +11,7 @@ BatchNorm keeps its running statistics (buffers); only its affine parameters tra
 from __future__ import annotations
 
 import ctypes as C
-from typing import Callable, NamedTuple, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -18,7 +19,9 @@ from . import _native as nat
 from .encoder import (BN_EPS, CH, DECODER_KEYS, FEATURES, PRESETS, FrozenEncoder, decoder_packed_floats, decoder_plan, layer_plan,
                       packed_floats)
 
-LEAVES = ("conv.weight", "conv.bias", "bn.weight", "bn.bias")  # the four parameters of a layer, in packed order
+LEAVES = ("conv.weight", "conv.bias", "bn.weight", "bn.bias")  # the four parameters of a dense layer, in packed order
+# those of a separable layer: depthwise (3,1), depthwise (1,3), pointwise, its bias, then the BatchNorm affine
+SEP_LEAVES = ("conv.0.weight", "conv.1.weight", "conv.2.weight", "conv.2.bias", "bn.weight", "bn.bias")
 ENCODER_PERM, DECODER_PERM = (1, 2, 3, 0), (0, 2, 3, 1)  # conv (cout,cin,3,3) / transposed conv (cin,cout,3,3) -> (cin,3,3,cout)
 
 
@@ -78,6 +81,48 @@ def unpack_encoder_buffer(buf: torch.Tensor):
     return unpack_layers(buf, _encoder_plan(), ENCODER_PERM)[0]
 
 
+def _sep_plan():
+    return [(cin, cout, sep) for _stem, cin, cout, sep, _stride in layer_plan(True)]
+
+
+def pack_sep_encoder_buffer(layers) -> torch.Tensor:
+    """layers: sixteen tuples in packed order, a separable layer (wv (cin,1,3,1), wh (cin,1,1,3), pw (cout,cin,1,1), bias,
+    scale, shift), a down (w (cout,cin,3,3), bias, scale, shift) -> the packed f32 buffer of the separable encoder
+    (``encoder.pack_state_dict``): wv[ci][3] | wh[ci][3] | pw[ci][co] | bias | scale | shift per separable layer, the dense
+    layout per down."""
+    parts = []
+    for layer in layers:
+        if len(layer) == 6:
+            wv, wh, pw, b, s, t = layer
+            parts += [wv.reshape(-1), wh.reshape(-1), pw[:, :, 0, 0].t().reshape(-1), b.reshape(-1), s.reshape(-1), t.reshape(-1)]
+        else:
+            parts.append(pack_layers([layer], ENCODER_PERM))
+    buf = torch.cat([p.to(torch.float32) for p in parts])
+    assert buf.numel() == packed_floats(True)
+    return buf
+
+
+def unpack_sep_encoder_buffer(buf: torch.Tensor):
+    """The inverse of ``pack_sep_encoder_buffer`` -> sixteen tuples of views of ``buf`` in the checkpoint's shapes."""
+    if buf.numel() != packed_floats(True):
+        raise ValueError(f"packed separable encoder buffer has {buf.numel()} floats, expected {packed_floats(True)}")
+    layers, off = [], 0
+    for cin, cout, sep in _sep_plan():
+        if sep:
+            wv = buf[off:off + 3 * cin].reshape(cin, 1, 3, 1)
+            wh = buf[off + 3 * cin:off + 6 * cin].reshape(cin, 1, 1, 3)
+            off += 6 * cin
+            pw = buf[off:off + cin * cout].reshape(cin, cout).t().reshape(cout, cin, 1, 1)
+            off += cin * cout
+            layers.append((wv, wh, pw, buf[off:off + cout], buf[off + cout:off + 2 * cout], buf[off + 2 * cout:off + 3 * cout]))
+            off += 3 * cout
+        else:
+            (layer,), used = unpack_layers(buf[off:], [(cin, cout)], ENCODER_PERM)
+            layers.append(layer)
+            off += used
+    return layers
+
+
 def pack_decoder_buffer(levels, cls_w, cls_b) -> torch.Tensor:
     """levels: five (w (2c,c,3,3), bias, scale, shift) -> the packed f32 buffer of the decoder, then cls_w[8] | cls_b
     (``encoder.pack_decoder``)."""
@@ -116,11 +161,15 @@ def register_under_key(module: torch.nn.Module, key: str, t: torch.Tensor, buffe
 
 # ---- a trainable part: where its tensors sit in the checkpoint and how they are packed -------------------------------------
 class Part(NamedTuple):
-    stems: Tuple[str, ...]  # per layer in packed order: stem + LEAVES are its parameters, stem + "bn.running_*" its statistics
+    stems: Tuple[str, ...]  # per layer in packed order: stem + its leaves are its parameters, stem + "bn.running_*" its statistics
     tail: Tuple[str, ...]   # the parameters packed after the layers
     floats: int             # of the packed buffer
-    pack: Callable          # (layers, tail tensors) -> packed buffer
+    pack: Callable          # (layers, tail tensors) -> packed buffer; a layer: (its conv leaves.., scale, shift)
     unpack: Callable        # packed buffer -> (layers, tail tensors)
+    leaves: Optional[Tuple[Tuple[str, ...], ...]] = None  # per layer, ending in bn.weight, bn.bias; None: LEAVES for every layer
+
+    def layer_leaves(self):
+        return self.leaves if self.leaves is not None else (LEAVES,) * len(self.stems)
 
 
 def encoder_part(preset: str) -> Part:
@@ -128,6 +177,15 @@ def encoder_part(preset: str) -> Part:
     stems = tuple(PRESETS[preset][0] + stem for stem, _ci, _co, _sep, _stride in layer_plan(False))
     return Part(stems, (), packed_floats(False), lambda layers, _tail: pack_encoder_buffer(layers),
                 lambda buf: (unpack_encoder_buffer(buf), ()))
+
+
+def sep_encoder_part(preset: str) -> Part:
+    """The 16 layers of the separable encoder under ``PRESETS[preset]``'s prefix: eleven separable layers, five dense downs."""
+    plan = layer_plan(True)
+    stems = tuple(PRESETS[preset][0] + stem for stem, _ci, _co, _sep, _stride in plan)
+    leaves = tuple(SEP_LEAVES if sep else LEAVES for _stem, _ci, _co, sep, _stride in plan)
+    return Part(stems, (), packed_floats(True), lambda layers, _tail: pack_sep_encoder_buffer(layers),
+                lambda buf: (unpack_sep_encoder_buffer(buf), ()), leaves)
 
 
 def decoder_part(preset: str) -> Part:
@@ -176,11 +234,11 @@ class TrainableNet(torch.nn.Module):
         return self.get_buffer(stem + "bn.running_mean"), self.get_buffer(stem + "bn.running_var")
 
     def ordered_parameters(self):
-        """[(key, parameter)] in packed order, part by part: per layer conv.weight, conv.bias, bn.weight, bn.bias, then the
-        part's tail (the classifier's weight, bias).  A grad head is not among them."""
+        """[(key, parameter)] in packed order, part by part: per layer its leaves (dense: conv.weight, conv.bias, bn.weight,
+        bn.bias), then the part's tail (the classifier's weight, bias).  A grad head is not among them."""
         names = []
         for part in self.parts:
-            names += [stem + leaf for stem in part.stems for leaf in LEAVES]
+            names += [stem + leaf for stem, leaves in zip(part.stems, part.layer_leaves()) for leaf in leaves]
             names += part.tail
         return [(k, self.get_parameter(k)) for k in names]
 
@@ -230,11 +288,11 @@ class _NetStep(torch.autograd.Function):
         folded, at = [], 0
         for part in net.parts:
             layers = []
-            for stem in part.stems:
-                w, b, gamma, beta = params[at:at + 4]
+            for stem, leaves in zip(part.stems, part.layer_leaves()):
+                *conv, gamma, beta = params[at:at + len(leaves)]
                 scale, shift, _rstd = fold_bn_vectors(gamma, beta, *net._stats(stem))
-                layers.append((w, b, scale, shift))
-                at += 4
+                layers.append((*conv, scale, shift))
+                at += len(leaves)
             folded.append((layers, params[at:at + len(part.tail)]))
             at += len(part.tail)
         packed = [part.pack(layers, tail).contiguous() for part, (layers, tail) in zip(net.parts, folded)]
@@ -266,8 +324,9 @@ class _NetStep(torch.autograd.Function):
         result = [None, None]
         for part, gp in zip(net.parts, grads_out):
             layers, tail = part.unpack(gp)
-            for stem, (dw, db, dscale, dshift) in zip(part.stems, layers):
+            for stem, (*dconv, dscale, dshift) in zip(part.stems, layers):
                 dgamma, dbeta = bn_param_grads(dscale, dshift, *net._stats(stem))
-                result += [dw.contiguous(), db.clone(), dgamma.to(torch.float32), dbeta.to(torch.float32)]
+                result += [t.clone(memory_format=torch.contiguous_format) for t in dconv]
+                result += [dgamma.to(torch.float32), dbeta.to(torch.float32)]
             result += [t.clone() for t in tail]
         return tuple(result)
