@@ -555,6 +555,41 @@ int occ_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, c
                          float* grad_enc_packed, float* grad_dec_packed, void* stream);
 
 /*
+ * Joint training of the SEPARABLE encoder, the decoder and the classifier (additive in ABI 12; csrc/occ_sepfull_bwd.hpp):
+ * the three entry points above for cfg->separable == 1, the step that pretrains FullNetwork(8, dilation=2, separable=True)
+ * (PPO.py:47; pretrainer.py --separable --dilation 2).  Supported: cfg->separable == 1, cfg->dilation 1 or 2, cfg->residual
+ * 0 or 1, cfg->img % 32 == 0 in [32, 1024], n_env in [1, 65535]; a dense cfg is refused (occ_fullnet_* are for it).  The
+ * arguments are those of the occ_fullnet_* functions with enc_packed / grad_enc_packed in the separable layout of
+ * occ_encoder_packed_floats (separable = 1).  BatchNorm runs with its running statistics in all 21 layers; the parameters
+ * that receive a gradient are those of occ_sep_encoder_backward and of occ_segment_backward.  No d obs is computed.
+ *
+ * occ_sep_fullnet_train_forward runs the encoder ONCE, as occ_sep_encoder_train_forward does, with the last down also
+ * storing its output, then the five up layers on that output and on the level tensors cc (the skips, not copied).  feats is
+ * bitwise what occ_encoder_forward writes, prob (8-byte aligned) what occ_segment_forward writes.  The workspace is that of
+ * occ_fullnet_train_workspace_query, part by part (the separable training workspace is the dense one).  23 launches.
+ *
+ * occ_sep_fullnet_backward is the backward of the LATEST occ_sep_fullnet_train_forward on ws (same cfg, n_env and packed
+ * buffers) for grad_feats (n_env,256) and grad_prob (n_env,1,S,S; 16-byte aligned), both required (zeros for an absent one).
+ * The decoder runs first, then the separable encoder, the deepest level first.  The two passes meet in the encoder's downs,
+ * which are dense in either form, exactly as in occ_fullnet_backward: dskip_lv is added in the epilogue of the level's
+ * stride-2 input gradient (rebuilt from grad_prob and the kept prob at lv = 0) and dlast in the last down's activation
+ * step; no join is a launch of its own, and the decoder's dU sits in g0, which the encoder pass first writes after the
+ * decoder's last launch.  Both gradient buffers are OVERWRITTEN, not accumulated.  scratch: the queried scratch_bytes
+ * (16-byte aligned), the larger of occ_sep_encoder_backward's and occ_segment_backward's.  No floating-point atomics;
+ * block partials are added in a fixed order in f64: every gradient is bitwise the same from call to call,
+ * grad_dec_packed is bitwise what occ_segment_backward gives for the same grad_prob, and with grad_prob = 0
+ * grad_enc_packed equals what occ_sep_encoder_backward gives.  137 launches (decoder 25, encoder 112) on `stream`,
+ * nothing allocated or synchronised.  OCC_ERR_ARG before any launch for an unsupported cfg, a null pointer, n_env outside
+ * [1, 65535], a misaligned or a short buffer.
+ */
+int occ_sep_fullnet_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes);
+int occ_sep_fullnet_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                                  int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, void* stream);
+int occ_sep_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env, void* ws,
+                             size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch, size_t scratch_bytes,
+                             float* grad_enc_packed, float* grad_dec_packed, void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

@@ -64,6 +64,7 @@ namespace occ {
 #include "occ_encoder_bwd.hpp"
 #include "occ_sepenc_bwd.hpp"
 #include "occ_fullnet_bwd.hpp"
+#include "occ_sepfull_bwd.hpp"
 #include "occ_criterion.hpp"
 
 }  // namespace occ
@@ -675,6 +676,7 @@ static bool full_train_cfg_ok(const OccEncoderConfig* c, int n_env) { return enc
 static bool sep_train_cfg_ok(const OccEncoderConfig* c, int n_env) {
     return enc_cfg_ok(c) && c->separable == 1 && n_env >= 1 && n_env <= 65535;
 }
+static bool sep_full_train_cfg_ok(const OccEncoderConfig* c, int n_env) { return sep_train_cfg_ok(c, n_env) && c->img % 32 == 0; }
 
 template <class... P>
 static bool non_null(P... p) {
@@ -802,6 +804,39 @@ extern "C" int occ_fullnet_backward(const OccEncoderConfig* cfg, const float* en
     if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
     full_backward(cfg->img, cfg->residual != 0, enc_packed, dec_packed, n_env, (char*)ws, grad_feats, grad_prob, (char*)scratch,
                   grad_enc_packed, grad_dec_packed, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- joint training of the separable encoder, decoder and classifier (occ_sepfull_bwd.hpp) -----------------------------
+extern "C" int occ_sep_fullnet_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes,
+                                                     size_t* scratch_bytes) {
+    if (!sep_full_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    return train_sizes(sep_full_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
+}
+
+extern "C" int occ_sep_fullnet_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
+                                             const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
+                                             void* stream) {
+    if (!sep_full_train_cfg_ok(cfg, n_env) || !non_null(enc_packed, dec_packed, obs, ws, feats, prob)) return OCC_ERR_ARG;
+    if (!aligned(16, ws) || !aligned(8, prob) || !aligned(4, enc_packed, dec_packed, obs, feats)) return OCC_ERR_ARG;
+    if (ws_bytes < sep_full_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
+    sep_full_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, enc_packed, dec_packed, obs, n_env, (char*)ws, feats, prob,
+                           (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_sep_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env,
+                                        void* ws, size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch,
+                                        size_t scratch_bytes, float* grad_enc_packed, float* grad_dec_packed, void* stream) {
+    if (!sep_full_train_cfg_ok(cfg, n_env) ||
+        !non_null(enc_packed, dec_packed, ws, grad_feats, grad_prob, scratch, grad_enc_packed, grad_dec_packed))
+        return OCC_ERR_ARG;
+    if (!aligned(16, ws, scratch, grad_prob) || !aligned(4, enc_packed, dec_packed, grad_feats, grad_enc_packed, grad_dec_packed))
+        return OCC_ERR_ARG;
+    const FullTrainWs l = sep_full_train_ws_layout(cfg->img, n_env);
+    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
+    sep_full_backward(cfg->img, cfg->dilation, cfg->residual != 0, enc_packed, dec_packed, n_env, (char*)ws, grad_feats, grad_prob,
+                      (char*)scratch, grad_enc_packed, grad_dec_packed, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

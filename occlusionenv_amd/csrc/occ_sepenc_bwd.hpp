@@ -414,8 +414,9 @@ static void sep_launch_train(const float* x, float* y, float* r, const float* re
 }
 
 // The separable encoder on n envs with everything kept: 18 launches.
+// y_last: where the last down also stores its output (n, 256, H_5, H_5), or null.
 static void sep_train_forward(int img, int dil, bool residual, const float* packed, const float* obs, int n, char* ws,
-                              float* feats, hipStream_t st) {
+                              float* feats, hipStream_t st, float* y_last = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n);
     EncLayer L[16];
     sep_train_layers(img, L);
@@ -431,7 +432,7 @@ static void sep_train_forward(int img, int dil, bool residual, const float* pack
         sep_launch_train(F(l.a[lv]), F(l.b[lv]), F(l.r1[lv]), nullptr, packed + Ll[0].woff, Ll[0], dil, n, st);
         sep_launch_train(F(l.b[lv]), F(l.cc[lv]), F(l.r2[lv]), residual ? F(l.a[lv]) : nullptr, packed + Ll[1].woff, Ll[1], dil, n,
                          st);
-        enc_launch_train(F(l.cc[lv]), last ? nullptr : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, packed + Ll[2].woff, Ll[2], n,
+        enc_launch_train(F(l.cc[lv]), last ? y_last : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, packed + Ll[2].woff, Ll[2], n,
                          last ? F(l.part) : nullptr, st);
     }
     const int Hl = L[15].Ho;
@@ -493,9 +494,10 @@ static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* 
 }
 
 // The backward of the latest sep_train_forward on this workspace, the deepest layer first: 112 launches.  grad_packed is
-// overwritten.
+// overwritten.  join (occ_sepfull_bwd.hpp): the decoder's gradients, which meet this pass in the dense downs as they meet
+// enc_backward: dlast in the last down's activation step, skip[lv] in the epilogue of the down's input gradient.
 static void sep_backward(int img, int dil, bool residual, const float* packed, int n, char* ws, const float* grad_feats,
-                         char* scratch, float* grad_packed, hipStream_t st) {
+                         char* scratch, float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n);
     EncLayer L[16];
     sep_train_layers(img, L);
@@ -504,9 +506,9 @@ static void sep_backward(int img, int dil, bool residual, const float* packed, i
     for (int lv = kEncLevels - 1; lv >= 0; --lv) {
         const EncLayer* Ll = L + 1 + 3 * lv;
         const bool last = lv == kEncLevels - 1;
-        enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), last ? nullptr : gA, gA, last ? grad_feats : nullptr,
-                      scratch, st);
-        enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st);
+        enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), last ? (join ? join->dlast : nullptr) : gA, gA,
+                      last ? grad_feats : nullptr, scratch, st);
+        enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st, join ? &join->skip[lv] : nullptr);
         sep_bwd_layer(Ll[1], dil, packed, grad_packed, n, F(l.b[lv]), F(l.r2[lv]), gB, gC, gA, gC, nullptr, scratch, st);
         sep_bwd_layer(Ll[0], dil, packed, grad_packed, n, F(l.a[lv]), F(l.r1[lv]), gC, gC, gA, gC, residual ? gB : nullptr, scratch,
                       st);

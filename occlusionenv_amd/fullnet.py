@@ -25,7 +25,8 @@ kept activations belong to the latest forward: a backward of an earlier forward 
 
 The host path (fold, packed layouts, parameters under the checkpoint's keys, workspace, the autograd function) is
 ``nettrain.TrainableNet``'s on two parts, the encoder's and the decoder's; here are the guards, the native symbols and the
-heads.
+heads.  The heads and ``forward`` are ``JointNet``'s, which ``sepfullnet.TrainableSeparableFullNetwork`` (the separable
+encoder's joint step) shares.
 """
 from __future__ import annotations
 
@@ -35,26 +36,15 @@ from .encoder import DECODER_KEYS, PRESETS, FrozenEncoder
 from .nettrain import TrainableNet, decoder_part, encoder_part
 
 
-class TrainableFullNetwork(TrainableNet):
-    """The trainable encoder, decoder, classifier and grad head of a dense ``FrozenEncoder``; see the module docstring."""
+class JointNet(TrainableNet):
+    """A ``TrainableNet`` over an encoder part and the decoder part whose step returns the pooled feature and the map,
+    both differentiable, with the grad head of the checkpoint in torch on top: what the dense and the separable joint
+    networks share.  A subclass checks its checkpoint and names its encoder part and its native symbols."""
 
-    SYMBOLS = ("occ_fullnet_train_workspace_query", "occ_fullnet_train_forward", "occ_fullnet_backward")
     RETURNS = DIFFERENTIABLE = ("feats", "prob")
 
-    def __init__(self, enc: FrozenEncoder):
-        if not isinstance(enc, FrozenEncoder):
-            raise ValueError("TrainableFullNetwork needs a FrozenEncoder")
-        if enc.preset not in DECODER_KEYS:
-            raise ValueError(f"preset {enc.preset!r} has no segmentation decoder; the presets are {sorted(DECODER_KEYS)}")
-        if enc.separable:
-            raise ValueError("the native joint backward covers dense 3x3 convs only: this checkpoint is separable")
-        if enc.dilation != 1:
-            raise ValueError(f"the native joint backward covers dilation 1 only, this encoder has dilation {enc.dilation}")
-        if not enc.has_decoder or enc.decoder_state is None:
-            raise ValueError("this checkpoint has no segmentation decoder (no 'segmenter.0.features.*' / 'decoder.features.*' keys)")
-        if enc.encoder_state is None:
-            raise ValueError("this FrozenEncoder keeps no unfolded encoder tensors (build it with from_state_dict)")
-        super().__init__(enc, [encoder_part(enc.preset), decoder_part(enc.preset)], {**enc.encoder_state, **enc.decoder_state})
+    def __init__(self, enc: FrozenEncoder, enc_part):
+        super().__init__(enc, [enc_part, decoder_part(enc.preset)], {**enc.encoder_state, **enc.decoder_state})
         self.grad_prefix = PRESETS[enc.preset][1]
         self.has_grad_head = self.grad_prefix is not None and self.grad_prefix + "weight" in enc.encoder_state
 
@@ -73,3 +63,24 @@ class TrainableFullNetwork(TrainableNet):
         grad_pred = torch.nn.functional.linear(feats, self.get_parameter(self.grad_prefix + "weight"),
                                                self.get_parameter(self.grad_prefix + "bias"))
         return feats, prob, grad_pred
+
+
+class TrainableFullNetwork(JointNet):
+    """The trainable encoder, decoder, classifier and grad head of a dense ``FrozenEncoder``; see the module docstring."""
+
+    SYMBOLS = ("occ_fullnet_train_workspace_query", "occ_fullnet_train_forward", "occ_fullnet_backward")
+
+    def __init__(self, enc: FrozenEncoder):
+        if not isinstance(enc, FrozenEncoder):
+            raise ValueError("TrainableFullNetwork needs a FrozenEncoder")
+        if enc.preset not in DECODER_KEYS:
+            raise ValueError(f"preset {enc.preset!r} has no segmentation decoder; the presets are {sorted(DECODER_KEYS)}")
+        if enc.separable:
+            raise ValueError("the native joint backward covers dense 3x3 convs only: this checkpoint is separable")
+        if enc.dilation != 1:
+            raise ValueError(f"the native joint backward covers dilation 1 only, this encoder has dilation {enc.dilation}")
+        if not enc.has_decoder or enc.decoder_state is None:
+            raise ValueError("this checkpoint has no segmentation decoder (no 'segmenter.0.features.*' / 'decoder.features.*' keys)")
+        if enc.encoder_state is None:
+            raise ValueError("this FrozenEncoder keeps no unfolded encoder tensors (build it with from_state_dict)")
+        super().__init__(enc, encoder_part(enc.preset))

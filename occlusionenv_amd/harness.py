@@ -16,7 +16,8 @@
   * ``validate_pretrained`` -- pretrainer.py:162-204 (``val``) itself, on a stored dataset: Loss / Dice / MSE / Accuracy /
     IoU as the means of the per-batch values.
   * ``pretrain_epoch`` -- pretrainer.py:112-159 (``train``) on a stored dataset: the summed segmentation and gradient loss
-    back-propagated through decoder, skips and encoder at once (``fullnet.TrainableFullNetwork``), AdamW.
+    back-propagated through decoder, skips and encoder at once (``fullnet.TrainableFullNetwork``, or
+    ``sepfullnet.TrainableSeparableFullNetwork`` for the separable network the agent runs), AdamW.
 """
 from __future__ import annotations
 
@@ -198,20 +199,28 @@ def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = Fa
                    optimizer=None) -> dict:
     """One epoch of ``PreTrainer.train()`` (pretrainer.py:112-159) on the device: ``batches`` is any iterable of
     ``(img, occlusion, grad, _)`` as for ``validate_pretrained``.  Every batch goes through ``net(img)``
-    (``fullnet.TrainableFullNetwork``: one native forward of encoder, decoder and classifier, the grad head in torch), takes
+    (``fullnet.TrainableFullNetwork`` or ``sepfullnet.TrainableSeparableFullNetwork``: one native forward of encoder, decoder
+    and classifier, the grad head in torch), takes
     ``segmentation.binary_dice_loss`` (``use_dice``) or ``binary_cross_entropy`` of the map plus ``nn.MSELoss()`` or
     ``nn.SmoothL1Loss(beta=0.01)`` (``use_l1``) of the gradient prediction, runs ``backward`` (one native joint backward)
     and one ``torch.optim.AdamW`` step (pretrainer.py:91; ``optimizer``: one to carry over epochs, made here when None).
-    ``net_or_enc``: a ``TrainableFullNetwork``, or a dense "ppo" ``FrozenEncoder`` with decoder and grad head, from which one
-    is made.  BatchNorm keeps its running statistics (``fullnet``).  Returned are ``net``, ``optimizer`` and the five numbers
+    ``net_or_enc``: a ``TrainableFullNetwork`` or a ``TrainableSeparableFullNetwork``, or a "ppo" ``FrozenEncoder`` with decoder
+    and grad head, from which the one for its form (dense or separable) is made.  BatchNorm keeps its running statistics
+    (``fullnet``).  Returned are ``net``, ``optimizer`` and the five numbers
     the reference prints, computed its way: ``loss``, ``segm_loss``, ``grad_loss`` = the mean over batches of the per-batch
     losses, ``accuracy`` and ``iou`` = the mean over batches of the per-batch ratios x 100 of the prediction the step learned
     from (``segmentation.seg_criterion``'s counts); also the pooled ``correct``, ``intersection``, ``union``, ``pixels``
     and ``batches``.  One host sync, at the end."""
     from . import segmentation
-    from .fullnet import TrainableFullNetwork
+    from .fullnet import JointNet, TrainableFullNetwork
+    from .sepfullnet import TrainableSeparableFullNetwork
 
-    net = net_or_enc if isinstance(net_or_enc, TrainableFullNetwork) else TrainableFullNetwork.from_encoder(net_or_enc)
+    if isinstance(net_or_enc, JointNet):
+        net = net_or_enc
+    elif getattr(net_or_enc, "separable", False):
+        net = TrainableSeparableFullNetwork.from_encoder(net_or_enc)
+    else:
+        net = TrainableFullNetwork.from_encoder(net_or_enc)
     if not net.has_grad_head or net.enc.preset != "ppo":
         raise ValueError("pretrain_epoch needs a FullNetwork checkpoint (preset 'ppo') with its gradPredictor head")
     opt = optimizer if optimizer is not None else torch.optim.AdamW(net.parameters(), lr=lr, weight_decay=weight_decay)

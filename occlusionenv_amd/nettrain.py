@@ -1,6 +1,7 @@
 """The one host path of the native training wrappers: ``seghead.SegmentationHead`` (decoder and classifier),
-``enctrain.TrainableEncoder`` (dense encoder), ``septrain.TrainableSeparableEncoder`` (separable encoder) and
-``fullnet.TrainableFullNetwork`` (dense encoder and decoder).  Each of them is a ``TrainableNet`` over one or two ``Part``s,
+``enctrain.TrainableEncoder`` (dense encoder), ``septrain.TrainableSeparableEncoder`` (separable encoder),
+``fullnet.TrainableFullNetwork`` (dense encoder and decoder) and ``sepfullnet.TrainableSeparableFullNetwork`` (separable
+encoder and decoder).  Each of them is a ``TrainableNet`` over one or two ``Part``s,
 and one ``torch.autograd.Function`` runs them all: forward folds the current
 BatchNorm parameters on the device in f64, packs every part in the library's layout and runs the native train forward;
 backward runs the native backward and maps each part's packed gradient back to the parameters.

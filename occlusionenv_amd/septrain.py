@@ -11,8 +11,8 @@ backward ``occ_sep_encoder_backward``.  ``obs`` gets no gradient.  ``net.predict
 dense leaves; ``enc.with_encoder(net.state_dict())`` is the trained network for inference.
 
 Limits: as ``enctrain``'s: BatchNorm keeps its running statistics (buffers here), a training call is one chunk
-(``N <= enc.max_chunk``), and the kept activations belong to the latest forward.  The joint step with the segmentation
-decoder (``fullnet``) covers dense encoders only.
+(``N <= enc.max_chunk``), and the kept activations belong to the latest forward.  The gradient reaches this encoder
+through the pooled feature only; the joint step with the segmentation decoder is ``sepfullnet.TrainableSeparableFullNetwork``.
 """
 from __future__ import annotations
 

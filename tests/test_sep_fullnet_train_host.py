@@ -1,0 +1,270 @@
+"""Host-side checks of the joint training path of the separable network (csrc/occ_sepfull_bwd.hpp,
+occlusionenv_amd/sepfullnet.py): the three entry points are exported and reject what they do not support before anything is
+launched, the workspace query is the restated layout, the two parts' packed layouts round-trip from the whole checkpoint,
+the f64 model of tests/sep_fullnet_train_model.py is the composition of the separable encoder's and the decoder's models,
+the split cases of the GPU test reach what they claim, and every GPU case keeps its gate band small.  No GPU."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from occlusionenv_amd import _native as nat
+from tests import decoder_split_model as dsm
+from tests import fullnet_train_model as ftm
+from tests import segmenter_model
+from tests import sep_encoder_train_model as stm
+from tests import sep_fullnet_train_model as m
+
+SYMBOLS = ("occ_sep_fullnet_train_workspace_query", "occ_sep_fullnet_train_forward", "occ_sep_fullnet_backward")
+P16 = C.c_void_p(4096)  # never dereferenced: every call below is rejected before a launch
+BAND_CAP = 0.005
+
+
+def _cfg(img=64, dilation=2, residual=1, separable=1):
+    cfg = nat.OccEncoderConfig()
+    cfg.img, cfg.dilation, cfg.residual, cfg.separable = img, dilation, residual, separable
+    return cfg
+
+
+def _query(lib, img, n, **kw):
+    ws, sc = C.c_size_t(), C.c_size_t()
+    rc = lib.occ_sep_fullnet_train_workspace_query(C.byref(_cfg(img, **kw)), n, C.byref(ws), C.byref(sc))
+    return rc, int(ws.value), int(sc.value)
+
+
+def test_symbols_declared_exported_and_abi_stays_12():
+    import os
+
+    lib = C.CDLL(nat.LIB_PATH)
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "occlusionenv_amd.h")).read()
+    for name in SYMBOLS:
+        assert hasattr(lib, name) and name in nat.SYMBOLS and f"int {name}(" in header
+    assert nat.load().occ_abi_version() == 12 == nat.ABI_VERSION
+    # the arguments are those of the dense joint entry points
+    for sep, dense in zip(SYMBOLS, ("occ_fullnet_train_workspace_query", "occ_fullnet_train_forward", "occ_fullnet_backward")):
+        assert nat.SYMBOLS[sep] == nat.SYMBOLS[dense]
+
+
+def test_workspace_query_is_the_restated_layout():
+    lib = nat.load()
+    pairs = {(s, n) for _w, _d, _r, s, n in m.CASES} | {(64, 4), (64, 1), (256, 128), (512, 64), (1024, 1)}
+    assert {(32, 2), (64, 3), (96, 2), (64, 130), (96, 65)} <= pairs
+    for img, n in sorted(pairs):
+        for d, residual in ((2, 1), (1, 1), (2, 0)):
+            rc, ws_b, sc_b = _query(lib, img, n, dilation=d, residual=residual)
+            assert rc == 0
+            assert ws_b == m.ws_bytes(img, n) == ftm.ws_bytes(img, n), (img, n)
+            assert sc_b == m.scratch_bytes(img, n), (img, n)
+            assert ws_b % 256 == 0 and sc_b % 256 == 0
+        # the workspace is the dense joint one; the scratch the larger of the two single passes'
+        f_ws, f_sc = C.c_size_t(), C.c_size_t()
+        dense = _cfg(img, dilation=1, separable=0)
+        assert lib.occ_fullnet_train_workspace_query(C.byref(dense), n, C.byref(f_ws), C.byref(f_sc)) == 0
+        assert ws_b == int(f_ws.value)
+        e_ws, e_sc, d_ws, d_sc = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        assert lib.occ_sep_encoder_train_workspace_query(C.byref(_cfg(img)), n, C.byref(e_ws), C.byref(e_sc)) == 0
+        assert lib.occ_segment_train_workspace_query(C.byref(_cfg(img)), n, C.byref(d_ws), C.byref(d_sc)) == 0
+        assert int(e_ws.value) == m.encoder_ws_bytes(img, n)
+        assert sc_b == max(int(e_sc.value), int(d_sc.value))
+        assert ws_b < int(e_ws.value) + int(d_ws.value)  # one encoder pass, 0.94 kept d skip buffers
+
+
+def test_query_rejects_what_is_not_supported():
+    lib = nat.load()
+    assert _query(lib, 64, 2)[0] == 0 and _query(lib, 64, 2, dilation=1, residual=0)[0] == 0 and _query(lib, 32, 1)[0] == 0
+    assert _query(lib, 64, 2, separable=0)[0] == 1 and _query(lib, 64, 2, separable=0, dilation=1)[0] == 1  # dense configs
+    assert _query(lib, 64, 2, separable=2)[0] == 1
+    assert _query(lib, 64, 2, dilation=0)[0] == 1 and _query(lib, 64, 2, dilation=3)[0] == 1
+    assert _query(lib, 64, 2, residual=2)[0] == 1
+    assert _query(lib, 48, 2)[0] == 1  # S % 32
+    assert _query(lib, 16, 2)[0] == 1 and _query(lib, 0, 2)[0] == 1 and _query(lib, 1056, 2)[0] == 1
+    assert _query(lib, 64, 0)[0] == 1 and _query(lib, 64, -1)[0] == 1 and _query(lib, 64, 65536)[0] == 1
+    assert _query(lib, 32, 65535)[0] == 0
+    ws, sc = C.c_size_t(), C.c_size_t()
+    assert lib.occ_sep_fullnet_train_workspace_query(None, 2, C.byref(ws), C.byref(sc)) == 1
+    assert lib.occ_sep_fullnet_train_workspace_query(C.byref(_cfg()), 2, None, C.byref(sc)) == 1
+    assert lib.occ_sep_fullnet_train_workspace_query(C.byref(_cfg()), 2, C.byref(ws), None) == 1
+    # the dense entry points keep refusing this network
+    assert lib.occ_fullnet_train_workspace_query(C.byref(_cfg()), 2, C.byref(ws), C.byref(sc)) == 1
+
+
+def test_argument_checks_need_no_gpu():
+    lib = nat.load()
+    good = _cfg(64)
+    big = 1 << 40
+    _rc, need_ws, need_sc = _query(lib, 64, 2)
+    bad_cfgs = (_cfg(64, separable=0), _cfg(64, separable=0, dilation=1), _cfg(64, dilation=3), _cfg(64, dilation=0), _cfg(48),
+                _cfg(16), _cfg(64, residual=2))
+    # occ_sep_fullnet_train_forward(cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, stream)
+    full = [C.byref(good), P16, P16, P16, 2, P16, big, P16, P16, None]
+    for i in (0, 1, 2, 3, 5, 7, 8):
+        args = list(full)
+        args[i] = None
+        assert lib.occ_sep_fullnet_train_forward(*args) == 1, i
+    for bad in bad_cfgs:
+        assert lib.occ_sep_fullnet_train_forward(C.byref(bad), *full[1:]) == 1
+    for n in (0, 65536):
+        assert lib.occ_sep_fullnet_train_forward(*full[:4], n, *full[5:]) == 1
+    assert lib.occ_sep_fullnet_train_forward(*full[:6], need_ws - 1, *full[7:]) == 1
+    assert lib.occ_sep_fullnet_train_forward(*full[:5], C.c_void_p(4096 + 8), *full[6:]) == 1  # ws not 16-byte aligned
+    assert lib.occ_sep_fullnet_train_forward(*full[:8], C.c_void_p(4096 + 4), None) == 1  # prob not 8-byte aligned
+    # occ_sep_fullnet_backward(cfg, enc_packed, dec_packed, n_env, ws, ws_bytes, grad_feats, grad_prob, scratch,
+    #                          scratch_bytes, grad_enc_packed, grad_dec_packed, stream)
+    full = [C.byref(good), P16, P16, 2, P16, big, P16, P16, P16, big, P16, P16, None]
+    for i in (0, 1, 2, 4, 6, 7, 8, 10, 11):
+        args = list(full)
+        args[i] = None
+        assert lib.occ_sep_fullnet_backward(*args) == 1, i
+    for bad in bad_cfgs:
+        assert lib.occ_sep_fullnet_backward(C.byref(bad), *full[1:]) == 1
+    for n in (0, 65536):
+        assert lib.occ_sep_fullnet_backward(*full[:3], n, *full[4:]) == 1
+    for i, short in ((5, need_ws - 1), (9, need_sc - 1)):
+        args = list(full)
+        args[i] = short
+        assert lib.occ_sep_fullnet_backward(*args) == 1, i
+    for i in (4, 7, 8):  # ws, grad_prob, scratch: 16-byte aligned
+        args = list(full)
+        args[i] = C.c_void_p(4096 + 8)
+        assert lib.occ_sep_fullnet_backward(*args) == 1, i
+
+
+@pytest.mark.parametrize("weights", ["golden", "seeded"])
+def test_pack_round_trips_from_a_whole_checkpoint(weights):
+    """Folding and packing the tensors ``TrainableSeparableFullNetwork`` holds, part by part, gives the buffers
+    ``FrozenEncoder`` packs from the same checkpoint, and unpacking gives the tensors back: bitwise."""
+    from occlusionenv_amd.encoder import DECODER_KEYS, pack_decoder, pack_state_dict
+    from occlusionenv_amd.nettrain import decoder_part, fold_bn_vectors, sep_encoder_part
+
+    sd = m.state_dict(weights)
+    assert set(m.enc_keys() + m.dec_keys() + m.head_keys()) <= set(sd)
+    assert len(m.enc_keys()) == 11 * 6 + 5 * 4 and len(m.dec_keys()) == 22
+    separable, want_enc, _off = pack_state_dict(sd, "encoder.")
+    assert separable
+    want = [want_enc, pack_decoder(sd, *DECODER_KEYS[m.PRESET])]
+    parts = [sep_encoder_part(m.PRESET), decoder_part(m.PRESET)]
+    assert list(parts[0].stems) == ["encoder." + stem for stem, *_ in stm.layers()]
+    for part, buf in zip(parts, want):
+        folded = []
+        for stem, leaves in zip(part.stems, part.layer_leaves()):
+            scale, shift, _ = fold_bn_vectors(sd[stem + "bn.weight"], sd[stem + "bn.bias"], sd[stem + "bn.running_mean"],
+                                              sd[stem + "bn.running_var"])
+            folded.append(tuple(sd[stem + leaf] for leaf in leaves[:-2]) + (scale, shift))
+        tail = tuple(sd[k] for k in part.tail)
+        got = part.pack(folded, tail)
+        assert got.dtype == torch.float32 and got.numel() == part.floats and np.array_equal(got.numpy(), buf)
+        layers, back_tail = part.unpack(got)
+        assert len(layers) == len(folded) and len(back_tail) == len(tail)
+        for b, f in zip(layers, folded):
+            assert len(b) == len(f) and all(x.shape == y.shape and torch.equal(x, y.float()) for x, y in zip(b, f))
+        assert all(torch.equal(x, y) for x, y in zip(back_tail, tail))
+
+
+@pytest.mark.parametrize("weights,dilation,residual", [("golden", 2, 1), ("golden", 1, 1), ("seeded", 2, 0)])
+def test_model_is_the_composition_of_the_two_models(weights, dilation, residual):
+    """Without gates: pooled is sep_encoder_train_model.encode_gated, the map segmenter_model.decode on segmenter_model.
+    encode_full, bitwise; with its own gates it is the same function up to rounding; each upstream gradient alone gives its
+    constituent's gradients, bitwise where the other one is zero."""
+    obs = m.case_obs(32, 2)
+    sd = {k: v.double() for k, v in m.state_dict(weights).items()}
+    p = segmenter_model.PRESETS[m.PRESET]
+    us = []
+    pooled, logit = m.forward_gated(sd, obs, dilation, residual, None, us)
+    assert len(us) == 21 and [u.shape[-1] for u in us[16:]] == [2, 4, 8, 16, 32] and us[15].shape[1:] == (256, 1, 1)
+    assert torch.equal(pooled, stm.encode_gated(sd, obs, p["prefix"], dilation, bool(residual)))
+    ref = segmenter_model.full_forward(sd, obs, m.PRESET, dilation, bool(residual))
+    # encode_full's depthwise pair is F.conv2d, the model's the sliced sums: the same function, not the same rounding
+    assert torch.allclose(logit, ref["logit"], rtol=1e-12, atol=1e-13) and torch.allclose(pooled, ref["pooled"], rtol=1e-12, atol=1e-13)
+    gates = [(u > 0).double() for u in us]
+    pooled_g, logit_g = m.forward_gated(sd, obs, dilation, residual, gates)
+    assert torch.allclose(pooled_g, pooled, rtol=1e-12, atol=1e-14) and torch.allclose(logit_g, logit, rtol=1e-12, atol=1e-14)
+    # alive: every layer has open and closed gates, the map both classes
+    assert all(0.02 < float(g.mean()) < 0.98 for g in gates), [float(g.mean()) for g in gates]
+    assert 0.02 < float((logit > 0).double().mean()) < 0.98
+
+    gen = torch.Generator().manual_seed(44)
+    gf = torch.randn(2, 256, generator=gen, dtype=torch.float64)
+    gp = torch.randn(2, 1, 32, 32, generator=gen, dtype=torch.float64)
+    host = m.HostModel(sd, dilation, residual, obs)
+    # grad_prob = 0: the encoder's gradients are the separable encoder model's, the decoder's exactly zero
+    a = host.grads((host.forward(gates)[0] * gf).sum())
+    enc_host = stm.HostModel(sd, m.PRESET, obs, dilation=dilation, residual=bool(residual))
+    want = enc_host.grads((enc_host.feats(gates[:16]) * gf).sum())
+    assert set(want) == set(m.enc_keys()) and all(torch.equal(a[k], w) for k, w in want.items())
+    assert all(float(a[k].abs().max()) == 0.0 for k in m.dec_keys())
+    # grad_feats = 0: the decoder's gradients are those of the dense joint model's decoder on the same last / skips
+    b = host.grads((host.forward(gates)[1] * gp).sum())
+    assert all(float(b[k].abs().max()) > 0.0 for k in m.enc_keys() + m.dec_keys())
+    dec = {k: sd[k].clone().requires_grad_() for k in m.dec_keys()}
+    with torch.no_grad():
+        x, skips = _last_and_skips(sd, obs, dilation, residual, gates)
+    prob = torch.sigmoid(_decode_gated({**sd, **dec}, x, skips, gates[16:]))
+    (prob * gp).sum().backward()
+    assert all(torch.equal(b[k], dec[k].grad) for k in m.dec_keys())
+    # together: the sum of the two
+    joint = host.grads((host.forward(gates)[0] * gf).sum() + (host.forward(gates)[1] * gp).sum())
+    for k, w in joint.items():
+        assert torch.allclose(a[k] + b[k], w, rtol=1e-11, atol=1e-13 * float(w.abs().max())), k
+
+
+def _last_and_skips(sd, obs, dilation, residual, gates):
+    """The gated separable encoder's last down output and level outputs, read off forward_gated by its own hooks."""
+    us = []
+    m.forward_gated(sd, obs, dilation, residual, gates, us)
+    p = segmenter_model.PRESETS[m.PRESET]["prefix"]
+    skips, x = [], None
+    for i, (stem, *_rest) in enumerate(stm.layers()):
+        y = ftm._bn(us[i] * gates[i], sd, p + stem)
+        if stem.endswith("Layer 2."):
+            skips.append(y + x if residual else y)
+        if stem == "initial." or stem.endswith("down."):
+            x = y  # the block input of the next level; after the last down, the decoder's input
+    return x, skips
+
+
+def _decode_gated(sd, x, skips, gates):
+    """fullnet_train_model.forward_gated's decoder on given inputs."""
+    p = segmenter_model.PRESETS[m.PRESET]
+    for j, y in enumerate(skips[::-1]):
+        st = f"{p['decoder']}{j}.up."
+        u = torch.nn.functional.conv_transpose2d(x, sd[st + "conv.weight"], sd[st + "conv.bias"], stride=2, padding=1, output_padding=1)
+        x = ftm._bn(u * gates[j], sd, st) + y
+    return torch.nn.functional.conv2d(x, sd[p["classifier"] + "weight"], sd[p["classifier"] + "bias"])
+
+
+def test_split_cases_reach_what_they_claim():
+    """From sep_encoder_train_model.dpw_plans and decoder_split_model.dw_plans alone."""
+    assert [(s, n) for _w, _d, _r, s, n in m.SPLIT_CASES] == [(64, 130), (96, 65)]
+    enc = stm.dpw_plans(64, 130)
+    # the initial layer and both layers of levels 0 (16-pixel tiles, 16 per env) and 1 (8-pixel tiles, 16 per env): 3 tiles
+    # per slice, 2080 = 693 x 3 + 1: a last slice of one tile, slices crossing env boundaries
+    for p in enc[:3] + enc[4:6]:
+        assert p["sep"] and p["tiles_env"] == 16 and p["total_tiles"] == 2080 and p["tps"] == 3 and p["slices"] == 694
+        assert p["short_last"] and p["total_tiles"] - 693 * 3 == 1 and p["straddles"]
+    assert [enc[i]["T"] for i in (0, 1, 4)] == [16, 16, 8]
+    assert not enc[3]["sep"] and enc[3]["tps"] == 5 and enc[3]["straddles"]  # the level-0 down
+    # the one-hot envs of the GPU test: the short last slice lies in the last env, and a slice ends in env 1 that began in env 0
+    assert (693 * 3) // 16 == 129 and any((s * 3) // 16 == 0 and (s * 3 + 2) // 16 == 1 for s in range(694))
+    assert any(p["tps"] >= 2 for p in dsm.dw_plans(64, 130))
+    # (96, 65) is the decoder's split shape; the separable layers of levels 3 and 4 straddle envs with a short last slice
+    dec = dsm.dw_plans(96, 65)
+    assert [p["tps"] for p in dec] == [2, 2, 2, 2, 5]
+    assert any(p["short_last"] for p in dec) and sum(p["straddles"] for p in dec) == 3
+    enc = stm.dpw_plans(96, 65)
+    for i in (10, 11, 13, 14):
+        assert enc[i]["sep"] and enc[i]["tps"] >= 2 and enc[i]["straddles"] and enc[i]["short_last"], (i, enc[i])
+    assert ("golden", 2, 1, 96, 65) in m.SPLIT_CASES and ("ppo", 96, 65) in dsm.SPLIT_CASES
+
+
+@pytest.mark.parametrize("weights,dilation,residual,img,n", m.CASES, ids=[f"{w}-d{d}-res{r}-S{s}-N{n}" for w, d, r, s, n in m.CASES])
+def test_gate_band_is_small_in_every_gpu_case(weights, dilation, residual, img, n):
+    """From the f64 model alone: at most 0.5 % of any layer's pixels have |u| <= 1e-4 max(1, max |u|), so that the 1 % cap
+    of the GPU test is met or missed by the kernels and not by the inputs."""
+    sd = {k: v.double() for k, v in m.state_dict(weights).items()}
+    us = []
+    with torch.no_grad():
+        m.forward_gated(sd, m.case_obs(img, n), dilation, residual, None, us)
+    shares = m.band_shares(us)
+    assert len(shares) == 21
+    assert max(shares) <= BAND_CAP, [f"{s:.4f}" for s in shares]
