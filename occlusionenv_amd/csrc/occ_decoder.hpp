@@ -24,6 +24,8 @@
 //                           FUSE = true (the last level, 16 -> 8 at full resolution, bandwidth-bound): the thread holds
 //                           all 8 channels of its quad, so the 1 x 1 classifier and the sigmoid run in the epilogue; the
 //                           (N,8,S,S) decoder feature and the logit are stored only when asked for.
+//                           TRAIN = true (the training forwards, occ_decoder_bwd.hpp) only adds stores to the epilogue: r =
+//                           relu(.) and y always and, FUSE, a kept copy of prob; prob is that of inference to the bit.
 //   occ_seg_metrics_kernel  per env the three integer counts of pretrainer.py:133-139 (agree, intersection, union of the
 //                           two maps thresholded > 0.5): wave reductions, one block sum, then integer atomic adds,
 //                           which commute exactly.
@@ -31,11 +33,14 @@
 // f32 with f32 accumulation in a fixed order, no floating-point atomics: maps are bitwise independent of the batch size and
 // of an env's position in the batch.
 
-template <int T, int COG, bool FUSE>
+// logit: inference: where the logit is stored, or null.  TRAIN: where the kept copy of prob is stored (no logit is).
+// rkeep (TRAIN): (n, cout, 2H, 2H), where r is stored; not read otherwise.
+template <int T, int COG, bool FUSE, bool TRAIN = false>
 __global__ __launch_bounds__(256) void occ_dec_up_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                          const float* __restrict__ skip, const float* __restrict__ w, int cin,
                                                          int cout, int H, int tiles_x, const float* __restrict__ cls,
-                                                         float* __restrict__ prob, float* __restrict__ logit) {
+                                                         float* __restrict__ prob, float* __restrict__ logit,
+                                                         float* __restrict__ rkeep) {
     constexpr int TT = T * T, R = T + 1, RR = R * R;
     __shared__ float s[kEncCC * RR];
     const int tid = threadIdx.x;
@@ -96,14 +101,21 @@ __global__ __launch_bounds__(256) void occ_dec_up_kernel(const float* __restrict
         const int co = co0 + j;
         const float2 s0 = *reinterpret_cast<const float2*>(skip + ebase + co * oplane + off);
         const float2 s1 = *reinterpret_cast<const float2*>(skip + ebase + co * oplane + off + W2);
-        float v[4];
+        float r[4], v[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = fmaf(fmaxf(acc[q][j] + bias[co], 0.f), bns[co], bnt[co]);
+        for (int q = 0; q < 4; ++q) {
+            r[q] = fmaxf(acc[q][j] + bias[co], 0.f);
+            v[q] = fmaf(r[q], bns[co], bnt[co]);
+        }
         v[0] += s0.x;
         v[1] += s0.y;
         v[2] += s1.x;
         v[3] += s1.y;
-        if (!FUSE || y) {
+        if constexpr (TRAIN) {
+            *reinterpret_cast<float2*>(rkeep + ebase + co * oplane + off) = make_float2(r[0], r[1]);
+            *reinterpret_cast<float2*>(rkeep + ebase + co * oplane + off + W2) = make_float2(r[2], r[3]);
+        }
+        if (TRAIN || !FUSE || y) {
             *reinterpret_cast<float2*>(y + ebase + co * oplane + off) = make_float2(v[0], v[1]);
             *reinterpret_cast<float2*>(y + ebase + co * oplane + off + W2) = make_float2(v[2], v[3]);
         }
@@ -123,7 +135,10 @@ __global__ __launch_bounds__(256) void occ_dec_up_kernel(const float* __restrict
         const size_t o = (size_t)blockIdx.z * oplane + off;
         *reinterpret_cast<float2*>(prob + o) = make_float2(pr[0], pr[1]);
         *reinterpret_cast<float2*>(prob + o + W2) = make_float2(pr[2], pr[3]);
-        if (logit) {
+        if constexpr (TRAIN) {
+            *reinterpret_cast<float2*>(logit + o) = make_float2(pr[0], pr[1]);
+            *reinterpret_cast<float2*>(logit + o + W2) = make_float2(pr[2], pr[3]);
+        } else if (logit) {
             *reinterpret_cast<float2*>(logit + o) = make_float2(z[0], z[1]);
             *reinterpret_cast<float2*>(logit + o + W2) = make_float2(z[2], z[3]);
         }
@@ -204,20 +219,27 @@ inline SegWs seg_ws_layout(int img, int n) {
     return l;
 }
 
-static void dec_launch_up(const float* x, float* y, const float* skip, const float* w, int cin, int cout, int H, int n,
-                          const float* cls, float* prob, float* logit, hipStream_t st) {
+// cls = null: a level below the last; prob and logit are not used.  rkeep = null: inference.  rkeep given (the training
+// forwards, occ_decoder_bwd.hpp): the TRAIN instantiation on the same grid; `logit` is then where the kept prob goes.
+template <bool TRAIN>
+static void dec_launch_up_t(const float* x, float* y, const float* skip, const float* w, int cin, int cout, int H, int n,
+                            const float* cls, float* prob, float* logit, hipStream_t st, float* rkeep) {
     constexpr int COG = 16;  // 64 accumulators per thread; cout = 128, 64, 32, 16 below the last level
     const int T = enc_tile(H);
     const TileLaunch l = tile_launch(T, H, cls ? 1 : cout / COG, n);
-    if (cls)  // the last level: cout = 8, H = S / 2 >= 16
-        hipLaunchKernelGGL((occ_dec_up_kernel<16, 8, true>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, cls, prob,
-                           logit);
-    else if (T == 16)
-        hipLaunchKernelGGL((occ_dec_up_kernel<16, COG, false>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, nullptr,
-                           nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((occ_dec_up_kernel<8, COG, false>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, nullptr,
-                           nullptr, nullptr);
+#define OCC_DEC_UP(TT, CG, FUSE)                                                                                               \
+    hipLaunchKernelGGL((occ_dec_up_kernel<TT, CG, FUSE, TRAIN>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, cls, \
+                       prob, logit, rkeep)
+    if (cls) OCC_DEC_UP(16, 8, true);  // the last level: cout = 8, H = S / 2 >= 16
+    else if (T == 16) OCC_DEC_UP(16, COG, false);
+    else OCC_DEC_UP(8, COG, false);
+#undef OCC_DEC_UP
+}
+
+static void dec_launch_up(const float* x, float* y, const float* skip, const float* w, int cin, int cout, int H, int n,
+                          const float* cls, float* prob, float* logit, hipStream_t st, float* rkeep = nullptr) {
+    if (rkeep) dec_launch_up_t<true>(x, y, skip, w, cin, cout, H, n, cls, prob, logit, st, rkeep);
+    else dec_launch_up_t<false>(x, y, skip, w, cin, cout, H, n, cls, prob, logit, st, nullptr);
 }
 
 // Encoder (17 launches, keeping the skips) + decoder (5 launches): 22 launches.  img % 32 == 0.

@@ -1,13 +1,13 @@
 // occ_decoder_bwd.hpp -- training of the segmentation decoder and classifier with the encoder frozen: a forward that keeps
 // what the backward needs, and the backward with respect to every decoder parameter.  Part of the single translation unit
-// occ_kernels.hip (included inside namespace occ, after occ_decoder.hpp, whose quad mapping, LDS staging and packed layout
-// it mirrors, and after occ_criterion.hpp's reduction rule, which it follows).
+// occ_kernels.hip (included inside namespace occ, after occ_decoder.hpp, whose forward kernel it launches and whose quad
+// mapping, LDS staging and packed layout its backward mirrors, and after occ_criterion.hpp's reduction rule, which it follows).
 //
 // Forward per level j (c = 128 .. 8): u = convT(x_j) + b, r = relu(u), y_j = s r + t + skip, x_{j+1} = y_j; after the last
 // level z = cls_w y_4 + cls_b, p = sigmoid(z).  BatchNorm runs with its running statistics (s, t folded by the host).
 //
-//   occ_dec_up_train_kernel     occ_dec_up_kernel with the same FMA order (prob and the pooled feature are the same to
-//                               the bit), which also stores r_j and, at the last level, y_4 and a second copy of p.
+//   occ_dec_up_kernel<.., TRAIN>  (occ_decoder.hpp) the inference kernel itself, one loop nest for both (prob is the same
+//                               to the bit), whose epilogue also stores r_j and, at the last level, y_4 and a second copy of p.
 //   occ_dec_bwd_act_kernel      per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0] written over dY (to a buffer of its
 //                               own in the joint training of occ_fullnet_bwd.hpp, which reads dY again), with dY = dz
 //                               cls_w[c], dz = g p (1 - p) at the last level; f64 block partials of dS = sum dY r, dT = sum
@@ -41,106 +41,6 @@ constexpr int kBwdChunk = 4096;   // pixels of one (env, channel) plane per bloc
 constexpr int kBwdDxCC = 8;       // output channels of dU staged per step of the input gradient
 constexpr int kBwdDxCIG = 16;     // input channels per thread of the input gradient
 constexpr int kBwdDwBlocks = 512;  // blocks of the weight gradient per level (K slices x (ci, co) tiles)
-
-template <int T, int COG, bool FUSE>
-__global__ __launch_bounds__(256) void occ_dec_up_train_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                               float* __restrict__ rkeep, const float* __restrict__ skip,
-                                                               const float* __restrict__ w, int cin, int cout, int H,
-                                                               int tiles_x, const float* __restrict__ cls,
-                                                               float* __restrict__ prob, float* __restrict__ pkeep) {
-    constexpr int TT = T * T, R = T + 1, RR = R * R;
-    __shared__ float s[kEncCC * RR];
-    const int tid = threadIdx.x;
-    const int p = tid % TT;
-    const int ng = blockDim.x / TT;
-    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
-    const int co0 = (blockIdx.y * ng + g) * COG;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int iy0 = ty * T, ix0 = tx * T;
-    const int py = p / T, px = p % T;
-    const size_t plane = (size_t)H * H;
-    const float* xe = x + (size_t)blockIdx.z * cin * plane;
-    const float* bias = w + (size_t)cin * 9 * cout;
-    const float* bns = bias + cout;
-    const float* bnt = bns + cout;
-
-    float acc[4][COG];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int j = 0; j < COG; ++j) acc[q][j] = 0.f;
-
-    for (int ci0 = 0; ci0 < cin; ci0 += kEncCC) {
-        const int cc = min(kEncCC, cin - ci0);
-        __syncthreads();
-        for (int i = tid; i < cc * RR; i += blockDim.x) {
-            const int c = i / RR, r = i - c * RR;
-            const int ry = r / R, rx = r - ry * R;
-            const int gy = iy0 + ry, gx = ix0 + rx;
-            float v = 0.f;
-            if (gy < H && gx < H) v = xe[(ci0 + c) * plane + (size_t)gy * H + gx];
-            s[i] = v;
-        }
-        __syncthreads();
-        for (int c = 0; c < cc; ++c) {
-            const float* sc = s + c * RR + py * R + px;
-            const float a = sc[0], b = sc[1], cv = sc[R], dv = sc[R + 1];
-            const float* wr = w + (size_t)(ci0 + c) * 9 * cout + co0;  // w[ci][ky * 3 + kx][co]
-#pragma unroll
-            for (int j = 0; j < COG; ++j) {  // the FMA order of occ_dec_up_kernel
-                acc[0][j] = fmaf(wr[4 * cout + j], a, acc[0][j]);
-                acc[1][j] = fmaf(wr[3 * cout + j], b, fmaf(wr[5 * cout + j], a, acc[1][j]));
-                acc[2][j] = fmaf(wr[1 * cout + j], cv, fmaf(wr[7 * cout + j], a, acc[2][j]));
-                acc[3][j] = fmaf(wr[0 * cout + j], dv,
-                                 fmaf(wr[2 * cout + j], cv, fmaf(wr[6 * cout + j], b, fmaf(wr[8 * cout + j], a, acc[3][j]))));
-            }
-        }
-    }
-    const int iy = iy0 + py, ix = ix0 + px;
-    if (iy >= H || ix >= H) return;
-    const int W2 = 2 * H;
-    const size_t oplane = 4 * plane;
-    const size_t off = (size_t)(2 * iy) * W2 + 2 * ix;
-    const size_t ebase = (size_t)blockIdx.z * cout * oplane;
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < COG; ++j) {
-        const int co = co0 + j;
-        const float2 s0 = *reinterpret_cast<const float2*>(skip + ebase + co * oplane + off);
-        const float2 s1 = *reinterpret_cast<const float2*>(skip + ebase + co * oplane + off + W2);
-        float r[4], v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            r[q] = fmaxf(acc[q][j] + bias[co], 0.f);
-            v[q] = fmaf(r[q], bns[co], bnt[co]);
-        }
-        v[0] += s0.x;
-        v[1] += s0.y;
-        v[2] += s1.x;
-        v[3] += s1.y;
-        *reinterpret_cast<float2*>(rkeep + ebase + co * oplane + off) = make_float2(r[0], r[1]);
-        *reinterpret_cast<float2*>(rkeep + ebase + co * oplane + off + W2) = make_float2(r[2], r[3]);
-        *reinterpret_cast<float2*>(y + ebase + co * oplane + off) = make_float2(v[0], v[1]);
-        *reinterpret_cast<float2*>(y + ebase + co * oplane + off + W2) = make_float2(v[2], v[3]);
-        if constexpr (FUSE) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) z[q] = fmaf(cls[j], v[q], z[q]);
-        }
-    }
-    if constexpr (FUSE) {
-        float pr[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            z[q] += cls[COG];
-            pr[q] = 1.f / (1.f + expf(-z[q]));
-        }
-        const size_t o = (size_t)blockIdx.z * oplane + off;
-        *reinterpret_cast<float2*>(prob + o) = make_float2(pr[0], pr[1]);
-        *reinterpret_cast<float2*>(prob + o + W2) = make_float2(pr[2], pr[3]);
-        *reinterpret_cast<float2*>(pkeep + o) = make_float2(pr[0], pr[1]);
-        *reinterpret_cast<float2*>(pkeep + o + W2) = make_float2(pr[2], pr[3]);
-    }
-}
 
 // Activation step of one level.  dy: (n, c, plane) (not read when LAST); du: (n, c, plane), may be dy itself (the decoder
 // alone; the joint training of occ_fullnet_bwd.hpp keeps dY, the level's d skip).  r: the forward's relu(u).
@@ -477,22 +377,6 @@ inline TrainPtrs train_ptrs(const TrainWs& l, char* ws) {
     return t;
 }
 
-static void dec_launch_up_train(const float* x, float* y, float* r, const float* skip, const float* w, int cin, int cout, int H,
-                                int n, const float* cls, float* prob, float* pkeep, hipStream_t st) {
-    constexpr int COG = 16;
-    const int T = enc_tile(H);
-    const TileLaunch l = tile_launch(T, H, cls ? 1 : cout / COG, n);  // the grids of dec_launch_up
-    if (cls)
-        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, 8, true>), l.grid, l.block, 0, st, x, y, r, skip, w, cin, cout, H, l.tiles_x,
-                           cls, prob, pkeep);
-    else if (T == 16)
-        hipLaunchKernelGGL((occ_dec_up_train_kernel<16, COG, false>), l.grid, l.block, 0, st, x, y, r, skip, w, cin, cout, H, l.tiles_x,
-                           nullptr, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((occ_dec_up_train_kernel<8, COG, false>), l.grid, l.block, 0, st, x, y, r, skip, w, cin, cout, H, l.tiles_x,
-                           nullptr, nullptr, nullptr);
-}
-
 // The five up levels on t.last and t.skip, keeping y_j, r_j and p: 5 launches.
 static void dec_train_forward(int img, const float* dec_packed, int n, const TrainPtrs& t, float* prob, hipStream_t st) {
     const float* w = dec_packed;
@@ -503,7 +387,7 @@ static void dec_train_forward(int img, const float* dec_packed, int n, const Tra
         const int lv = kEncLevels - 1 - j;
         const int c = kEncCh << lv;
         const bool last = j == kEncLevels - 1;
-        dec_launch_up_train(x, t.y[j], t.r[j], t.skip[lv], w, 2 * c, c, H, n, last ? cls : nullptr, prob, t.p, st);
+        dec_launch_up(x, t.y[j], t.skip[lv], w, 2 * c, c, H, n, last ? cls : nullptr, prob, t.p, st, t.r[j]);
         w += 9LL * 2 * c * c + 3LL * c;
         x = t.y[j];
         H *= 2;

@@ -10,17 +10,20 @@
 //   occ_enc_sep_kernel    one separable Conv: depthwise (3,1) with dilation (d,1), depthwise (1,3) with dilation (1,d),
 //                         pointwise + bias, ReLU, BN affine, + residual.  The input tile and its dilation halo are staged
 //                         in LDS (8 channels at a time); each thread forms both depthwise results of its pixel in
-//                         registers, so neither depthwise intermediate exists outside the thread.
+//                         registers, so neither depthwise intermediate exists outside the thread.  TRAIN = true (the
+//                         training forwards, occ_encoder_bwd.hpp) also stores r = relu(.), which the backward reads.
 //   occ_enc_dense_kernel  dense 3x3 Conv, stride 1 or 2, dilation 1 or 2, + bias, ReLU, BN affine (+ residual): the
 //                         down convs and the dense layers of the "predictor" preset.  POOL = true (the last down): the
 //                         output is not stored; each block writes the per-channel sum over its tile's pixels (a fixed
 //                         sequential order) to a partials row instead.  KEEP = true (occ_segment_forward) stores the
-//                         output as well, from the same registers: the partials do not change by a bit.
+//                         output as well, from the same registers: the partials do not change by a bit.  TRAIN = true
+//                         also stores r and, POOL, the output where the caller gives a place for it.
 //   occ_enc_pool_kernel   per (env, channel) one fixed-order sum of the tile partials / (Ho * Wo).
 //
 // A thread owns one output pixel and COG output channels; a block is a T x T pixel tile times NG channel groups (one
 // wave-uniform group per wave when T = 8).  Nothing depends on the batch size or on an env's position in the batch, and
-// there are no atomics: features are bitwise reproducible.
+// there are no atomics: features are bitwise reproducible.  TRAIN only adds stores to the epilogue: the training forwards
+// run these very loop nests, so their features are those of inference to the bit.
 
 constexpr int kEncCh = 8;       // channels after the initial layer
 constexpr int kEncLevels = 5;   // ConvBlocks
@@ -32,10 +35,12 @@ constexpr int kEncMaxR = 35;    // staged rows / columns: (16 - 1) * stride 2 + 
 constexpr int kEncLds = kEncCC * kEncMaxR * kEncMaxR;
 constexpr int kEncSepLds = kEncCC * 20 * 20;
 
-template <int T, int COG>
+// rkeep (TRAIN): (n, cout, H, W), where r is stored; not read otherwise.
+template <int T, int COG, bool TRAIN = false>
 __global__ __launch_bounds__(256) void occ_enc_sep_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                           const float* __restrict__ resid, const float* __restrict__ w,
-                                                          int cin, int cout, int H, int W, int d, int tiles_x) {
+                                                          int cin, int cout, int H, int W, int d, int tiles_x,
+                                                          float* __restrict__ rkeep) {
     __shared__ float s[kEncSepLds];
     constexpr int TT = T * T;
     const int tid = threadIdx.x;
@@ -95,21 +100,25 @@ __global__ __launch_bounds__(256) void occ_enc_sep_kernel(const float* __restric
     if (oy >= H || ox >= W) return;
     float* ye = y + (size_t)blockIdx.z * cout * plane + (size_t)oy * W + ox;
     const float* re = resid ? resid + (size_t)blockIdx.z * cout * plane + (size_t)oy * W + ox : nullptr;
+    float* rk = TRAIN ? rkeep + (size_t)blockIdx.z * cout * plane + (size_t)oy * W + ox : nullptr;
 #pragma unroll
     for (int j = 0; j < COG; ++j) {
         const int co = co0 + j;
-        float v = fmaxf(acc[j] + bias[co], 0.f);
-        v = fmaf(v, bns[co], bnt[co]);
+        const float r = fmaxf(acc[j] + bias[co], 0.f);
+        float v = fmaf(r, bns[co], bnt[co]);
         if (re) v += re[co * plane];
+        if constexpr (TRAIN) rk[co * plane] = r;
         ye[co * plane] = v;
     }
 }
 
-template <int T, int COG, bool POOL, bool KEEP = false>
+// rkeep (TRAIN): (n, cout, Ho, Wo), where r is stored; not read otherwise.  TRAIN && POOL: y may be null (no output kept).
+template <int T, int COG, bool POOL, bool KEEP = false, bool TRAIN = false>
 __global__ __launch_bounds__(256) void occ_enc_dense_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                             const float* __restrict__ resid, const float* __restrict__ w,
                                                             int cin, int cout, int H, int W, int Ho, int Wo, int stride,
-                                                            int d, int tiles_x, float* __restrict__ partials) {
+                                                            int d, int tiles_x, float* __restrict__ partials,
+                                                            float* __restrict__ rkeep) {
     __shared__ float s[kEncLds];
     constexpr int TT = T * T;
     const int tid = threadIdx.x;
@@ -167,12 +176,14 @@ __global__ __launch_bounds__(256) void occ_enc_dense_kernel(const float* __restr
         if (!valid) return;
         float* ye = y + (size_t)blockIdx.z * cout * oplane + (size_t)oy * Wo + ox;
         const float* re = resid ? resid + (size_t)blockIdx.z * cout * oplane + (size_t)oy * Wo + ox : nullptr;
+        float* rk = TRAIN ? rkeep + (size_t)blockIdx.z * cout * oplane + (size_t)oy * Wo + ox : nullptr;
 #pragma unroll
         for (int j = 0; j < COG; ++j) {
             const int co = co0 + j;
-            float v = fmaxf(acc[j] + bias[co], 0.f);
-            v = fmaf(v, bns[co], bnt[co]);
+            const float r = fmaxf(acc[j] + bias[co], 0.f);
+            float v = fmaf(r, bns[co], bnt[co]);
             if (re) v += re[co * oplane];
+            if constexpr (TRAIN) rk[co * oplane] = r;
             ye[co * oplane] = v;
         }
     } else {
@@ -183,11 +194,18 @@ __global__ __launch_bounds__(256) void occ_enc_dense_kernel(const float* __restr
 #pragma unroll
         for (int j = 0; j < COG; ++j) {
             const int co = co0 + j;
-            float v = fmaxf(acc[j] + bias[co], 0.f);
-            v = fmaf(v, bns[co], bnt[co]);
+            const float r = fmaxf(acc[j] + bias[co], 0.f);
+            const float v = fmaf(r, bns[co], bnt[co]);
             s[(g * COG + j) * TT + p] = valid ? v : 0.f;
             if constexpr (KEEP) {
                 if (valid) y[((size_t)blockIdx.z * cout + co) * oplane + (size_t)oy * Wo + ox] = v;
+            }
+            if constexpr (TRAIN) {
+                if (valid) {
+                    const size_t o = ((size_t)blockIdx.z * cout + co) * oplane + (size_t)oy * Wo + ox;
+                    rkeep[o] = r;
+                    if (y) y[o] = v;  // the joint training's decoder reads the last down's output
+                }
             }
         }
         __syncthreads();
@@ -265,55 +283,59 @@ inline void enc_ws_layout(int img, int n, size_t* buf_bytes, size_t* part_bytes)
     *part_bytes = enc_align((size_t)n * enc_tiles(h) * kEncFeat * sizeof(float));
 }
 
-template <int T>
+// The launchers of one layer.  rkeep = null: inference.  rkeep given (the training forwards, occ_encoder_bwd.hpp): the TRAIN
+// instantiation on the same grid, which also stores r there.
+template <int T, bool TRAIN>
 static void enc_launch_sep_t(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int d,
-                             int n, hipStream_t st) {
+                             int n, hipStream_t st, float* rkeep) {
     const int cog = enc_cog(cout), ng = enc_groups(T, cout);
     const int tiles_x = (H + T - 1) / T;
     const dim3 grid(tiles_x * tiles_x, cout / (cog * ng), n), block(T * T * ng);
-    switch (cog) {
-        case 8: hipLaunchKernelGGL((occ_enc_sep_kernel<T, 8>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, d, tiles_x); break;
-        case 16: hipLaunchKernelGGL((occ_enc_sep_kernel<T, 16>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, d, tiles_x); break;
-        default: hipLaunchKernelGGL((occ_enc_sep_kernel<T, 32>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, d, tiles_x); break;
-    }
+#define OCC_ENC_SEP(COG) \
+    hipLaunchKernelGGL((occ_enc_sep_kernel<T, COG, TRAIN>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, d, tiles_x, rkeep)
+    if (cog == 8) OCC_ENC_SEP(8);
+    else if (cog == 16) OCC_ENC_SEP(16);
+    else OCC_ENC_SEP(32);
+#undef OCC_ENC_SEP
 }
 
 static void enc_launch_sep(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int d, int n,
-                           hipStream_t st) {
-    if (enc_tile(H) == 16) enc_launch_sep_t<16>(x, y, resid, w, cin, cout, H, d, n, st);
-    else enc_launch_sep_t<8>(x, y, resid, w, cin, cout, H, d, n, st);
+                           hipStream_t st, float* rkeep = nullptr) {
+    const bool t16 = enc_tile(H) == 16;
+    if (rkeep) t16 ? enc_launch_sep_t<16, true>(x, y, resid, w, cin, cout, H, d, n, st, rkeep)
+                   : enc_launch_sep_t<8, true>(x, y, resid, w, cin, cout, H, d, n, st, rkeep);
+    else t16 ? enc_launch_sep_t<16, false>(x, y, resid, w, cin, cout, H, d, n, st, nullptr)
+             : enc_launch_sep_t<8, false>(x, y, resid, w, cin, cout, H, d, n, st, nullptr);
 }
 
-template <int T>
+// keep (inference, with partials): the last down also stores its output.  With rkeep it does so where y is not null.
+template <int T, bool TRAIN>
 static void enc_launch_dense_t(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int stride,
-                               int d, int n, float* partials, bool keep, hipStream_t st) {
+                               int d, int n, float* partials, bool keep, hipStream_t st, float* rkeep) {
     const int Ho = enc_out_size(H, stride);
     const int cog = enc_cog(cout), ng = enc_groups(T, cout);
     const int tiles_x = (Ho + T - 1) / T;
     const dim3 grid(tiles_x * tiles_x, cout / (cog * ng), n), block(T * T * ng);
+#define OCC_ENC_DENSE(COG, POOL, KEEP)                                                                                          \
+    hipLaunchKernelGGL((occ_enc_dense_kernel<T, COG, POOL, KEEP, TRAIN>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho, \
+                       stride, d, tiles_x, partials, rkeep)
     if (partials) {  // the last down: cout = 256
-        if (keep)
-            hipLaunchKernelGGL((occ_enc_dense_kernel<T, 32, true, true>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho,
-                               stride, d, tiles_x, partials);
-        else
-            hipLaunchKernelGGL((occ_enc_dense_kernel<T, 32, true>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho,
-                               stride, d, tiles_x, partials);
-        return;
-    }
-    switch (cog) {
-        case 8: hipLaunchKernelGGL((occ_enc_dense_kernel<T, 8, false>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho,
-                                   stride, d, tiles_x, partials); break;
-        case 16: hipLaunchKernelGGL((occ_enc_dense_kernel<T, 16, false>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho,
-                                    Ho, stride, d, tiles_x, partials); break;
-        default: hipLaunchKernelGGL((occ_enc_dense_kernel<T, 32, false>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho,
-                                    Ho, stride, d, tiles_x, partials); break;
-    }
+        if constexpr (TRAIN) OCC_ENC_DENSE(32, true, false);
+        else if (keep) OCC_ENC_DENSE(32, true, true);
+        else OCC_ENC_DENSE(32, true, false);
+    } else if (cog == 8) OCC_ENC_DENSE(8, false, false);
+    else if (cog == 16) OCC_ENC_DENSE(16, false, false);
+    else OCC_ENC_DENSE(32, false, false);
+#undef OCC_ENC_DENSE
 }
 
 static void enc_launch_dense(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int stride,
-                             int d, int n, float* partials, hipStream_t st, bool keep = false) {
-    if (enc_tile(enc_out_size(H, stride)) == 16) enc_launch_dense_t<16>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st);
-    else enc_launch_dense_t<8>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st);
+                             int d, int n, float* partials, hipStream_t st, bool keep = false, float* rkeep = nullptr) {
+    const bool t16 = enc_tile(enc_out_size(H, stride)) == 16;
+    if (rkeep) t16 ? enc_launch_dense_t<16, true>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, rkeep)
+                   : enc_launch_dense_t<8, true>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, rkeep);
+    else t16 ? enc_launch_dense_t<16, false>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, nullptr)
+             : enc_launch_dense_t<8, false>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, nullptr);
 }
 
 // The whole encoder on n envs: 17 launches (the initial layer, two layers and a down per level, the pool).

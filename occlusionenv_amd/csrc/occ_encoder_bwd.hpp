@@ -1,16 +1,19 @@
 // occ_encoder_bwd.hpp -- training of the dense (non-separable, dilation 1) encoder through its pooled 256-d feature: a
 // forward that keeps what the backward needs, and the backward with respect to every encoder parameter.  Part of the
-// single translation unit occ_kernels.hip (included inside namespace occ, after occ_encoder.hpp, whose tiling and packed
-// layout it mirrors, and after occ_decoder_bwd.hpp, whose reduction rule and two of whose kernels it reuses).
+// single translation unit occ_kernels.hip (included inside namespace occ, after occ_encoder.hpp, whose forward kernels it
+// launches and whose tiling and packed layout its backward mirrors, and after occ_decoder_bwd.hpp, whose reduction rule and
+// two of whose kernels it reuses).  The training forward walk (enc_train_forward) and the layer table (enc_train_layers)
+// here also serve the separable encoder (occ_sepenc_bwd.hpp).
 //
 // Forward per layer (16 of them: initial, then Layer 1, Layer 2, down per level): u = conv(x) + b, r = relu(u),
 // y = s r + t (+ the block input, Layer 2 of a residual block); feats = mean of the last down's y.  BatchNorm runs with
 // its running statistics (s, t folded by the host).  No d obs is computed.
 //
 //   occ_enc_copy_kernel           obs -> ws (the backward has no obs argument; the initial layer's dW reads the copy).
-//   occ_enc_dense_train_kernel    occ_enc_dense_kernel at dilation 1 with the same FMA order (feats are the same to the
-//                                 bit) which also stores r; POOL (the last down) stores r and the pool partials, and y
-//                                 only for the joint training (occ_fullnet_bwd.hpp), whose decoder reads it.
+//   occ_enc_dense_kernel<.., TRAIN>  (occ_encoder.hpp) the inference kernel itself at dilation 1, one loop nest for both
+//                                 (feats are the same to the bit), whose epilogue also stores r; POOL (the last down)
+//                                 stores r and the pool partials, and y only for the joint training (occ_fullnet_bwd.hpp),
+//                                 whose decoder reads it.
 //   occ_enc_bwd_act_kernel        per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0], written to a buffer of its
 //                                 own (the dY of a residual block's Layer 2 is needed again); POOL: dY = grad_feats[n][c] /
 //                                 (H H), never stored.  f64 block partials of dS = sum dY r, dT = sum dY, dB = sum dU in
@@ -53,103 +56,6 @@ constexpr int kEncDwCot = 8;       // output channels per thread of the weight g
 
 __global__ __launch_bounds__(256) void occ_enc_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-
-template <int T, int COG, bool POOL>
-__global__ __launch_bounds__(256) void occ_enc_dense_train_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                  float* __restrict__ rkeep, const float* __restrict__ resid,
-                                                                  const float* __restrict__ w, int cin, int cout, int H,
-                                                                  int Ho, int stride, int tiles_x,
-                                                                  float* __restrict__ partials) {
-    __shared__ float s[kEncLds];
-    constexpr int TT = T * T;
-    const int tid = threadIdx.x;
-    const int p = tid % TT;
-    const int ng = blockDim.x / TT;
-    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
-    const int co0 = (blockIdx.y * ng + g) * COG;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int oy0 = ty * T, ox0 = tx * T;
-    const int py = p / T, px = p % T;
-    const size_t plane = (size_t)H * H;
-    const float* xe = x + (size_t)blockIdx.z * cin * plane;
-    const float* bias = w + (size_t)cin * 9 * cout;
-    const float* bns = bias + cout;
-    const float* bnt = bns + cout;
-    const int R = (T - 1) * stride + 3;
-    const int RR = R * R;
-    const int iy0 = oy0 * stride - 1, ix0 = ox0 * stride - 1;
-
-    float acc[COG];
-#pragma unroll
-    for (int j = 0; j < COG; ++j) acc[j] = 0.f;
-
-    for (int ci0 = 0; ci0 < cin; ci0 += kEncCC) {
-        const int cc = min(kEncCC, cin - ci0);
-        __syncthreads();
-        for (int i = tid; i < cc * RR; i += blockDim.x) {
-            const int c = i / RR, r = i - c * RR;
-            const int ry = r / R, rx = r - ry * R;
-            const int gy = iy0 + ry, gx = ix0 + rx;
-            float v = 0.f;
-            if (gy >= 0 && gy < H && gx >= 0 && gx < H) v = xe[(ci0 + c) * plane + (size_t)gy * H + gx];
-            s[i] = v;
-        }
-        __syncthreads();
-        for (int c = 0; c < cc; ++c) {
-            const int ci = ci0 + c;
-            const float* sc = s + c * RR + (py * stride) * R + px * stride;
-            float in[9];
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) in[ky * 3 + kx] = sc[ky * R + kx];
-            const float* wr = w + (size_t)ci * 9 * cout + co0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k)  // the FMA order of occ_enc_dense_kernel
-#pragma unroll
-                for (int j = 0; j < COG; ++j) acc[j] = fmaf(wr[k * cout + j], in[k], acc[j]);
-        }
-    }
-    const int oy = oy0 + py, ox = ox0 + px;
-    const bool valid = oy < Ho && ox < Ho;
-    const size_t oplane = (size_t)Ho * Ho;
-    const size_t o = (size_t)blockIdx.z * cout * oplane + (size_t)oy * Ho + ox;
-    if constexpr (!POOL) {
-        if (!valid) return;
-#pragma unroll
-        for (int j = 0; j < COG; ++j) {
-            const int co = co0 + j;
-            const float r = fmaxf(acc[j] + bias[co], 0.f);
-            float v = fmaf(r, bns[co], bnt[co]);
-            if (resid) v += resid[o + co * oplane];
-            rkeep[o + co * oplane] = r;
-            y[o + co * oplane] = v;
-        }
-    } else {
-        static_assert(256 * COG <= kEncLds, "the pool stage reuses the LDS stage");
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < COG; ++j) {
-            const int co = co0 + j;
-            const float r = fmaxf(acc[j] + bias[co], 0.f);
-            const float v = fmaf(r, bns[co], bnt[co]);
-            s[(g * COG + j) * TT + p] = valid ? v : 0.f;
-            if (valid) {
-                rkeep[o + co * oplane] = r;
-                if (y) y[o + co * oplane] = v;  // the joint training's decoder reads the last down's output
-            }
-        }
-        __syncthreads();
-        if (tid < ng * COG) {
-            const float* row = s + tid * TT;
-            float sum = 0.f;
-            for (int q = 0; q < TT; ++q) sum += row[q];
-            const int gg = tid / COG, j = tid % COG;
-            const int ntiles = gridDim.x;
-            partials[((size_t)blockIdx.z * ntiles + blockIdx.x) * cout + (blockIdx.y * ng + gg) * COG + j] = sum;
-        }
-    }
 }
 
 // Activation step of one layer.  dy: (n, c, plane); du: (n, c, plane), may be dy itself.  POOL: dY = gf[env][ch] / count, plus
@@ -441,18 +347,18 @@ __global__ __launch_bounds__(256) void occ_enc_bwd_dw_kernel(const float* __rest
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-// The 16 layers in packed order.
+// The 16 layers in packed order.  separable: the stride-1 layers are separable ones (the downs are dense either way).
 struct EncLayer {
     int cin, cout, stride, H, Ho;  // input side, output side
     long long woff;                // floats into the packed buffer
 };
 
-inline void enc_train_layers(int img, EncLayer* L) {
+inline void enc_train_layers(int img, bool separable, EncLayer* L) {
     long long off = 0;
     int H = img, i = 0;
     auto put = [&](int cin, int cout, int stride) {
         L[i++] = {cin, cout, stride, H, enc_out_size(H, stride), off};
-        off += enc_layer_floats(cin, cout, false);
+        off += enc_layer_floats(cin, cout, separable && stride == 1);
     };
     put(4, kEncCh, 1);
     for (int lv = 0; lv < kEncLevels; ++lv) {
@@ -504,7 +410,7 @@ inline EncTrainWs enc_train_ws_layout(int img, int n) {
     l.total = at;
     l.scratch = 0;
     EncLayer L[16];
-    enc_train_layers(img, L);
+    enc_train_layers(img, false, L);
     for (int i = 0; i < 16; ++i) {
         const size_t act = (size_t)L[i].cout * n * bwd_chunks(L[i].Ho * L[i].Ho) * 3 * sizeof(double);
         const size_t dw = enc_dw_plan(L[i].cin, L[i].cout, L[i].Ho, n).part_bytes;
@@ -515,49 +421,31 @@ inline EncTrainWs enc_train_ws_layout(int img, int n) {
     return l;
 }
 
-template <int T>
-static void enc_launch_train_t(const float* x, float* y, float* r, const float* resid, const float* w, const EncLayer& L, int n,
-                               float* partials, hipStream_t st) {
-    const int cog = enc_cog(L.cout), ng = enc_groups(T, L.cout);  // the grids of enc_launch_dense_t
-    const int tiles_x = (L.Ho + T - 1) / T;
-    const dim3 grid(tiles_x * tiles_x, L.cout / (cog * ng), n), block(T * T * ng);
-#define OCC_ENC_TRAIN(COG, POOL)                                                                                              \
-    hipLaunchKernelGGL((occ_enc_dense_train_kernel<T, COG, POOL>), grid, block, 0, st, x, y, r, resid, w, L.cin, L.cout, L.H, L.Ho, \
-                       L.stride, tiles_x, partials)
-    if (partials) OCC_ENC_TRAIN(32, true);
-    else if (cog == 8) OCC_ENC_TRAIN(8, false);
-    else if (cog == 16) OCC_ENC_TRAIN(16, false);
-    else OCC_ENC_TRAIN(32, false);
-#undef OCC_ENC_TRAIN
-}
-
-static void enc_launch_train(const float* x, float* y, float* r, const float* resid, const float* w, const EncLayer& L, int n,
-                             float* partials, hipStream_t st) {
-    if (enc_tile(L.Ho) == 16) enc_launch_train_t<16>(x, y, r, resid, w, L, n, partials, st);
-    else enc_launch_train_t<8>(x, y, r, resid, w, L, n, partials, st);
-}
-
-// The dense encoder on n envs with everything kept: 18 launches.
+// The encoder, dense (dil = 1) or separable, on n envs with everything kept: 18 launches (copy, 16 layers through the
+// launchers of occ_encoder.hpp with a place for r, pool).
 // last_y: where the last down also stores its output (n, 256, H_5, H_5), or null.
-static void enc_train_forward(int img, bool residual, const float* packed, const float* obs, int n, char* ws, float* feats,
-                              hipStream_t st, float* last_y = nullptr) {
+static void enc_train_forward(int img, int dil, bool residual, bool separable, const float* packed, const float* obs, int n,
+                              char* ws, float* feats, hipStream_t st, float* last_y = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n);
     EncLayer L[16];
-    enc_train_layers(img, L);
+    enc_train_layers(img, separable, L);
     auto F = [&](size_t off) { return (float*)(ws + off); };
     const size_t nobs = (size_t)n * 4 * img * img;
     const size_t cblocks = (nobs + 1023) / 1024;
     hipLaunchKernelGGL(occ_enc_copy_kernel, dim3((unsigned)(cblocks < 65535 ? cblocks : 65535)), dim3(256), 0, st, obs, F(l.obs),
                        nobs);
-    enc_launch_train(F(l.obs), F(l.a[0]), F(l.r_init), nullptr, packed + L[0].woff, L[0], n, nullptr, st);
+    auto layer = [&](const EncLayer& Li, int d, const float* x, float* y, float* r, const float* resid, float* partials) {
+        const float* w = packed + Li.woff;
+        if (separable && Li.stride == 1) enc_launch_sep(x, y, resid, w, Li.cin, Li.cout, Li.H, d, n, st, r);
+        else enc_launch_dense(x, y, resid, w, Li.cin, Li.cout, Li.H, Li.stride, d, n, partials, st, false, r);
+    };
+    layer(L[0], 1, F(l.obs), F(l.a[0]), F(l.r_init), nullptr, nullptr);
     for (int lv = 0; lv < kEncLevels; ++lv) {
         const EncLayer* Ll = L + 1 + 3 * lv;
         const bool last = lv == kEncLevels - 1;
-        enc_launch_train(F(l.a[lv]), F(l.b[lv]), F(l.r1[lv]), nullptr, packed + Ll[0].woff, Ll[0], n, nullptr, st);
-        enc_launch_train(F(l.b[lv]), F(l.cc[lv]), F(l.r2[lv]), residual ? F(l.a[lv]) : nullptr, packed + Ll[1].woff, Ll[1], n,
-                         nullptr, st);
-        enc_launch_train(F(l.cc[lv]), last ? last_y : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, packed + Ll[2].woff, Ll[2], n,
-                         last ? F(l.part) : nullptr, st);
+        layer(Ll[0], dil, F(l.a[lv]), F(l.b[lv]), F(l.r1[lv]), nullptr, nullptr);
+        layer(Ll[1], dil, F(l.b[lv]), F(l.cc[lv]), F(l.r2[lv]), residual ? F(l.a[lv]) : nullptr, nullptr);
+        layer(Ll[2], 1, F(l.cc[lv]), last ? last_y : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, last ? F(l.part) : nullptr);
     }
     const int Hl = L[15].Ho;
     hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, F(l.part), enc_tiles(Hl), (float)(Hl * Hl), feats);
@@ -648,7 +536,7 @@ static void enc_backward(int img, bool residual, const float* packed, int n, cha
                          float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n);
     EncLayer L[16];
-    enc_train_layers(img, L);
+    enc_train_layers(img, false, L);
     auto F = [&](size_t off) { return (float*)(ws + off); };
     float *gA = F(l.g[0]), *gB = F(l.g[1]), *gC = F(l.g[2]);
     for (int lv = kEncLevels - 1; lv >= 0; --lv) {

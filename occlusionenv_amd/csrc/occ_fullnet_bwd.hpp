@@ -73,7 +73,7 @@ static void full_train_forward(int img, bool residual, const float* enc_packed, 
                                char* ws, float* feats, float* prob, hipStream_t st) {
     const FullTrainWs l = full_train_ws_layout(img, n);
     const TrainPtrs t = full_train_ptrs(l, ws);
-    enc_train_forward(img, residual, enc_packed, obs, n, ws, feats, st, t.last);
+    enc_train_forward(img, 1, residual, false, enc_packed, obs, n, ws, feats, st, t.last);
     dec_train_forward(img, dec_packed, n, t, prob, st);
 }
 

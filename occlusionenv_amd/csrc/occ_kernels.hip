@@ -31,8 +31,14 @@
 //                       conv, last down fused with the average pool
 //   occ_dec_up_kernel   the segmentation decoder of the same network (occ_decoder.hpp): transposed conv + skip add per
 //                       launch, classifier and sigmoid fused into the last; occ_seg_metrics_kernel: accuracy / IoU counts
-//   occ_dec_bwd_*       training of that decoder with the encoder frozen (occ_decoder_bwd.hpp): a forward that keeps its
-//                       activations, then activation step, input gradient and weight gradient per level, fixed-order sums
+//                       The three conv forwards (occ_enc_sep_kernel, occ_enc_dense_kernel, occ_dec_up_kernel) exist once:
+//                       instantiated with TRAIN they also store what a backward reads, and are the training forwards
+//   occ_dec_bwd_*       training of that decoder with the encoder frozen (occ_decoder_bwd.hpp): the up kernel with TRAIN,
+//                       then activation step, input gradient and weight gradient per level, fixed-order sums
+//   occ_enc_bwd_*       training of the dense encoder (occ_encoder_bwd.hpp): one training forward walk for the dense and the
+//   occ_sep_bwd_*       separable encoder, then per layer the activation step, weight and input gradients; the separable
+//                       layers' own backward kernels (occ_sepenc_bwd.hpp); the joint steps with the decoder
+//                       (occ_fullnet_bwd.hpp, occ_sepfull_bwd.hpp) have host code only
 //   occ_seg_criterion_* the pretrainer's criterion on that map (occ_criterion.hpp): Dice / BCE sums and the counts in one
 //                       read, fixed-order f64 sums, and the gradient with respect to the prediction
 //
@@ -734,7 +740,7 @@ extern "C" int occ_encoder_train_forward(const OccEncoderConfig* cfg, const floa
     if (!enc_train_cfg_ok(cfg, n_env) || !non_null(packed, obs, ws, feats)) return OCC_ERR_ARG;
     if (!aligned(16, ws) || !aligned(4, packed, obs, feats)) return OCC_ERR_ARG;
     if (ws_bytes < enc_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
-    enc_train_forward(cfg->img, cfg->residual != 0, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
+    enc_train_forward(cfg->img, 1, cfg->residual != 0, false, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 
@@ -760,7 +766,7 @@ extern "C" int occ_sep_encoder_train_forward(const OccEncoderConfig* cfg, const 
     if (!sep_train_cfg_ok(cfg, n_env) || !non_null(packed, obs, ws, feats)) return OCC_ERR_ARG;
     if (!aligned(16, ws) || !aligned(4, packed, obs, feats)) return OCC_ERR_ARG;
     if (ws_bytes < sep_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
-    sep_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
+    enc_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, true, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

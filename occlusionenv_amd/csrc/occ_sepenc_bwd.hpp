@@ -1,7 +1,7 @@
 // occ_sepenc_bwd.hpp -- training of the separable encoder (dilation 1 or 2, with or without the residual) through its
-// pooled 256-d feature: the separable counterpart of occ_encoder_bwd.hpp, whose workspace, gradient-buffer rotation and
-// kernels for the dense stride-2 downs it reuses.  Part of the single translation unit occ_kernels.hip (included inside
-// namespace occ, after occ_encoder_bwd.hpp).
+// pooled 256-d feature: the separable counterpart of occ_encoder_bwd.hpp, whose training forward (enc_train_forward, one
+// walk for both forms), workspace, gradient-buffer rotation and kernels for the dense stride-2 downs it reuses.  Part of
+// the single translation unit occ_kernels.hip (included inside namespace occ, after occ_encoder_bwd.hpp).
 //
 // A separable layer (initial at dilation 1, Layer 1 and Layer 2 of every level at dilation d): h = dw_h(dw_v(x)), both
 // depthwise convs without bias and with zero padding d, so h[ci] is the 9-tap stencil wv[ci][kv] wh[ci][kh] on zero-padded
@@ -9,8 +9,9 @@
 // residual block).  Packed: wv[ci][3] | wh[ci][3] | pw[ci][co] | bias | scale | shift.  The downs are dense (packed and
 // trained as in occ_encoder_bwd.hpp).
 //
-//   occ_enc_sep_train_kernel   occ_enc_sep_kernel with the same grid and FMA order (feats are the same to the bit) which
-//                              also stores r.  h is not kept: the backward rebuilds it from the kept x.
+//   occ_enc_sep_kernel<.., TRAIN>  (occ_encoder.hpp) the inference kernel itself, one loop nest for both (feats are the
+//                              same to the bit), whose epilogue also stores r.  h is not kept: the backward rebuilds it
+//                              from the kept x.
 //   occ_enc_bwd_act_kernel     (occ_encoder_bwd.hpp, as it is) dU = dY s [r > 0] and the f64 partials of ds, dt, dbias.
 //   occ_sep_bwd_dpw_kernel     dPW[ci][co] = sum_{n,p} h[ci][p] dU[co][p], a cin x cout contraction over K = N H^2 with the
 //                              thread layout and K split of occ_enc_bwd_dw_kernel: a thread owns 1 ci x 8 co, keeps its
@@ -39,78 +40,6 @@
 // Layer 2's dU, Layer 1's dY / dU and the block input's gradient, which is the gA of the level above.
 
 constexpr int kSepDwBlocks = 1024;  // blocks of the pointwise weight gradient per layer (K slices x (ci, co) tiles)
-
-template <int T, int COG>
-__global__ __launch_bounds__(256) void occ_enc_sep_train_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                float* __restrict__ rkeep, const float* __restrict__ resid,
-                                                                const float* __restrict__ w, int cin, int cout, int H, int d,
-                                                                int tiles_x) {
-    __shared__ float s[kEncSepLds];
-    constexpr int TT = T * T;
-    const int tid = threadIdx.x;
-    const int p = tid % TT;
-    const int ng = blockDim.x / TT;
-    const int g = __builtin_amdgcn_readfirstlane(tid / TT);
-    const int co0 = (blockIdx.y * ng + g) * COG;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-    const int oy0 = ty * T, ox0 = tx * T;
-    const int py = p / T, px = p % T;
-    const size_t plane = (size_t)H * H;
-    const float* xe = x + (size_t)blockIdx.z * cin * plane;
-    const float* wv = w;
-    const float* wh = wv + 3 * cin;
-    const float* pw = wh + 3 * cin;
-    const float* bias = pw + (size_t)cin * cout;
-    const float* bns = bias + cout;
-    const float* bnt = bns + cout;
-    const int R = T + 2 * d;
-    const int RR = R * R;
-
-    float acc[COG];
-#pragma unroll
-    for (int j = 0; j < COG; ++j) acc[j] = 0.f;
-
-    for (int ci0 = 0; ci0 < cin; ci0 += kEncCC) {
-        const int cc = min(kEncCC, cin - ci0);
-        __syncthreads();
-        for (int i = tid; i < cc * RR; i += blockDim.x) {
-            const int c = i / RR, r = i - c * RR;
-            const int ry = r / R, rx = r - ry * R;
-            const int gy = oy0 - d + ry, gx = ox0 - d + rx;
-            float v = 0.f;
-            if (gy >= 0 && gy < H && gx >= 0 && gx < H) v = xe[(ci0 + c) * plane + (size_t)gy * H + gx];
-            s[i] = v;
-        }
-        __syncthreads();
-        for (int c = 0; c < cc; ++c) {
-            const int ci = ci0 + c;
-            const float* sc = s + c * RR + py * R + px;  // staged (py - d, px - d)
-            float u = 0.f;
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh) {  // the FMA order of occ_enc_sep_kernel
-                float t = 0.f;
-#pragma unroll
-                for (int kv = 0; kv < 3; ++kv) t = fmaf(wv[ci * 3 + kv], sc[(kv * d) * R + kh * d], t);
-                u = fmaf(wh[ci * 3 + kh], t, u);
-            }
-            const float* pr = pw + (size_t)ci * cout + co0;
-#pragma unroll
-            for (int j = 0; j < COG; ++j) acc[j] = fmaf(pr[j], u, acc[j]);
-        }
-    }
-    const int oy = oy0 + py, ox = ox0 + px;
-    if (oy >= H || ox >= H) return;
-    const size_t o = (size_t)blockIdx.z * cout * plane + (size_t)oy * H + ox;
-#pragma unroll
-    for (int j = 0; j < COG; ++j) {
-        const int co = co0 + j;
-        const float r = fmaxf(acc[j] + bias[co], 0.f);
-        float v = fmaf(r, bns[co], bnt[co]);
-        if (resid) v += resid[o + co * plane];
-        rkeep[o + co * plane] = r;
-        y[o + co * plane] = v;
-    }
-}
 
 // x: (n, cin, H, H); du: (n, cout, H, H); w: the layer's packed wv[ci][3] | wh[ci][3];
 // part: [slice * PB + wave or pixel lane][cin * cout], PB = 256 / max(Q, 64).
@@ -345,24 +274,6 @@ __global__ __launch_bounds__(256) void occ_sep_bwd_dx_kernel(const float* __rest
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-// The 16 layers in packed order with the separable offsets: stride 1 = separable, stride 2 = a dense down.
-inline void sep_train_layers(int img, EncLayer* L) {
-    long long off = 0;
-    int H = img, i = 0;
-    auto put = [&](int cin, int cout, int stride) {
-        L[i++] = {cin, cout, stride, H, enc_out_size(H, stride), off};
-        off += enc_layer_floats(cin, cout, stride == 1);
-    };
-    put(4, kEncCh, 1);
-    for (int lv = 0; lv < kEncLevels; ++lv) {
-        const int c = kEncCh << lv;
-        put(c, c, 1);
-        put(c, c, 1);
-        put(c, 2 * c, 2);
-        H = enc_out_size(H, 2);
-    }
-}
-
 // The (ci, co) tile, pixel tile and K split (dw_split, occ_decoder_bwd.hpp) of the pointwise weight gradient: a thread
 // owns 1 ci x 8 co; 16-pixel tiles where a block owns at most 8 input channels (the smaller halo share).
 inline DwPlan sep_dpw_plan(int cin, int cout, int H, int n) {
@@ -378,7 +289,7 @@ inline EncTrainWs sep_train_ws_layout(int img, int n) {
     EncTrainWs l = enc_train_ws_layout(img, n);
     l.scratch = 0;
     EncLayer L[16];
-    sep_train_layers(img, L);
+    enc_train_layers(img, true, L);
     for (int i = 0; i < 16; ++i) {
         const size_t chunks = bwd_chunks(L[i].Ho * L[i].Ho);
         const size_t act = (size_t)L[i].cout * n * chunks * 3 * sizeof(double);
@@ -391,52 +302,6 @@ inline EncTrainWs sep_train_ws_layout(int img, int n) {
     }
     l.scratch = enc_align(l.scratch);
     return l;
-}
-
-template <int T>
-static void sep_launch_train_t(const float* x, float* y, float* r, const float* resid, const float* w, const EncLayer& L, int d,
-                               int n, hipStream_t st) {
-    const int cog = enc_cog(L.cout), ng = enc_groups(T, L.cout);  // the grids of enc_launch_sep_t
-    const int tiles_x = (L.H + T - 1) / T;
-    const dim3 grid(tiles_x * tiles_x, L.cout / (cog * ng), n), block(T * T * ng);
-#define OCC_SEP_TRAIN(COG) \
-    hipLaunchKernelGGL((occ_enc_sep_train_kernel<T, COG>), grid, block, 0, st, x, y, r, resid, w, L.cin, L.cout, L.H, d, tiles_x)
-    if (cog == 8) OCC_SEP_TRAIN(8);
-    else if (cog == 16) OCC_SEP_TRAIN(16);
-    else OCC_SEP_TRAIN(32);
-#undef OCC_SEP_TRAIN
-}
-
-static void sep_launch_train(const float* x, float* y, float* r, const float* resid, const float* w, const EncLayer& L, int d,
-                             int n, hipStream_t st) {
-    if (enc_tile(L.H) == 16) sep_launch_train_t<16>(x, y, r, resid, w, L, d, n, st);
-    else sep_launch_train_t<8>(x, y, r, resid, w, L, d, n, st);
-}
-
-// The separable encoder on n envs with everything kept: 18 launches.
-// y_last: where the last down also stores its output (n, 256, H_5, H_5), or null.
-static void sep_train_forward(int img, int dil, bool residual, const float* packed, const float* obs, int n, char* ws,
-                              float* feats, hipStream_t st, float* y_last = nullptr) {
-    const EncTrainWs l = enc_train_ws_layout(img, n);
-    EncLayer L[16];
-    sep_train_layers(img, L);
-    auto F = [&](size_t off) { return (float*)(ws + off); };
-    const size_t nobs = (size_t)n * 4 * img * img;
-    const size_t cblocks = (nobs + 1023) / 1024;
-    hipLaunchKernelGGL(occ_enc_copy_kernel, dim3((unsigned)(cblocks < 65535 ? cblocks : 65535)), dim3(256), 0, st, obs, F(l.obs),
-                       nobs);
-    sep_launch_train(F(l.obs), F(l.a[0]), F(l.r_init), nullptr, packed + L[0].woff, L[0], 1, n, st);
-    for (int lv = 0; lv < kEncLevels; ++lv) {
-        const EncLayer* Ll = L + 1 + 3 * lv;
-        const bool last = lv == kEncLevels - 1;
-        sep_launch_train(F(l.a[lv]), F(l.b[lv]), F(l.r1[lv]), nullptr, packed + Ll[0].woff, Ll[0], dil, n, st);
-        sep_launch_train(F(l.b[lv]), F(l.cc[lv]), F(l.r2[lv]), residual ? F(l.a[lv]) : nullptr, packed + Ll[1].woff, Ll[1], dil, n,
-                         st);
-        enc_launch_train(F(l.cc[lv]), last ? y_last : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, packed + Ll[2].woff, Ll[2], n,
-                         last ? F(l.part) : nullptr, st);
-    }
-    const int Hl = L[15].Ho;
-    hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, F(l.part), enc_tiles(Hl), (float)(Hl * Hl), feats);
 }
 
 template <int T, int CIB, int COB>
@@ -493,14 +358,14 @@ static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* 
     else hipLaunchKernelGGL((occ_sep_bwd_dx_kernel<8>), tl.grid, tl.block, 0, st, dh, dx, add, w, L.cin, L.H, d, tl.tiles_x);
 }
 
-// The backward of the latest sep_train_forward on this workspace, the deepest layer first: 112 launches.  grad_packed is
-// overwritten.  join (occ_sepfull_bwd.hpp): the decoder's gradients, which meet this pass in the dense downs as they meet
+// The backward of the latest separable enc_train_forward on this workspace, the deepest layer first: 112 launches.
+// grad_packed is overwritten.  join (occ_sepfull_bwd.hpp): the decoder's gradients, which meet this pass in the dense downs as they meet
 // enc_backward: dlast in the last down's activation step, skip[lv] in the epilogue of the down's input gradient.
 static void sep_backward(int img, int dil, bool residual, const float* packed, int n, char* ws, const float* grad_feats,
                          char* scratch, float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n);
     EncLayer L[16];
-    sep_train_layers(img, L);
+    enc_train_layers(img, true, L);
     auto F = [&](size_t off) { return (float*)(ws + off); };
     float *gA = F(l.g[0]), *gB = F(l.g[1]), *gC = F(l.g[2]);
     for (int lv = kEncLevels - 1; lv >= 0; --lv) {

@@ -4,7 +4,7 @@
 // occ_kernels.hip (included inside namespace occ, after occ_sepenc_bwd.hpp and occ_fullnet_bwd.hpp; it has no kernel and no
 // launcher of its own: both passes go through dec_backward and sep_backward).
 //
-// Forward: sep_train_forward with the last down also storing its output (18 launches), then dec_train_forward on that
+// Forward: the separable enc_train_forward with the last down also storing its output (18 launches), then dec_train_forward on that
 // output and on the encoder's level tensors cc[lv] as the skips, which are not copied (5 launches): 23 launches.  The FMA
 // order and the grids are those of the two training forwards, so feats and prob are the same to the bit.
 //
@@ -32,7 +32,7 @@ static void sep_full_train_forward(int img, int dil, bool residual, const float*
                                    const float* obs, int n, char* ws, float* feats, float* prob, hipStream_t st) {
     const FullTrainWs l = full_train_ws_layout(img, n);
     const TrainPtrs t = full_train_ptrs(l, ws);
-    sep_train_forward(img, dil, residual, enc_packed, obs, n, ws, feats, st, t.last);
+    enc_train_forward(img, dil, residual, true, enc_packed, obs, n, ws, feats, st, t.last);
     dec_train_forward(img, dec_packed, n, t, prob, st);
 }
 
