@@ -555,7 +555,7 @@ int occ_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, c
                          float* grad_enc_packed, float* grad_dec_packed, void* stream);
 
 /*
- * Joint training of the SEPARABLE encoder, the decoder and the classifier (additive in ABI 12; csrc/occ_sepfull_bwd.hpp):
+ * Joint training of the SEPARABLE encoder, the decoder and the classifier (additive in ABI 12; csrc/occ_fullnet_bwd.hpp):
  * the three entry points above for cfg->separable == 1, the step that pretrains FullNetwork(8, dilation=2, separable=True)
  * (PPO.py:47; pretrainer.py --separable --dilation 2).  Supported: cfg->separable == 1, cfg->dilation 1 or 2, cfg->residual
  * 0 or 1, cfg->img % 32 == 0 in [32, 1024], n_env in [1, 65535]; a dense cfg is refused (occ_fullnet_* are for it).  The

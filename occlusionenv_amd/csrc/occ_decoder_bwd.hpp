@@ -33,14 +33,73 @@
 // No floating-point atomics; the split of K is a function of (S, N) alone: every gradient is bitwise the same from call to
 // call.  f32 chains: a thread's accumulator sees at most tiles-per-slice x T^2 / P products before the f64 stage.
 //
-// Host side, shared with occ_encoder_bwd.hpp: DwPlan / dw_split (the K split of a weight gradient) and bwd_layer_tail (what
-// follows a layer's activation step); the grids of the up layers and of the input gradient come from tile_launch
-// (occ_encoder.hpp).
+// The tails that make up that contract exist once, as device helpers below, for the kernels of this file, of
+// occ_encoder_bwd.hpp and of occ_sepenc_bwd.hpp: bwd_block_partials (the f64 sums of a block), bwd_wave_strided_sum (the
+// final sum of block partials) and bwd_dw_fold (the pixel lanes and the partial slot of a K-split weight gradient).
+//
+// Host side, shared with occ_encoder_bwd.hpp and occ_sepenc_bwd.hpp: DwPlan / dw_split (the K split of a weight gradient)
+// and bwd_layer_tail (what follows a layer's activation step); the grids of the up layers and of the input gradient come
+// from tile_launch (occ_encoder.hpp).
 
 constexpr int kBwdChunk = 4096;   // pixels of one (env, channel) plane per block of the activation step
 constexpr int kBwdDxCC = 8;       // output channels of dU staged per step of the input gradient
 constexpr int kBwdDxCIG = 16;     // input channels per thread of the input gradient
 constexpr int kBwdDwBlocks = 512;  // blocks of the weight gradient per level (K slices x (ci, co) tiles)
+
+// ---- the fixed-order reductions of every training backward (this file, occ_encoder_bwd.hpp, occ_sepenc_bwd.hpp) --------
+
+// The NS f64 sums of a 256-thread block to dst[NS]: six __shfl_down steps per wave, then thread k < NS adds the four
+// waves in order.
+template <int NS>
+__device__ __forceinline__ void bwd_block_partials(double (&sum)[NS], double* __restrict__ dst) {
+    __shared__ double part[4][NS];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) sum[k] += __shfl_down(sum[k], d);
+    const int wave = threadIdx.x / 64;
+    if (threadIdx.x % 64 == 0)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) part[wave][k] = sum[k];
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        double t = 0.0;
+        for (int k = 0; k < 4; ++k) t += part[k][threadIdx.x];
+        dst[threadIdx.x] = t;
+    }
+}
+
+// One wave's sum of p[0], p[stride], .., p[(n - 1) stride]: lane l adds elements l, l + 64, .. in order, then six
+// __shfl_down steps; lane 0 holds the sum.
+__device__ __forceinline__ double bwd_wave_strided_sum(const double* __restrict__ p, int n, int stride) {
+    double sum = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) sum += p[(size_t)i * stride];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, d);
+    return sum;
+}
+
+// The partials a block of a K-split weight gradient writes when one pixel takes q threads: one per wave (q < 64, the
+// wave's pixel lanes are folded first) or one per pixel lane.
+constexpr int dw_partials(int q) { return 256 / (q < 64 ? 64 : q); }
+
+// The end of a K-split weight gradient kernel whose pixel takes Q threads (pixel lane pl = tid / Q): the pixel lanes of a
+// wave are added into its first Q lanes by __shfl_xor steps from Q upwards, element by element.  False: the thread stores
+// nothing; true: it stores acc into partial pb of its block's dw_partials(Q).
+template <int Q, int N>
+__device__ __forceinline__ bool bwd_dw_fold(float (&acc)[N], int pl, int& pb) {
+    if constexpr (Q < 64) {
+#pragma unroll
+        for (int d = Q; d < 64; d <<= 1)
+#pragma unroll
+            for (int i = 0; i < N; ++i) acc[i] += __shfl_xor(acc[i], d);
+        if (threadIdx.x % 64 >= Q) return false;
+        pb = threadIdx.x / 64;
+    } else {
+        pb = pl;
+    }
+    return true;
+}
 
 // Activation step of one level.  dy: (n, c, plane) (not read when LAST); du: (n, c, plane), may be dy itself (the decoder
 // alone; the joint training of occ_fullnet_bwd.hpp keeps dY, the level's d skip).  r: the forward's relu(u).
@@ -53,7 +112,6 @@ __global__ __launch_bounds__(256) void occ_dec_bwd_act_kernel(const float* dyp, 
                                                               const float* __restrict__ y4, const float* __restrict__ clsw,
                                                               double* __restrict__ partials) {
     constexpr int NS = LAST ? 5 : 3;
-    __shared__ double part[4][NS];
     const int ch = blockIdx.y, env = blockIdx.z;
     const size_t base = ((size_t)env * c + ch) * plane;
     const float sc = bns[ch];
@@ -97,20 +155,7 @@ __global__ __launch_bounds__(256) void occ_dec_bwd_act_kernel(const float* dyp, 
         }
         *reinterpret_cast<float4*>(dup + base + i) = make_float4(du[0], du[1], du[2], du[3]);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < NS; ++k) sum[k] += __shfl_down(sum[k], d);
-    const int wave = threadIdx.x / 64;
-    if (threadIdx.x % 64 == 0)
-#pragma unroll
-        for (int k = 0; k < NS; ++k) part[wave][k] = sum[k];
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        double t = 0.0;
-        for (int k = 0; k < 4; ++k) t += part[k][threadIdx.x];
-        partials[((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * NS + threadIdx.x] = t;
-    }
+    bwd_block_partials(sum, partials + ((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * NS);
 }
 
 // One wave per (channel, sum k): dst[k][ch] = the channel's nparts partials.  dst[4] (sum dz) is taken from channel 0 only
@@ -123,10 +168,7 @@ __global__ __launch_bounds__(64) void occ_dec_bwd_act_final_kernel(const double*
                                                                    BwdActDst dst) {
     const int ch = blockIdx.x, k = blockIdx.y;
     const double* pe = partials + (size_t)ch * nparts * ns + k;
-    double sum = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 64) sum += pe[(size_t)i * ns];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, d);
+    const double sum = bwd_wave_strided_sum(pe, nparts, ns);
     if (threadIdx.x != 0) return;
     if (k < 4) dst.p[k][ch] = (float)sum;
     else if (ch == 0) dst.p[4][0] = (float)sum;
@@ -252,17 +294,9 @@ __global__ __launch_bounds__(256) void occ_dec_bwd_dw_kernel(const float* __rest
             }
         }
     }
-    if constexpr (Q < 64) {  // the pixel lanes of a wave, in a fixed order
-#pragma unroll
-        for (int d = Q; d < 64; d <<= 1)
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-#pragma unroll
-                for (int k = 0; k < 9; ++k) acc[i][k] += __shfl_xor(acc[i][k], d);
-        if (tid % 64 >= Q) return;
-    }
-    constexpr int PB = 256 / (Q < 64 ? 64 : Q);
-    const int pb = Q < 64 ? tid / 64 : pl;
+    constexpr int PB = dw_partials(Q);
+    int pb;
+    if (!bwd_dw_fold<Q>(reinterpret_cast<float(&)[16 * 9]>(acc), pl, pb)) return;
     const size_t nout = (size_t)cin * 9 * cout;
     float* dst = part + ((size_t)blockIdx.x * PB + pb) * nout + (size_t)(ci0 + cig * 16) * 9 * cout + co0 + col;
 #pragma unroll
@@ -299,7 +333,7 @@ struct DwPlan {
 inline DwPlan dw_split(int cib, int cob, int T, int q, int cin, int cout, int side, int n, int blocks) {
     DwPlan p;
     p.T = T, p.cib = cib, p.cob = cob;
-    p.pb = 256 / (q < 64 ? 64 : q);
+    p.pb = dw_partials(q);
     p.grid_y = (cin / cib) * (cout / cob);
     p.tiles_x = (side + T - 1) / T;
     p.total_tiles = n * p.tiles_x * p.tiles_x;
@@ -431,14 +465,14 @@ static void dec_launch_dx(const float* du, float* dx, const float* w, int cin, i
 
 // What follows the activation step of one layer, the decoder's or the encoder's: the block partials of its `sums`
 // per-channel sums (in scratch, n_part per sum and channel) added into dst, then the weight gradient from the layer's input
-// and dU: launch_dw(part) writes the partials of plan p to scratch, which are added into gw.  3 launches.
+// and dU: launch_dw(part) writes the partials of plan p to scratch, which are added into the nout elements of gw (9 cin
+// cout of a dense layer, cin cout of a pointwise one).  3 launches.
 template <class LaunchDw>
-static void bwd_layer_tail(const DwPlan& p, int cin, int cout, int n_part, int sums, const BwdActDst& dst, char* scratch, float* gw,
+static void bwd_layer_tail(const DwPlan& p, int nout, int cout, int n_part, int sums, const BwdActDst& dst, char* scratch, float* gw,
                            hipStream_t st, LaunchDw launch_dw) {
     hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(cout, sums), dim3(64), 0, st, (const double*)scratch, n_part, sums, dst);
     float* part = (float*)scratch;
     launch_dw(part);
-    const int nout = 9 * cin * cout;
     hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, part, p.slices * p.pb, nout, gw);
 }
 
@@ -485,7 +519,7 @@ static void dec_backward(int img, const float* dec_packed, int n, const TrainPtr
             hipLaunchKernelGGL((occ_dec_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, g, t.r[j], w + 9LL * cin * c + c, c, plane,
                                nullptr, nullptr, nullptr, nullptr, (double*)scratch);
         const DwPlan p = bwd_dw_plan(j, H, n);
-        bwd_layer_tail(p, cin, c, n * chunks, last ? 5 : 3, dst, scratch, gw, st,
+        bwd_layer_tail(p, 9 * cin * c, c, n * chunks, last ? 5 : 3, dst, scratch, gw, st,
                        [&](float* part) { dec_launch_dw(p, x, g, part, cin, c, H, st); });
         if (j > 0 || join)  // into the dY of level j - 1
             dec_launch_dx(g, !join ? t.g[(kEncLevels - j) % 2] : j > 0 ? join->dskip[lv + 1] : join->dlast, w, cin, c, H, n, st);

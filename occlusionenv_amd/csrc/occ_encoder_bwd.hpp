@@ -1,9 +1,11 @@
-// occ_encoder_bwd.hpp -- training of the dense (non-separable, dilation 1) encoder through its pooled 256-d feature: a
-// forward that keeps what the backward needs, and the backward with respect to every encoder parameter.  Part of the
-// single translation unit occ_kernels.hip (included inside namespace occ, after occ_encoder.hpp, whose forward kernels it
-// launches and whose tiling and packed layout its backward mirrors, and after occ_decoder_bwd.hpp, whose reduction rule and
-// two of whose kernels it reuses).  The training forward walk (enc_train_forward) and the layer table (enc_train_layers)
-// here also serve the separable encoder (occ_sepenc_bwd.hpp).
+// occ_encoder_bwd.hpp -- training of the encoder through its pooled 256-d feature: a forward that keeps what the backward
+// needs, and the backward with respect to every encoder parameter.  The kernels here are those of the dense (non-separable,
+// dilation 1) layers; the host side -- the layer table (enc_train_layers), the workspace and scratch sizes
+// (enc_train_ws_layout), the training forward walk (enc_train_forward) and the backward walk (enc_backward) -- exists once
+// for the dense and the separable encoder, whose stride-1 layers go through sep_bwd_layer (occ_sepenc_bwd.hpp) and whose
+// downs are the dense stride-2 layers of this file.  Part of the single translation unit occ_kernels.hip (included inside
+// namespace occ, after occ_encoder.hpp, whose forward kernels it launches and whose tiling and packed layout its backward
+// mirrors, and after occ_decoder_bwd.hpp, whose reduction helpers and two of whose kernels it reuses).
 //
 // Forward per layer (16 of them: initial, then Layer 1, Layer 2, down per level): u = conv(x) + b, r = relu(u),
 // y = s r + t (+ the block input, Layer 2 of a residual block); feats = mean of the last down's y.  BatchNorm runs with
@@ -17,8 +19,8 @@
 //   occ_enc_bwd_act_kernel        per (chunk of 4096 pixels, channel, env): dU = dY s [r > 0], written to a buffer of its
 //                                 own (the dY of a residual block's Layer 2 is needed again); POOL: dY = grad_feats[n][c] /
 //                                 (H H), never stored.  f64 block partials of dS = sum dY r, dT = sum dY, dB = sum dU in
-//                                 the layout of occ_dec_bwd_act_kernel; occ_dec_bwd_act_final_kernel adds them in block
-//                                 order.  The gate is the forward's own r > 0.
+//                                 the layout of occ_dec_bwd_act_kernel (bwd_block_partials); occ_dec_bwd_act_final_kernel
+//                                 adds them in block order.  The gate is the forward's own r > 0.
 //   occ_enc_bwd_dx1_kernel        stride 1: dX[ci][y][x] = sum_co sum_k w[ci][k][co] dU[co][y + 1 - ky][x + 1 - kx] (+ add).
 //                                 A thread owns one pixel for CIG input channels; the (T + 2)^2 dU tile (one-pixel halo,
 //                                 zero outside the image) is staged in LDS 8 output channels at a time; weights are
@@ -34,17 +36,18 @@
 //                                 accumulators); a block owns a CIB x COB tile of (ci, co) and one slice of K (consecutive
 //                                 T x T output-pixel tiles, envs in order); when the tile needs fewer than 256 threads the
 //                                 others take other pixels (P pixel lanes), added inside the wave by __shfl_xor steps in
-//                                 a fixed order.  Every block writes its partial dW (one per wave or pixel lane) to caller
-//                                 scratch; occ_dec_bwd_sum_kernel adds the partials in f64 in a fixed order.
+//                                 a fixed order (bwd_dw_fold).  Every block writes its partial dW (one per wave or pixel
+//                                 lane) to caller scratch; occ_dec_bwd_sum_kernel adds the partials in f64 in a fixed order.
 //
-// Launches: train forward 18 (copy, 16 layers, pool); backward 79 (per layer act, act-final, dW, sum = 64, and the input
-// gradient of the 15 layers above the initial one).  No floating-point atomics; the split of K is a function of
-// (S, N) alone: every gradient is bitwise the same from call to call.  Nothing is allocated or synchronised.
+// Launches: train forward 18 (copy, 16 layers, pool); dense backward 79 (per layer act, act-final, dW, sum = 64, and the
+// input gradient of the 15 layers above the initial one); separable backward 112 (occ_sepenc_bwd.hpp).  No floating-point
+// atomics; the split of K is a function of (S, N) alone: every gradient is bitwise the same from call to call.  Nothing is
+// allocated or synchronised.
 // Host side: the K split (DwPlan, dw_split) and the per-layer tail (bwd_layer_tail) are those of occ_decoder_bwd.hpp, the
 // grids of the two input gradients come from tile_launch (occ_encoder.hpp).
 //
-// Workspace (occ_encoder_train_workspace_query), every part 256-byte aligned, f32, H_0 = S, H_{lv+1} = ceil(H_lv / 2),
-// c = 8 << lv:
+// Workspace (occ_encoder_train_workspace_query, occ_sep_encoder_train_workspace_query: the same tensors are kept for both
+// forms; only the scratch differs), every part 256-byte aligned, f32, H_0 = S, H_{lv+1} = ceil(H_lv / 2), c = 8 << lv:
 //   obs (n,4,S,S) | r_init (n,8,S,S) |
 //   per level lv: a (n,c,H,H) block input | r1 | b = Layer 1 output | r2 | cc = Layer 2 output (+ a) | rd (n,2c,H',H')
 //                 (a of level lv + 1 is the down's y; the last down stores no y)
@@ -66,7 +69,6 @@ __global__ __launch_bounds__(256) void occ_enc_bwd_act_kernel(const float* dy, f
                                                               const float* __restrict__ bns, int c, int plane,
                                                               const float* __restrict__ gf, float count,
                                                               double* __restrict__ partials) {
-    __shared__ double part[4][3];
     const int ch = blockIdx.y, env = blockIdx.z;
     const size_t base = ((size_t)env * c + ch) * plane;
     const float sc = bns[ch];
@@ -87,20 +89,7 @@ __global__ __launch_bounds__(256) void occ_enc_bwd_act_kernel(const float* dy, f
         sum[2] += (double)u;
         du[base + i] = u;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) sum[k] += __shfl_down(sum[k], d);
-    const int wave = threadIdx.x / 64;
-    if (threadIdx.x % 64 == 0)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) part[wave][k] = sum[k];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double t = 0.0;
-        for (int k = 0; k < 4; ++k) t += part[k][threadIdx.x];
-        partials[((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * 3 + threadIdx.x] = t;
-    }
+    bwd_block_partials(sum, partials + ((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * 3);
 }
 
 // du: (n, cout, H, H); dx, add: (n, cin, H, H); w: the layer's packed w[ci][k][co].  cin % CIG == 0, cout % 8 == 0.
@@ -326,17 +315,9 @@ __global__ __launch_bounds__(256) void occ_enc_bwd_dw_kernel(const float* __rest
             }
         }
     }
-    if constexpr (Q < 64) {  // the pixel lanes of a wave, in a fixed order
-#pragma unroll
-        for (int d = Q; d < 64; d <<= 1)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-#pragma unroll
-                for (int j = 0; j < COT; ++j) acc[k][j] += __shfl_xor(acc[k][j], d);
-        if (tid % 64 >= Q) return;
-    }
-    constexpr int PB = 256 / (Q < 64 ? 64 : Q);
-    const int pb = Q < 64 ? tid / 64 : pl;
+    constexpr int PB = dw_partials(Q);
+    int pb;
+    if (!bwd_dw_fold<Q>(reinterpret_cast<float(&)[9 * COT]>(acc), pl, pb)) return;
     const size_t nout = (size_t)cin * 9 * cout;
     float* dst = part + ((size_t)blockIdx.x * PB + pb) * nout + (size_t)(ci0 + cil) * 9 * cout + co0 + cog * COT;
 #pragma unroll
@@ -382,7 +363,14 @@ struct EncTrainWs {
     size_t total, scratch;
 };
 
-inline EncTrainWs enc_train_ws_layout(int img, int n) {
+// The separable stride-1 layer's backward (occ_sepenc_bwd.hpp, included after this file).
+inline DwPlan sep_dpw_plan(int cin, int cout, int H, int n);
+static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* grad_packed, int n, const float* x, const float* r,
+                          const float* dy, float* du, float* dh, float* dx, const float* add, char* scratch, hipStream_t st);
+
+// The workspace is the same for both forms (the same tensors are kept); the scratch is the largest of every layer's
+// activation partials, weight gradient partials (dense or, a separable layer, pointwise) and, a separable layer, G partials.
+inline EncTrainWs enc_train_ws_layout(int img, int n, bool separable) {
     EncTrainWs l;
     size_t at = 0;
     auto take = [&](size_t floats) {
@@ -410,12 +398,17 @@ inline EncTrainWs enc_train_ws_layout(int img, int n) {
     l.total = at;
     l.scratch = 0;
     EncLayer L[16];
-    enc_train_layers(img, false, L);
+    enc_train_layers(img, separable, L);
     for (int i = 0; i < 16; ++i) {
-        const size_t act = (size_t)L[i].cout * n * bwd_chunks(L[i].Ho * L[i].Ho) * 3 * sizeof(double);
-        const size_t dw = enc_dw_plan(L[i].cin, L[i].cout, L[i].Ho, n).part_bytes;
+        const bool sep = separable && L[i].stride == 1;
+        const size_t chunks = bwd_chunks(L[i].Ho * L[i].Ho);
+        const size_t act = (size_t)L[i].cout * n * chunks * 3 * sizeof(double);
+        const size_t dw = sep ? sep_dpw_plan(L[i].cin, L[i].cout, L[i].H, n).part_bytes
+                              : enc_dw_plan(L[i].cin, L[i].cout, L[i].Ho, n).part_bytes;
+        const size_t gp = sep ? (size_t)L[i].cin * n * chunks * 9 * sizeof(double) : 0;
         l.scratch = act > l.scratch ? act : l.scratch;
         l.scratch = dw > l.scratch ? dw : l.scratch;
+        l.scratch = gp > l.scratch ? gp : l.scratch;
     }
     l.scratch = enc_align(l.scratch);
     return l;
@@ -426,7 +419,7 @@ inline EncTrainWs enc_train_ws_layout(int img, int n) {
 // last_y: where the last down also stores its output (n, 256, H_5, H_5), or null.
 static void enc_train_forward(int img, int dil, bool residual, bool separable, const float* packed, const float* obs, int n,
                               char* ws, float* feats, hipStream_t st, float* last_y = nullptr) {
-    const EncTrainWs l = enc_train_ws_layout(img, n);
+    const EncTrainWs l = enc_train_ws_layout(img, n, separable);
     EncLayer L[16];
     enc_train_layers(img, separable, L);
     auto F = [&](size_t off) { return (float*)(ws + off); };
@@ -519,39 +512,69 @@ static void enc_bwd_layer(const EncLayer& L, const float* packed, float* grad_pa
                            (double*)scratch);
     const BwdActDst dst = {{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
     const DwPlan p = enc_dw_plan(L.cin, L.cout, L.Ho, n);
-    bwd_layer_tail(p, L.cin, L.cout, n * chunks, 3, dst, scratch, gw, st, [&](float* part) { enc_launch_dw(p, x, du, part, L, st); });
+    bwd_layer_tail(p, 9 * L.cin * L.cout, L.cout, n * chunks, 3, dst, scratch, gw, st, [&](float* part) { enc_launch_dw(p, x, du, part, L, st); });
 }
 
-// The backward of the latest enc_train_forward on this workspace, the deepest layer first: 79 launches.  grad_packed is
-// overwritten.  Gradient buffers per level: gA holds the down's dY / dU, gB the dY of Layer 2's output (kept for the
-// residual), gC Layer 2's dU and then the block input's gradient, which is the gA of the level above.
-// join (occ_fullnet_bwd.hpp): the decoder's gradients that meet the encoder's: dlast joins the pool backward in the last
-// down's activation step, skip[lv] joins the dY of cc[lv] in the epilogue of the down's input gradient.
+// join (occ_fullnet_bwd.hpp): the decoder's gradients that meet the encoder's, in the dense downs of either form: dlast
+// joins the pool backward in the last down's activation step, skip[lv] joins the dY of cc[lv] in the epilogue of the
+// down's input gradient.
 struct EncJoin {
     const float* dlast;             // (n, 256, H_5, H_5)
     EncSkipGrad skip[kEncLevels];
 };
 
-static void enc_backward(int img, bool residual, const float* packed, int n, char* ws, const float* grad_feats, char* scratch,
-                         float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
-    const EncTrainWs l = enc_train_ws_layout(img, n);
+// Where a stride-1 layer of the walk reads its dY and leaves dU, dH (separable only) and its input gradient (null: none).
+// Per level gA holds the down's dY / dU and gB the dY of Layer 2's output (kept for the residual); the block input's
+// gradient ends in gC, which is the gA of the level above.  In between the two forms differ:
+//   dense      gC = Layer 2's dU, gA = Layer 1's dY, turned into its dU in place;
+//   separable  gA = dH of both layers, gC = Layer 2's dU, Layer 1's dY and dU in place (the initial layer's dH goes to gC).
+struct EncBwdBufs {
+    const float* dy;
+    float *du, *dh, *dx;
+};
+enum EncBwdRole { kBwdLayer2, kBwdLayer1, kBwdInitial };
+
+inline EncBwdBufs enc_bwd_bufs(bool separable, EncBwdRole role, float* gA, float* gB, float* gC) {
+    if (separable) {
+        if (role == kBwdLayer2) return {gB, gC, gA, gC};
+        if (role == kBwdLayer1) return {gC, gC, gA, gC};
+        return {gA, gA, gC, nullptr};
+    }
+    if (role == kBwdLayer2) return {gB, gC, nullptr, gA};
+    if (role == kBwdLayer1) return {gA, gA, nullptr, gC};
+    return {gA, gA, nullptr, nullptr};
+}
+
+// The backward of the latest enc_train_forward of the same form on this workspace, the deepest layer first: 79 launches
+// (dense), 112 (separable).  grad_packed is overwritten.
+static void enc_backward(int img, int dil, bool residual, bool separable, const float* packed, int n, char* ws,
+                         const float* grad_feats, char* scratch, float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
+    const EncTrainWs l = enc_train_ws_layout(img, n, separable);
     EncLayer L[16];
-    enc_train_layers(img, false, L);
+    enc_train_layers(img, separable, L);
     auto F = [&](size_t off) { return (float*)(ws + off); };
     float *gA = F(l.g[0]), *gB = F(l.g[1]), *gC = F(l.g[2]);
+    // one stride-1 layer: its parameter gradients and, when b.dx is not null, its input gradient (+ add)
+    auto layer = [&](const EncLayer& Li, int d, EncBwdRole role, const float* x, const float* r, const float* add) {
+        const EncBwdBufs b = enc_bwd_bufs(separable, role, gA, gB, gC);
+        if (separable) {
+            sep_bwd_layer(Li, d, packed, grad_packed, n, x, r, b.dy, b.du, b.dh, b.dx, add, scratch, st);
+        } else {
+            enc_bwd_layer(Li, packed, grad_packed, n, x, r, b.dy, b.du, nullptr, scratch, st);
+            if (b.dx) enc_launch_dx1(b.du, b.dx, add, packed + Li.woff, Li, n, st);
+        }
+    };
     for (int lv = kEncLevels - 1; lv >= 0; --lv) {
         const EncLayer* Ll = L + 1 + 3 * lv;
         const bool last = lv == kEncLevels - 1;
         enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), last ? (join ? join->dlast : nullptr) : gA, gA,
                       last ? grad_feats : nullptr, scratch, st);
         enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st, join ? &join->skip[lv] : nullptr);
-        enc_bwd_layer(Ll[1], packed, grad_packed, n, F(l.b[lv]), F(l.r2[lv]), gB, gC, nullptr, scratch, st);
-        enc_launch_dx1(gC, gA, nullptr, packed + Ll[1].woff, Ll[1], n, st);
-        enc_bwd_layer(Ll[0], packed, grad_packed, n, F(l.a[lv]), F(l.r1[lv]), gA, gA, nullptr, scratch, st);
-        enc_launch_dx1(gA, gC, residual ? gB : nullptr, packed + Ll[0].woff, Ll[0], n, st);
+        layer(Ll[1], dil, kBwdLayer2, F(l.b[lv]), F(l.r2[lv]), nullptr);
+        layer(Ll[0], dil, kBwdLayer1, F(l.a[lv]), F(l.r1[lv]), residual ? gB : nullptr);
         float* t = gA;
         gA = gC;
         gC = t;
     }
-    enc_bwd_layer(L[0], packed, grad_packed, n, F(l.obs), F(l.r_init), gA, gA, nullptr, scratch, st);
+    layer(L[0], 1, kBwdInitial, F(l.obs), F(l.r_init), nullptr);
 }

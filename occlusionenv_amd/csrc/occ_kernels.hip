@@ -35,10 +35,12 @@
 //                       instantiated with TRAIN they also store what a backward reads, and are the training forwards
 //   occ_dec_bwd_*       training of that decoder with the encoder frozen (occ_decoder_bwd.hpp): the up kernel with TRAIN,
 //                       then activation step, input gradient and weight gradient per level, fixed-order sums
-//   occ_enc_bwd_*       training of the dense encoder (occ_encoder_bwd.hpp): one training forward walk for the dense and the
-//   occ_sep_bwd_*       separable encoder, then per layer the activation step, weight and input gradients; the separable
-//                       layers' own backward kernels (occ_sepenc_bwd.hpp); the joint steps with the decoder
-//                       (occ_fullnet_bwd.hpp, occ_sepfull_bwd.hpp) have host code only
+//                       The fixed-order f64 reductions of every training backward (block partials, wave-final sum, pixel-
+//                       lane fold of a K-split weight gradient) exist once, as device helpers at the top of that file
+//   occ_enc_bwd_*       training of the encoder (occ_encoder_bwd.hpp): one training forward walk and one backward walk for
+//   occ_sep_bwd_*       the dense and the separable encoder, per layer the activation step, weight and input gradients;
+//                       the separable layer's own backward kernels (occ_sepenc_bwd.hpp); the joint step with the decoder
+//                       (occ_fullnet_bwd.hpp), one for both encoder forms, has host code only
 //   occ_seg_criterion_* the pretrainer's criterion on that map (occ_criterion.hpp): Dice / BCE sums and the counts in one
 //                       read, fixed-order f64 sums, and the gradient with respect to the prediction
 //
@@ -70,7 +72,6 @@ namespace occ {
 #include "occ_encoder_bwd.hpp"
 #include "occ_sepenc_bwd.hpp"
 #include "occ_fullnet_bwd.hpp"
-#include "occ_sepfull_bwd.hpp"
 #include "occ_criterion.hpp"
 
 }  // namespace occ
@@ -694,7 +695,7 @@ template <class... P>
 static bool aligned(uintptr_t bytes, P... p) {
     return ((... | (uintptr_t)p) & (bytes - 1)) == 0;
 }
-// the answer of the three workspace queries
+// the answer of the training workspace queries
 template <class Layout>
 static int train_sizes(const Layout& l, size_t* ws_bytes, size_t* scratch_bytes) {
     *ws_bytes = l.total;
@@ -729,121 +730,136 @@ extern "C" int occ_segment_backward(const OccEncoderConfig* cfg, const float* de
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 
-// ---- encoder training (occ_encoder_bwd.hpp) ------------------------------------------------------------------------------
+// ---- encoder training (occ_encoder_bwd.hpp, occ_sepenc_bwd.hpp) and joint training (occ_fullnet_bwd.hpp) -----------------
+// Each entry point exists for the dense encoder (which refuses a separable config or dilation != 1) and for the separable
+// one (which refuses a dense config): a pair shares its body, given its config predicate and its form.
+typedef bool (*TrainCfgOk)(const OccEncoderConfig*, int);
+
+static int enc_train_query(TrainCfgOk ok, bool separable, const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes,
+                           size_t* scratch_bytes) {
+    if (!ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    return train_sizes(enc_train_ws_layout(cfg->img, n_env, separable), ws_bytes, scratch_bytes);
+}
+
+static int enc_train_fwd(TrainCfgOk ok, bool separable, const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env,
+                         void* ws, size_t ws_bytes, float* feats, void* stream) {
+    if (!ok(cfg, n_env) || !non_null(packed, obs, ws, feats)) return OCC_ERR_ARG;
+    if (!aligned(16, ws) || !aligned(4, packed, obs, feats)) return OCC_ERR_ARG;
+    if (ws_bytes < enc_train_ws_layout(cfg->img, n_env, separable).total) return OCC_ERR_ARG;
+    enc_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, separable, packed, obs, n_env, (char*)ws, feats,
+                      (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+static int enc_train_bwd(TrainCfgOk ok, bool separable, const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws,
+                         size_t ws_bytes, const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed,
+                         void* stream) {
+    if (!ok(cfg, n_env) || !non_null(packed, ws, grad_feats, scratch, grad_packed)) return OCC_ERR_ARG;
+    if (!aligned(16, ws, scratch) || !aligned(4, packed, grad_feats, grad_packed)) return OCC_ERR_ARG;
+    const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env, separable);
+    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
+    enc_backward(cfg->img, cfg->dilation, cfg->residual != 0, separable, packed, n_env, (char*)ws, grad_feats, (char*)scratch,
+                 grad_packed, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+static int full_train_query(TrainCfgOk ok, bool separable, const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes,
+                            size_t* scratch_bytes) {
+    if (!ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    return train_sizes(full_train_ws_layout(cfg->img, n_env, separable), ws_bytes, scratch_bytes);
+}
+
+static int full_train_fwd(TrainCfgOk ok, bool separable, const OccEncoderConfig* cfg, const float* enc_packed,
+                          const float* dec_packed, const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats,
+                          float* prob, void* stream) {
+    if (!ok(cfg, n_env) || !non_null(enc_packed, dec_packed, obs, ws, feats, prob)) return OCC_ERR_ARG;
+    if (!aligned(16, ws) || !aligned(8, prob) || !aligned(4, enc_packed, dec_packed, obs, feats)) return OCC_ERR_ARG;
+    if (ws_bytes < full_train_ws_layout(cfg->img, n_env, separable).total) return OCC_ERR_ARG;
+    full_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, separable, enc_packed, dec_packed, obs, n_env, (char*)ws, feats,
+                       prob, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+static int full_train_bwd(TrainCfgOk ok, bool separable, const OccEncoderConfig* cfg, const float* enc_packed,
+                          const float* dec_packed, int n_env, void* ws, size_t ws_bytes, const float* grad_feats,
+                          const float* grad_prob, void* scratch, size_t scratch_bytes, float* grad_enc_packed,
+                          float* grad_dec_packed, void* stream) {
+    if (!ok(cfg, n_env) || !non_null(enc_packed, dec_packed, ws, grad_feats, grad_prob, scratch, grad_enc_packed, grad_dec_packed))
+        return OCC_ERR_ARG;
+    if (!aligned(16, ws, scratch, grad_prob) || !aligned(4, enc_packed, dec_packed, grad_feats, grad_enc_packed, grad_dec_packed))
+        return OCC_ERR_ARG;
+    const FullTrainWs l = full_train_ws_layout(cfg->img, n_env, separable);
+    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
+    full_backward(cfg->img, cfg->dilation, cfg->residual != 0, separable, enc_packed, dec_packed, n_env, (char*)ws, grad_feats,
+                  grad_prob, (char*)scratch, grad_enc_packed, grad_dec_packed, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
 extern "C" int occ_encoder_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
-    if (!enc_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
-    return train_sizes(enc_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
+    return enc_train_query(enc_train_cfg_ok, false, cfg, n_env, ws_bytes, scratch_bytes);
 }
 
 extern "C" int occ_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env, void* ws,
                                          size_t ws_bytes, float* feats, void* stream) {
-    if (!enc_train_cfg_ok(cfg, n_env) || !non_null(packed, obs, ws, feats)) return OCC_ERR_ARG;
-    if (!aligned(16, ws) || !aligned(4, packed, obs, feats)) return OCC_ERR_ARG;
-    if (ws_bytes < enc_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
-    enc_train_forward(cfg->img, 1, cfg->residual != 0, false, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return enc_train_fwd(enc_train_cfg_ok, false, cfg, packed, obs, n_env, ws, ws_bytes, feats, stream);
 }
 
 extern "C" int occ_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
                                     const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed, void* stream) {
-    if (!enc_train_cfg_ok(cfg, n_env) || !non_null(packed, ws, grad_feats, scratch, grad_packed)) return OCC_ERR_ARG;
-    if (!aligned(16, ws, scratch) || !aligned(4, packed, grad_feats, grad_packed)) return OCC_ERR_ARG;
-    const EncTrainWs l = enc_train_ws_layout(cfg->img, n_env);
-    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
-    enc_backward(cfg->img, cfg->residual != 0, packed, n_env, (char*)ws, grad_feats, (char*)scratch, grad_packed, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return enc_train_bwd(enc_train_cfg_ok, false, cfg, packed, n_env, ws, ws_bytes, grad_feats, scratch, scratch_bytes, grad_packed,
+                         stream);
 }
 
-// ---- separable encoder training (occ_sepenc_bwd.hpp) -------------------------------------------------------------------
 extern "C" int occ_sep_encoder_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes,
                                                      size_t* scratch_bytes) {
-    if (!sep_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
-    return train_sizes(sep_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
+    return enc_train_query(sep_train_cfg_ok, true, cfg, n_env, ws_bytes, scratch_bytes);
 }
 
 extern "C" int occ_sep_encoder_train_forward(const OccEncoderConfig* cfg, const float* packed, const float* obs, int n_env, void* ws,
                                              size_t ws_bytes, float* feats, void* stream) {
-    if (!sep_train_cfg_ok(cfg, n_env) || !non_null(packed, obs, ws, feats)) return OCC_ERR_ARG;
-    if (!aligned(16, ws) || !aligned(4, packed, obs, feats)) return OCC_ERR_ARG;
-    if (ws_bytes < sep_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
-    enc_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, true, packed, obs, n_env, (char*)ws, feats, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return enc_train_fwd(sep_train_cfg_ok, true, cfg, packed, obs, n_env, ws, ws_bytes, feats, stream);
 }
 
 extern "C" int occ_sep_encoder_backward(const OccEncoderConfig* cfg, const float* packed, int n_env, void* ws, size_t ws_bytes,
                                         const float* grad_feats, void* scratch, size_t scratch_bytes, float* grad_packed,
                                         void* stream) {
-    if (!sep_train_cfg_ok(cfg, n_env) || !non_null(packed, ws, grad_feats, scratch, grad_packed)) return OCC_ERR_ARG;
-    if (!aligned(16, ws, scratch) || !aligned(4, packed, grad_feats, grad_packed)) return OCC_ERR_ARG;
-    const EncTrainWs l = sep_train_ws_layout(cfg->img, n_env);
-    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
-    sep_backward(cfg->img, cfg->dilation, cfg->residual != 0, packed, n_env, (char*)ws, grad_feats, (char*)scratch, grad_packed,
-                 (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return enc_train_bwd(sep_train_cfg_ok, true, cfg, packed, n_env, ws, ws_bytes, grad_feats, scratch, scratch_bytes, grad_packed,
+                         stream);
 }
 
-// ---- joint training of encoder, decoder and classifier (occ_fullnet_bwd.hpp) ---------------------------------------------
 extern "C" int occ_fullnet_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes) {
-    if (!full_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
-    return train_sizes(full_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
+    return full_train_query(full_train_cfg_ok, false, cfg, n_env, ws_bytes, scratch_bytes);
 }
 
 extern "C" int occ_fullnet_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
                                          const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
                                          void* stream) {
-    if (!full_train_cfg_ok(cfg, n_env) || !non_null(enc_packed, dec_packed, obs, ws, feats, prob)) return OCC_ERR_ARG;
-    if (!aligned(16, ws) || !aligned(8, prob) || !aligned(4, enc_packed, dec_packed, obs, feats)) return OCC_ERR_ARG;
-    if (ws_bytes < full_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
-    full_train_forward(cfg->img, cfg->residual != 0, enc_packed, dec_packed, obs, n_env, (char*)ws, feats, prob, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return full_train_fwd(full_train_cfg_ok, false, cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, stream);
 }
 
 extern "C" int occ_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env,
                                     void* ws, size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch,
                                     size_t scratch_bytes, float* grad_enc_packed, float* grad_dec_packed, void* stream) {
-    if (!full_train_cfg_ok(cfg, n_env) ||
-        !non_null(enc_packed, dec_packed, ws, grad_feats, grad_prob, scratch, grad_enc_packed, grad_dec_packed))
-        return OCC_ERR_ARG;
-    if (!aligned(16, ws, scratch, grad_prob) || !aligned(4, enc_packed, dec_packed, grad_feats, grad_enc_packed, grad_dec_packed))
-        return OCC_ERR_ARG;
-    const FullTrainWs l = full_train_ws_layout(cfg->img, n_env);
-    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
-    full_backward(cfg->img, cfg->residual != 0, enc_packed, dec_packed, n_env, (char*)ws, grad_feats, grad_prob, (char*)scratch,
-                  grad_enc_packed, grad_dec_packed, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return full_train_bwd(full_train_cfg_ok, false, cfg, enc_packed, dec_packed, n_env, ws, ws_bytes, grad_feats, grad_prob, scratch,
+                          scratch_bytes, grad_enc_packed, grad_dec_packed, stream);
 }
 
-// ---- joint training of the separable encoder, decoder and classifier (occ_sepfull_bwd.hpp) -----------------------------
 extern "C" int occ_sep_fullnet_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes,
                                                      size_t* scratch_bytes) {
-    if (!sep_full_train_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
-    return train_sizes(sep_full_train_ws_layout(cfg->img, n_env), ws_bytes, scratch_bytes);
+    return full_train_query(sep_full_train_cfg_ok, true, cfg, n_env, ws_bytes, scratch_bytes);
 }
 
 extern "C" int occ_sep_fullnet_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
                                              const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
                                              void* stream) {
-    if (!sep_full_train_cfg_ok(cfg, n_env) || !non_null(enc_packed, dec_packed, obs, ws, feats, prob)) return OCC_ERR_ARG;
-    if (!aligned(16, ws) || !aligned(8, prob) || !aligned(4, enc_packed, dec_packed, obs, feats)) return OCC_ERR_ARG;
-    if (ws_bytes < sep_full_train_ws_layout(cfg->img, n_env).total) return OCC_ERR_ARG;
-    sep_full_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, enc_packed, dec_packed, obs, n_env, (char*)ws, feats, prob,
-                           (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return full_train_fwd(sep_full_train_cfg_ok, true, cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, stream);
 }
 
 extern "C" int occ_sep_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env,
                                         void* ws, size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch,
                                         size_t scratch_bytes, float* grad_enc_packed, float* grad_dec_packed, void* stream) {
-    if (!sep_full_train_cfg_ok(cfg, n_env) ||
-        !non_null(enc_packed, dec_packed, ws, grad_feats, grad_prob, scratch, grad_enc_packed, grad_dec_packed))
-        return OCC_ERR_ARG;
-    if (!aligned(16, ws, scratch, grad_prob) || !aligned(4, enc_packed, dec_packed, grad_feats, grad_enc_packed, grad_dec_packed))
-        return OCC_ERR_ARG;
-    const FullTrainWs l = sep_full_train_ws_layout(cfg->img, n_env);
-    if (ws_bytes < l.total || scratch_bytes < l.scratch) return OCC_ERR_ARG;
-    sep_full_backward(cfg->img, cfg->dilation, cfg->residual != 0, enc_packed, dec_packed, n_env, (char*)ws, grad_feats, grad_prob,
-                      (char*)scratch, grad_enc_packed, grad_dec_packed, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return full_train_bwd(sep_full_train_cfg_ok, true, cfg, enc_packed, dec_packed, n_env, ws, ws_bytes, grad_feats, grad_prob,
+                          scratch, scratch_bytes, grad_enc_packed, grad_dec_packed, stream);
 }
 
 extern "C" int occ_seg_metrics(const float* pred, const float* target, int target_stride, int n_env, int img, int64_t* counts,

@@ -1,7 +1,8 @@
-// occ_sepenc_bwd.hpp -- training of the separable encoder (dilation 1 or 2, with or without the residual) through its
-// pooled 256-d feature: the separable counterpart of occ_encoder_bwd.hpp, whose training forward (enc_train_forward, one
-// walk for both forms), workspace, gradient-buffer rotation and kernels for the dense stride-2 downs it reuses.  Part of
-// the single translation unit occ_kernels.hip (included inside namespace occ, after occ_encoder_bwd.hpp).
+// occ_sepenc_bwd.hpp -- the backward of one separable layer (dilation 1 or 2): its kernels, the K split of its pointwise
+// weight gradient (sep_dpw_plan) and sep_bwd_layer, which the one backward walk of occ_encoder_bwd.hpp (enc_backward with
+// `separable`) calls for the initial layer and for Layer 1 and Layer 2 of every level.  The training forward, the workspace,
+// the gradient-buffer rotation and the dense stride-2 downs are those of occ_encoder_bwd.hpp.  Part of the single
+// translation unit occ_kernels.hip (included inside namespace occ, after occ_encoder_bwd.hpp).
 //
 // A separable layer (initial at dilation 1, Layer 1 and Layer 2 of every level at dilation d): h = dw_h(dw_v(x)), both
 // depthwise convs without bias and with zero padding d, so h[ci] is the 9-tap stencil wv[ci][kv] wh[ci][kh] on zero-padded
@@ -14,30 +15,25 @@
 //                              from the kept x.
 //   occ_enc_bwd_act_kernel     (occ_encoder_bwd.hpp, as it is) dU = dY s [r > 0] and the f64 partials of ds, dt, dbias.
 //   occ_sep_bwd_dpw_kernel     dPW[ci][co] = sum_{n,p} h[ci][p] dU[co][p], a cin x cout contraction over K = N H^2 with the
-//                              thread layout and K split of occ_enc_bwd_dw_kernel: a thread owns 1 ci x 8 co, keeps its
-//                              channel's six depthwise taps in registers and forms h of each pixel from the LDS-staged x
-//                              tile (halo d) in the forward's FMA order.  Partials to caller scratch, added by
-//                              occ_dec_bwd_sum_kernel.
+//                              thread layout, K split and lane fold (bwd_dw_fold) of occ_enc_bwd_dw_kernel: a thread owns
+//                              1 ci x 8 co, keeps its channel's six depthwise taps in registers and forms h of each pixel
+//                              from the LDS-staged x tile (halo d) in the forward's FMA order.  Partials to caller scratch,
+//                              added by occ_dec_bwd_sum_kernel (bwd_layer_tail with cin cout elements).
 //   occ_sep_bwd_dh_kernel      dH[ci][p] = sum_co pw[ci][co] dU[co][p]: a thread owns one pixel for CIG input channels,
 //                              weights are wave-uniform scalar loads.
 //   occ_sep_bwd_g_kernel       per (chunk of 4096 pixels, channel, env) the nine correlation sums
 //                              G[kv][kh] = sum_p dH[p] x[p + ((kv - 1) d, (kh - 1) d)] (x zero outside), in f64, as block
-//                              partials in the layout of occ_enc_bwd_act_kernel with nine sums.
-//   occ_sep_bwd_g_final_kernel one wave per channel: the partials of G in block order, then in f64
+//                              partials in the layout of occ_enc_bwd_act_kernel with nine sums (bwd_block_partials).
+//   occ_sep_bwd_g_final_kernel one wave per channel: the partials of G in block order (bwd_wave_strided_sum), then in f64
 //                              dwv[kv] = sum_kh wh[kh] G[kv][kh], dwh[kh] = sum_kv wv[kv] G[kv][kh].
 //   occ_sep_bwd_dx_kernel      dX[ci][p] = sum_{kv,kh} wv[kv] wh[kh] dH[ci][p - ((kv - 1) d, (kh - 1) d)] (+ add, the
 //                              residual's second path): the forward's depthwise pair with the stencil flipped, two 3-tap
 //                              passes in registers on an LDS tile of side T + 2 d.  Not run for the initial layer.
 //
-// Launches: train forward 18 (copy, 16 layers, pool).  Backward 112: a separable layer takes 8 (act, act-final, dPW, sum,
-// dH, G, G-final, dX; 7 for the initial layer), a down 5 as in occ_encoder_bwd.hpp.  No floating-point atomics; every
-// reduction over pixels or envs goes through block partials in caller scratch added in f64 in a fixed order, and the K
-// split is a function of (S, N) alone: every gradient is bitwise the same from call to call.  Nothing is allocated or
-// synchronised.
-//
-// Workspace: that of occ_encoder_train_workspace_query (EncTrainWs: the same tensors are kept).  Gradient buffers per
-// level: gA holds the down's dY / dU and then dH of both layers, gB the dY of Layer 2's output (kept for the residual), gC
-// Layer 2's dU, Layer 1's dY / dU and the block input's gradient, which is the gA of the level above.
+// Launches: a separable layer takes 8 (act, act-final, dPW, sum, dH, G, G-final, dX; 7 for the initial layer), a down 5 as
+// in occ_encoder_bwd.hpp: 112 for the backward.  No floating-point atomics; every reduction over pixels or envs goes through
+// block partials in caller scratch added in f64 in a fixed order, and the K split is a function of (S, N) alone: every
+// gradient is bitwise the same from call to call.  Nothing is allocated or synchronised.
 
 constexpr int kSepDwBlocks = 1024;  // blocks of the pointwise weight gradient per layer (K slices x (ci, co) tiles)
 
@@ -106,15 +102,9 @@ __global__ __launch_bounds__(256) void occ_sep_bwd_dpw_kernel(const float* __res
             for (int j = 0; j < COT; ++j) acc[j] = fmaf(h, dp[j * TT], acc[j]);
         }
     }
-    if constexpr (Q < 64) {  // the pixel lanes of a wave, in a fixed order
-#pragma unroll
-        for (int s = Q; s < 64; s <<= 1)
-#pragma unroll
-            for (int j = 0; j < COT; ++j) acc[j] += __shfl_xor(acc[j], s);
-        if (tid % 64 >= Q) return;
-    }
-    constexpr int PB = 256 / (Q < 64 ? 64 : Q);
-    const int pb = Q < 64 ? tid / 64 : pl;
+    constexpr int PB = dw_partials(Q);
+    int pb;
+    if (!bwd_dw_fold<Q>(acc, pl, pb)) return;
     const size_t nout = (size_t)cin * cout;
     float* dst = part + ((size_t)blockIdx.x * PB + pb) * nout + (size_t)(ci0 + cil) * cout + co0 + cog * COT;
 #pragma unroll
@@ -150,7 +140,6 @@ __global__ __launch_bounds__(256) void occ_sep_bwd_dh_kernel(const float* __rest
 // x, dh: (n, c, H, H).  partials[((ch * n + env) * chunks + chunk) * 9 + kv * 3 + kh].
 __global__ __launch_bounds__(256) void occ_sep_bwd_g_kernel(const float* __restrict__ x, const float* __restrict__ dh, int c,
                                                             int H, int d, double* __restrict__ partials) {
-    __shared__ double part[4][9];
     const int ch = blockIdx.y, env = blockIdx.z;
     const int plane = H * H;
     const size_t base = ((size_t)env * c + ch) * plane;
@@ -173,37 +162,17 @@ __global__ __launch_bounds__(256) void occ_sep_bwd_g_kernel(const float* __restr
                 sum[kv * 3 + kh] = fma(g, (double)v, sum[kv * 3 + kh]);
             }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) sum[k] += __shfl_down(sum[k], s);
-    const int wave = threadIdx.x / 64;
-    if (threadIdx.x % 64 == 0)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) part[wave][k] = sum[k];
-    __syncthreads();
-    if (threadIdx.x < 9) {
-        double t = 0.0;
-        for (int k = 0; k < 4; ++k) t += part[k][threadIdx.x];
-        partials[((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * 9 + threadIdx.x] = t;
-    }
+    bwd_block_partials(sum, partials + ((((size_t)ch * gridDim.z + env) * gridDim.x) + blockIdx.x) * 9);
 }
 
-// One wave per channel: G = the channel's nparts partials (lane l adds partials l, l + 64, .. in order, then six
-// shuffle steps), then the two depthwise gradients.  w, gw: the layer's packed wv[ci][3] | wh[ci][3] and its gradient.
+// One wave per channel: G = the channel's nparts partials (bwd_wave_strided_sum), then the two depthwise gradients.  w, gw: the layer's packed wv[ci][3] | wh[ci][3] and its gradient.
 __global__ __launch_bounds__(64) void occ_sep_bwd_g_final_kernel(const double* __restrict__ partials, int nparts,
                                                                  const float* __restrict__ w, float* __restrict__ gw, int cin) {
     const int ch = blockIdx.x;
     const double* pe = partials + (size_t)ch * nparts * 9;
     double G[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        double sum = 0.0;
-        for (int i = threadIdx.x; i < nparts; i += 64) sum += pe[(size_t)i * 9 + k];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) sum += __shfl_down(sum, s);
-        G[k] = sum;
-    }
+    for (int k = 0; k < 9; ++k) G[k] = bwd_wave_strided_sum(pe + k, nparts, 9);
     if (threadIdx.x != 0) return;
     const float* wv = w + ch * 3;
     const float* wh = w + 3 * cin + ch * 3;
@@ -283,27 +252,6 @@ inline DwPlan sep_dpw_plan(int cin, int cout, int H, int n) {
     return p;
 }
 
-// The workspace is the dense training workspace; the scratch is the largest of every layer's activation partials, weight
-// gradient partials (pointwise or, a down, dense) and G partials.
-inline EncTrainWs sep_train_ws_layout(int img, int n) {
-    EncTrainWs l = enc_train_ws_layout(img, n);
-    l.scratch = 0;
-    EncLayer L[16];
-    enc_train_layers(img, true, L);
-    for (int i = 0; i < 16; ++i) {
-        const size_t chunks = bwd_chunks(L[i].Ho * L[i].Ho);
-        const size_t act = (size_t)L[i].cout * n * chunks * 3 * sizeof(double);
-        const size_t dw = L[i].stride == 1 ? sep_dpw_plan(L[i].cin, L[i].cout, L[i].H, n).part_bytes
-                                           : enc_dw_plan(L[i].cin, L[i].cout, L[i].Ho, n).part_bytes;
-        const size_t gp = L[i].stride == 1 ? (size_t)L[i].cin * n * chunks * 9 * sizeof(double) : 0;
-        l.scratch = act > l.scratch ? act : l.scratch;
-        l.scratch = dw > l.scratch ? dw : l.scratch;
-        l.scratch = gp > l.scratch ? gp : l.scratch;
-    }
-    l.scratch = enc_align(l.scratch);
-    return l;
-}
-
 template <int T, int CIB, int COB>
 static void sep_launch_dpw_t(const DwPlan& p, const float* x, const float* du, const float* w, float* part, const EncLayer& L, int d,
                              hipStream_t st) {
@@ -335,12 +283,9 @@ static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* 
     hipLaunchKernelGGL((occ_enc_bwd_act_kernel<false>), dim3(chunks, L.cout, n), dim3(256), 0, st, dy, du, r, bns, L.cout, plane,
                        nullptr, 1.f, (double*)scratch);
     const BwdActDst dst = {{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
-    hipLaunchKernelGGL(occ_dec_bwd_act_final_kernel, dim3(L.cout, 3), dim3(64), 0, st, (const double*)scratch, n * chunks, 3, dst);
     const DwPlan p = sep_dpw_plan(L.cin, L.cout, L.H, n);
-    sep_launch_dpw(p, x, du, w, (float*)scratch, L, d, st);
-    const int nout = L.cin * L.cout;
-    hipLaunchKernelGGL(occ_dec_bwd_sum_kernel, dim3((nout + 63) / 64), dim3(256), 0, st, (const float*)scratch, p.slices * p.pb, nout,
-                       gpw);
+    bwd_layer_tail(p, L.cin * L.cout, L.cout, n * chunks, 3, dst, scratch, gpw, st,
+                   [&](float* part) { sep_launch_dpw(p, x, du, w, part, L, d, st); });
     const int pblocks = (plane + 255) / 256;
     if (L.cin == 4)
         hipLaunchKernelGGL((occ_sep_bwd_dh_kernel<4>), dim3(pblocks, 1, n), dim3(256), 0, st, du, dh, pw, L.cin, L.cout, plane);
@@ -356,30 +301,4 @@ static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* 
     const TileLaunch tl = tile_launch(T, L.H, L.cin / 8, n);
     if (T == 16) hipLaunchKernelGGL((occ_sep_bwd_dx_kernel<16>), tl.grid, tl.block, 0, st, dh, dx, add, w, L.cin, L.H, d, tl.tiles_x);
     else hipLaunchKernelGGL((occ_sep_bwd_dx_kernel<8>), tl.grid, tl.block, 0, st, dh, dx, add, w, L.cin, L.H, d, tl.tiles_x);
-}
-
-// The backward of the latest separable enc_train_forward on this workspace, the deepest layer first: 112 launches.
-// grad_packed is overwritten.  join (occ_sepfull_bwd.hpp): the decoder's gradients, which meet this pass in the dense downs as they meet
-// enc_backward: dlast in the last down's activation step, skip[lv] in the epilogue of the down's input gradient.
-static void sep_backward(int img, int dil, bool residual, const float* packed, int n, char* ws, const float* grad_feats,
-                         char* scratch, float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
-    const EncTrainWs l = enc_train_ws_layout(img, n);
-    EncLayer L[16];
-    enc_train_layers(img, true, L);
-    auto F = [&](size_t off) { return (float*)(ws + off); };
-    float *gA = F(l.g[0]), *gB = F(l.g[1]), *gC = F(l.g[2]);
-    for (int lv = kEncLevels - 1; lv >= 0; --lv) {
-        const EncLayer* Ll = L + 1 + 3 * lv;
-        const bool last = lv == kEncLevels - 1;
-        enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), last ? (join ? join->dlast : nullptr) : gA, gA,
-                      last ? grad_feats : nullptr, scratch, st);
-        enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st, join ? &join->skip[lv] : nullptr);
-        sep_bwd_layer(Ll[1], dil, packed, grad_packed, n, F(l.b[lv]), F(l.r2[lv]), gB, gC, gA, gC, nullptr, scratch, st);
-        sep_bwd_layer(Ll[0], dil, packed, grad_packed, n, F(l.a[lv]), F(l.r1[lv]), gC, gC, gA, gC, residual ? gB : nullptr, scratch,
-                      st);
-        float* t = gA;
-        gA = gC;
-        gC = t;
-    }
-    sep_bwd_layer(L[0], 1, packed, grad_packed, n, F(l.obs), F(l.r_init), gA, gA, gC, nullptr, nullptr, scratch, st);
 }

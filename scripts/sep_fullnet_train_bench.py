@@ -1,5 +1,5 @@
 """One step of the pretrainer below its optimizer on the network the agent runs, FullNetwork(8, dilation=2, separable=True):
-native (occlusionenv_amd/sepfullnet.py: ``net(obs)`` -> Dice + MSE -> ``backward``; csrc/occ_sepfull_bwd.hpp) against
+native (occlusionenv_amd/sepfullnet.py: ``net(obs)`` -> Dice + MSE -> ``backward``; csrc/occ_fullnet_bwd.hpp) against
 (a) the same network as PyTorch-ROCm ops in f32 with torch autograd (tests/segmenter_model.full_forward, BatchNorm in eval
 mode), and (b) what reaches the same parameters without the joint backward: one ``seghead.SegmentationHead`` step (Dice) plus
 one ``septrain.TrainableSeparableEncoder`` step (MSE on the head), which runs the encoder twice and still misses the join.

@@ -1,4 +1,4 @@
-"""GPU tests of the native joint backward of the separable network (csrc/occ_sepfull_bwd.hpp,
+"""GPU tests of the native joint backward of the separable network (csrc/occ_fullnet_bwd.hpp,
 occlusionenv_amd/sepfullnet.py, harness.pretrain_epoch) against tests/sep_fullnet_train_model.py in f64 on the CPU with torch
 autograd.
 

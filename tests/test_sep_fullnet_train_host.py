@@ -1,4 +1,4 @@
-"""Host-side checks of the joint training path of the separable network (csrc/occ_sepfull_bwd.hpp,
+"""Host-side checks of the joint training path of the separable network (csrc/occ_fullnet_bwd.hpp,
 occlusionenv_amd/sepfullnet.py): the three entry points are exported and reject what they do not support before anything is
 launched, the workspace query is the restated layout, the two parts' packed layouts round-trip from the whole checkpoint,
 the f64 model of tests/sep_fullnet_train_model.py is the composition of the separable encoder's and the decoder's models,
