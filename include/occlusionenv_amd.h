@@ -590,6 +590,46 @@ int occ_sep_fullnet_backward(const OccEncoderConfig* cfg, const float* enc_packe
                              float* grad_enc_packed, float* grad_dec_packed, void* stream);
 
 /*
+ * The joint training step with batch-statistics ("train-mode") BatchNorm (additive in ABI 12; csrc/occ_bn_train.hpp):
+ * nn.BatchNorm2d as pretrainer.py runs it after model.train(), in all 21 layers (16 encoder layers, 5 decoder levels), for
+ * BOTH encoder forms: cfg->separable == 0 with the limits of occ_fullnet_*, cfg->separable == 1 with those of
+ * occ_sep_fullnet_*.  The arguments are those of the occ_fullnet_* functions, with these differences.  enc_packed and
+ * dec_packed carry gamma and beta (NOT folded) in every layer's scale / shift slots; grad_enc_packed and grad_dec_packed
+ * carry d gamma and d beta there.  Per layer and channel c, over the M = n_env H W values of r = relu(u):
+ *   mu = mean r, v = mean r^2 - mu^2 (biased), rstd = 1 / sqrt(v + 1e-5), y = gamma rstd (r - mu) + beta (+ the residual or
+ *   the skip); the gradients go through mu and v: d beta = sum dY, d gamma = rstd (sum dY r - mu sum dY),
+ *   dR = A dY + C r + B with A = gamma rstd, C = -A rstd d gamma / M, B = -A d beta / M - C mu (formed in f64).
+ * Every layer needs M >= 2, i.e. n_env (S / 32)^2 >= 2: OCC_ERR_ARG otherwise (PyTorch raises there too).  The envs of a
+ * call are coupled through the statistics: feats and prob are not those of the running-statistics step.
+ *
+ * occ_fullnet_bn_train_forward additionally writes bn_stats (2 x 1248 floats): per layer in packed order (the 16 encoder
+ * layers, then the 5 decoder levels), mean[c] | var_biased[c], from which the caller moves its running statistics
+ * (running_var takes var_biased M / (M - 1)).  prob is 16-byte aligned.  After each conv / up kernel of the joint forward,
+ * which keeps r, three launches form the layer's statistics (f64 block partials per chunk of 4096 pixels, one wave per
+ * channel adds them), and y; the last down's also writes feats (a fixed-order f64 mean of y), the last level's runs the
+ * classifier and the sigmoid on the normalised y_4.  85 launches.
+ * Workspace, every part 256-byte aligned: the workspace of occ_fullnet_train_workspace_query |
+ *   coef: per layer in packed order s[c] | t[c] (f32; y = s r + t) | mu[c] | rstd[c] (f64): 24 x 1248 bytes |
+ *   abc: A[256] | B[256] | C[256] (f32) of the layer whose backward is in flight |
+ *   forward partials: the largest layer's c n_env ceil(H W / 4096) 2 doubles
+ *
+ * occ_fullnet_bn_backward is the backward of the LATEST occ_fullnet_bn_train_forward on ws.  Every activation step of
+ * occ_fullnet_backward / occ_sep_fullnet_backward becomes a sums pass that forms dY as that step does and stores only f64
+ * partials, a one-wave-per-channel kernel that writes d gamma, d beta (and the classifier's gradient) and A, B, C, and a pass
+ * that writes dU = [r > 0] dR and the partials of d bias; weight gradients, input gradients and the joins are those of the
+ * running-statistics step.  scratch: that of the joint step of the same form.  Both gradient buffers are OVERWRITTEN.  No
+ * floating-point atomics, every sum in a fixed order in f64: bn_stats and every gradient are bitwise the same from call to
+ * call.  146 launches (dense), 179 (separable) on `stream`, nothing allocated or synchronised.  OCC_ERR_ARG before any launch
+ * for an unsupported cfg or shape, a null pointer, a misaligned or a short buffer.
+ */
+int occ_fullnet_bn_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes, size_t* scratch_bytes);
+int occ_fullnet_bn_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                                 int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* bn_stats, void* stream);
+int occ_fullnet_bn_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env, void* ws,
+                            size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch, size_t scratch_bytes,
+                            float* grad_enc_packed, float* grad_dec_packed, void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

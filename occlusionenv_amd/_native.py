@@ -235,6 +235,12 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "occ_sep_fullnet_backward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "occ_fullnet_bn_train_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t),
+                                                      C.POINTER(C.c_size_t)]),
+    "occ_fullnet_bn_train_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "occ_fullnet_bn_backward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "occ_seg_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "occ_seg_criterion_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "occ_seg_criterion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -357,6 +357,20 @@ inline DwPlan bwd_dw_plan(int j, int H, int n) {
 
 inline int bwd_chunks(int plane) { return (plane + kBwdChunk - 1) / kBwdChunk; }
 
+// Batch-statistics BatchNorm of the joint training (occ_bn_train.hpp, included after occ_fullnet_bwd.hpp).  A walk that is
+// given a BnTrain runs bn_fwd_layer after each conv / up kernel and bn_bwd_act in place of each activation step.
+struct BnTrain;
+struct BnDy {
+    const float* dy;    // (n, c, plane), or with gf what is added to the pooled gradient (may be null)
+    const float* gf;    // the last down: d loss / d feats (n, c)
+    const float *gp, *prob, *y4, *clsw;  // the last decoder level: d loss / d prob, the kept prob, y_4 and cls_w
+};
+static void bn_fwd_layer(const BnTrain& bn, int layer, int c, int plane, int n, const float* gamma, const float* beta,
+                         const float* r, float* y, const float* add, float* feats, const float* cls, float* prob, float* pkeep,
+                         hipStream_t st);
+static void bn_bwd_act(const BnTrain& bn, int layer, int c, int plane, int n, const BnDy& src, float* du, const float* r,
+                       const float* gamma, float* gscale, float* gshift, float* gcls, char* scratch, hipStream_t st);
+
 // workspace of occ_segment_train_forward / occ_segment_backward: the workspace of occ_segment_forward (b0 | b1 | partials |
 // skips | last; b0 and b1 serve the encoder only), then per level j: y_j | r_j, then p, then the two gradient buffers
 // g0 (the size of y_4) and g1 (the size of y_3) that dY / dU of the levels alternate in.
@@ -411,8 +425,10 @@ inline TrainPtrs train_ptrs(const TrainWs& l, char* ws) {
     return t;
 }
 
-// The five up levels on t.last and t.skip, keeping y_j, r_j and p: 5 launches.
-static void dec_train_forward(int img, const float* dec_packed, int n, const TrainPtrs& t, float* prob, hipStream_t st) {
+// The five up levels on t.last and t.skip, keeping y_j, r_j and p: 5 launches.  bn: batch statistics (3 launches per level
+// more; the scale / shift slots carry gamma / beta).
+static void dec_train_forward(int img, const float* dec_packed, int n, const TrainPtrs& t, float* prob, hipStream_t st,
+                              const BnTrain* bn = nullptr) {
     const float* w = dec_packed;
     const float* cls = dec_packed + dec_packed_floats() - (kEncCh + 1);
     const float* x = t.last;
@@ -422,6 +438,11 @@ static void dec_train_forward(int img, const float* dec_packed, int n, const Tra
         const int c = kEncCh << lv;
         const bool last = j == kEncLevels - 1;
         dec_launch_up(x, t.y[j], t.skip[lv], w, 2 * c, c, H, n, last ? cls : nullptr, prob, t.p, st, t.r[j]);
+        if (bn) {
+            const float* gamma = w + 9LL * 2 * c * c + c;
+            bn_fwd_layer(*bn, 16 + j, c, 4 * H * H, n, gamma, gamma + c, t.r[j], t.y[j], t.skip[lv], nullptr, last ? cls : nullptr,
+                         prob, t.p, st);
+        }
         w += 9LL * 2 * c * c + 3LL * c;
         x = t.y[j];
         H *= 2;
@@ -486,9 +507,10 @@ struct DecJoin {
 // The backward of the latest forward on the tensors of t: per level, last first, the activation step (2 launches), the
 // weight gradient (2 launches) and, above level 0, the input gradient: 24 launches.  grad_packed is overwritten.  Without
 // join dY and dU alternate in t.g, dU written over dY.  With join the activation step is out of place and level 0 has an
-// input gradient too: 25 launches.
+// input gradient too: 25 launches.  bn: the forward ran with batch statistics; every activation step is bn_bwd_act (2
+// launches per level more).
 static void dec_backward(int img, const float* dec_packed, int n, const TrainPtrs& t, const float* grad_prob, char* scratch,
-                         float* grad_packed, hipStream_t st, const DecJoin* join = nullptr) {
+                         float* grad_packed, hipStream_t st, const DecJoin* join = nullptr, const BnTrain* bn = nullptr) {
     long long woff[kEncLevels];
     long long off = 0;
     for (int j = 0; j < kEncLevels; ++j) {
@@ -511,15 +533,20 @@ static void dec_backward(int img, const float* dec_packed, int n, const TrainPtr
         const float* x = j == 0 ? t.last : t.y[j - 1];
         const int chunks = bwd_chunks(plane);
         const dim3 agrid(chunks, c, n);
-        const BwdActDst dst = {{gbias + c, gbias + 2 * c, gbias, gcls, gcls + kEncCh}};
-        if (last)
+        const BwdActDst dst = bn ? BwdActDst{{gbias, nullptr, nullptr, nullptr, nullptr}}
+                                 : BwdActDst{{gbias + c, gbias + 2 * c, gbias, gcls, gcls + kEncCh}};
+        if (bn) {
+            const BnDy src = last ? BnDy{nullptr, nullptr, grad_prob, t.p, t.y[j], cls}
+                                  : BnDy{dy, nullptr, nullptr, nullptr, nullptr, nullptr};
+            bn_bwd_act(*bn, 16 + j, c, plane, n, src, g, t.r[j], w + 9LL * cin * c + c, gbias + c, gbias + 2 * c, gcls, scratch, st);
+        } else if (last)
             hipLaunchKernelGGL((occ_dec_bwd_act_kernel<true>), agrid, dim3(256), 0, st, nullptr, g, t.r[j], w + 9LL * cin * c + c, c, plane,
                                grad_prob, t.p, t.y[j], cls, (double*)scratch);
         else
             hipLaunchKernelGGL((occ_dec_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, g, t.r[j], w + 9LL * cin * c + c, c, plane,
                                nullptr, nullptr, nullptr, nullptr, (double*)scratch);
         const DwPlan p = bwd_dw_plan(j, H, n);
-        bwd_layer_tail(p, 9 * cin * c, c, n * chunks, last ? 5 : 3, dst, scratch, gw, st,
+        bwd_layer_tail(p, 9 * cin * c, c, n * chunks, bn ? 1 : last ? 5 : 3, dst, scratch, gw, st,
                        [&](float* part) { dec_launch_dw(p, x, g, part, cin, c, H, st); });
         if (j > 0 || join)  // into the dY of level j - 1
             dec_launch_dx(g, !join ? t.g[(kEncLevels - j) % 2] : j > 0 ? join->dskip[lv + 1] : join->dlast, w, cin, c, H, n, st);

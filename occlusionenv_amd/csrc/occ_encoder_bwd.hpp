@@ -366,7 +366,8 @@ struct EncTrainWs {
 // The separable stride-1 layer's backward (occ_sepenc_bwd.hpp, included after this file).
 inline DwPlan sep_dpw_plan(int cin, int cout, int H, int n);
 static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* grad_packed, int n, const float* x, const float* r,
-                          const float* dy, float* du, float* dh, float* dx, const float* add, char* scratch, hipStream_t st);
+                          const float* dy, float* du, float* dh, float* dx, const float* add, char* scratch, hipStream_t st,
+                          const BnTrain* bn = nullptr, int index = 0);
 
 // The workspace is the same for both forms (the same tensors are kept); the scratch is the largest of every layer's
 // activation partials, weight gradient partials (dense or, a separable layer, pointwise) and, a separable layer, G partials.
@@ -417,8 +418,10 @@ inline EncTrainWs enc_train_ws_layout(int img, int n, bool separable) {
 // The encoder, dense (dil = 1) or separable, on n envs with everything kept: 18 launches (copy, 16 layers through the
 // launchers of occ_encoder.hpp with a place for r, pool).
 // last_y: where the last down also stores its output (n, 256, H_5, H_5), or null.
+// bn (with last_y): batch statistics (occ_bn_train.hpp): every layer's y and feats come from bn_fwd_layer (3 launches per
+// layer more, no pool launch); the scale / shift slots of `packed` carry gamma / beta.
 static void enc_train_forward(int img, int dil, bool residual, bool separable, const float* packed, const float* obs, int n,
-                              char* ws, float* feats, hipStream_t st, float* last_y = nullptr) {
+                              char* ws, float* feats, hipStream_t st, float* last_y = nullptr, const BnTrain* bn = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n, separable);
     EncLayer L[16];
     enc_train_layers(img, separable, L);
@@ -431,6 +434,11 @@ static void enc_train_forward(int img, int dil, bool residual, bool separable, c
         const float* w = packed + Li.woff;
         if (separable && Li.stride == 1) enc_launch_sep(x, y, resid, w, Li.cin, Li.cout, Li.H, d, n, st, r);
         else enc_launch_dense(x, y, resid, w, Li.cin, Li.cout, Li.H, Li.stride, d, n, partials, st, false, r);
+        if (bn) {
+            const float* gamma = w + enc_layer_floats(Li.cin, Li.cout, separable && Li.stride == 1) - 2 * Li.cout;
+            bn_fwd_layer(*bn, (int)(&Li - L), Li.cout, Li.Ho * Li.Ho, n, gamma, gamma + Li.cout, r, y, resid,
+                         partials ? feats : nullptr, nullptr, nullptr, nullptr, st);
+        }
     };
     layer(L[0], 1, F(l.obs), F(l.a[0]), F(l.r_init), nullptr, nullptr);
     for (int lv = 0; lv < kEncLevels; ++lv) {
@@ -440,6 +448,7 @@ static void enc_train_forward(int img, int dil, bool residual, bool separable, c
         layer(Ll[1], dil, F(l.b[lv]), F(l.cc[lv]), F(l.r2[lv]), residual ? F(l.a[lv]) : nullptr, nullptr);
         layer(Ll[2], 1, F(l.cc[lv]), last ? last_y : F(l.a[lv + 1]), F(l.rd[lv]), nullptr, last ? F(l.part) : nullptr);
     }
+    if (bn) return;
     const int Hl = L[15].Ho;
     hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, F(l.part), enc_tiles(Hl), (float)(Hl * Hl), feats);
 }
@@ -495,24 +504,29 @@ static void enc_launch_dx2(const float* du, float* dx, const float* w, const Enc
 }
 
 // One layer's parameter gradients from its dY (or, pool, from grad_feats and, when not null, dy): dU is left in `du`.
-// 4 launches.
+// 4 launches.  bn: the forward ran with batch statistics; the activation step is bn_bwd_act for layer `index` (6 launches).
 static void enc_bwd_layer(const EncLayer& L, const float* packed, float* grad_packed, int n, const float* x, const float* r,
-                          const float* dy, float* du, const float* gf, char* scratch, hipStream_t st) {
+                          const float* dy, float* du, const float* gf, char* scratch, hipStream_t st, const BnTrain* bn = nullptr,
+                          int index = 0) {
     const int plane = L.Ho * L.Ho, chunks = bwd_chunks(plane);
     const float* w = packed + L.woff;
     float* gw = grad_packed + L.woff;
     float* gbias = gw + 9LL * L.cin * L.cout;
     const float* bns = w + 9LL * L.cin * L.cout + L.cout;
     const dim3 agrid(chunks, L.cout, n);
-    if (gf)
+    if (bn)
+        bn_bwd_act(*bn, index, L.cout, plane, n, BnDy{dy, gf, nullptr, nullptr, nullptr, nullptr}, du, r, bns, gbias + L.cout,
+                   gbias + 2 * L.cout, nullptr, scratch, st);
+    else if (gf)
         hipLaunchKernelGGL((occ_enc_bwd_act_kernel<true>), agrid, dim3(256), 0, st, dy, du, r, bns, L.cout, plane, gf,
                            (float)plane, (double*)scratch);
     else
         hipLaunchKernelGGL((occ_enc_bwd_act_kernel<false>), agrid, dim3(256), 0, st, dy, du, r, bns, L.cout, plane, nullptr, 1.f,
                            (double*)scratch);
-    const BwdActDst dst = {{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
+    const BwdActDst dst = bn ? BwdActDst{{gbias, nullptr, nullptr, nullptr, nullptr}}
+                             : BwdActDst{{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
     const DwPlan p = enc_dw_plan(L.cin, L.cout, L.Ho, n);
-    bwd_layer_tail(p, 9 * L.cin * L.cout, L.cout, n * chunks, 3, dst, scratch, gw, st, [&](float* part) { enc_launch_dw(p, x, du, part, L, st); });
+    bwd_layer_tail(p, 9 * L.cin * L.cout, L.cout, n * chunks, bn ? 1 : 3, dst, scratch, gw, st, [&](float* part) { enc_launch_dw(p, x, du, part, L, st); });
 }
 
 // join (occ_fullnet_bwd.hpp): the decoder's gradients that meet the encoder's, in the dense downs of either form: dlast
@@ -548,7 +562,8 @@ inline EncBwdBufs enc_bwd_bufs(bool separable, EncBwdRole role, float* gA, float
 // The backward of the latest enc_train_forward of the same form on this workspace, the deepest layer first: 79 launches
 // (dense), 112 (separable).  grad_packed is overwritten.
 static void enc_backward(int img, int dil, bool residual, bool separable, const float* packed, int n, char* ws,
-                         const float* grad_feats, char* scratch, float* grad_packed, hipStream_t st, const EncJoin* join = nullptr) {
+                         const float* grad_feats, char* scratch, float* grad_packed, hipStream_t st, const EncJoin* join = nullptr,
+                         const BnTrain* bn = nullptr) {
     const EncTrainWs l = enc_train_ws_layout(img, n, separable);
     EncLayer L[16];
     enc_train_layers(img, separable, L);
@@ -558,9 +573,9 @@ static void enc_backward(int img, int dil, bool residual, bool separable, const 
     auto layer = [&](const EncLayer& Li, int d, EncBwdRole role, const float* x, const float* r, const float* add) {
         const EncBwdBufs b = enc_bwd_bufs(separable, role, gA, gB, gC);
         if (separable) {
-            sep_bwd_layer(Li, d, packed, grad_packed, n, x, r, b.dy, b.du, b.dh, b.dx, add, scratch, st);
+            sep_bwd_layer(Li, d, packed, grad_packed, n, x, r, b.dy, b.du, b.dh, b.dx, add, scratch, st, bn, (int)(&Li - L));
         } else {
-            enc_bwd_layer(Li, packed, grad_packed, n, x, r, b.dy, b.du, nullptr, scratch, st);
+            enc_bwd_layer(Li, packed, grad_packed, n, x, r, b.dy, b.du, nullptr, scratch, st, bn, (int)(&Li - L));
             if (b.dx) enc_launch_dx1(b.du, b.dx, add, packed + Li.woff, Li, n, st);
         }
     };
@@ -568,7 +583,7 @@ static void enc_backward(int img, int dil, bool residual, bool separable, const 
         const EncLayer* Ll = L + 1 + 3 * lv;
         const bool last = lv == kEncLevels - 1;
         enc_bwd_layer(Ll[2], packed, grad_packed, n, F(l.cc[lv]), F(l.rd[lv]), last ? (join ? join->dlast : nullptr) : gA, gA,
-                      last ? grad_feats : nullptr, scratch, st);
+                      last ? grad_feats : nullptr, scratch, st, bn, 3 + 3 * lv);
         enc_launch_dx2(gA, gB, packed + Ll[2].woff, Ll[2], n, st, join ? &join->skip[lv] : nullptr);
         layer(Ll[1], dil, kBwdLayer2, F(l.b[lv]), F(l.r2[lv]), nullptr);
         layer(Ll[0], dil, kBwdLayer1, F(l.a[lv]), F(l.r1[lv]), residual ? gB : nullptr);

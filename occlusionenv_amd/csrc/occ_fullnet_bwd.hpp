@@ -32,6 +32,9 @@
 //   last (n,256,S/32,S/32) | per decoder level j = 0..4: y_j | r_j (n, 128 >> j, S/16 << j, S/16 << j) | p (n,S,S) |
 //   dlast (n,256,S/32,S/32) | dskip[lv], lv = 1..4 (n, 8 << lv, S >> lv, S >> lv)
 // g0 holds the decoder's dU.  Scratch: the larger of the two backward passes' scratch (the encoder's depends on its form).
+//
+// Both passes take an optional BnTrain (occ_bn_train.hpp): BatchNorm on the batch's statistics instead of the folded running
+// ones, on a workspace with three more parts; null leaves every launch as it is.
 
 struct FullTrainWs {
     EncTrainWs enc;
@@ -76,20 +79,21 @@ inline TrainPtrs full_train_ptrs(const FullTrainWs& l, char* ws) {
     return t;
 }
 
-// 23 launches.
+// 23 launches.  bn: batch-statistics BatchNorm (occ_bn_train.hpp), which both passes take.
 static void full_train_forward(int img, int dil, bool residual, bool separable, const float* enc_packed, const float* dec_packed,
-                               const float* obs, int n, char* ws, float* feats, float* prob, hipStream_t st) {
+                               const float* obs, int n, char* ws, float* feats, float* prob, hipStream_t st,
+                               const BnTrain* bn = nullptr) {
     const FullTrainWs l = full_train_ws_layout(img, n, separable);
     const TrainPtrs t = full_train_ptrs(l, ws);
-    enc_train_forward(img, dil, residual, separable, enc_packed, obs, n, ws, feats, st, t.last);
-    dec_train_forward(img, dec_packed, n, t, prob, st);
+    enc_train_forward(img, dil, residual, separable, enc_packed, obs, n, ws, feats, st, t.last, bn);
+    dec_train_forward(img, dec_packed, n, t, prob, st, bn);
 }
 
 // The backward of the latest full_train_forward of the same form on this workspace: 104 launches (dense), 137
 // (separable).  Both gradient buffers are overwritten.
 static void full_backward(int img, int dil, bool residual, bool separable, const float* enc_packed, const float* dec_packed, int n,
                           char* ws, const float* grad_feats, const float* grad_prob, char* scratch, float* grad_enc,
-                          float* grad_dec, hipStream_t st) {
+                          float* grad_dec, hipStream_t st, const BnTrain* bn = nullptr) {
     const FullTrainWs l = full_train_ws_layout(img, n, separable);
     const TrainPtrs t = full_train_ptrs(l, ws);
     DecJoin dj;
@@ -97,11 +101,11 @@ static void full_backward(int img, int dil, bool residual, bool separable, const
     dj.dskip[0] = nullptr;
     for (int lv = 1; lv < kEncLevels; ++lv) dj.dskip[lv] = (float*)(ws + l.dskip[lv]);
     dj.du = (float*)(ws + l.enc.g[0]);
-    dec_backward(img, dec_packed, n, t, grad_prob, scratch, grad_dec, st, &dj);
+    dec_backward(img, dec_packed, n, t, grad_prob, scratch, grad_dec, st, &dj, bn);
 
     EncJoin ej;
     ej.dlast = dj.dlast;
     ej.skip[0] = {nullptr, grad_prob, t.p, dec_packed + dec_packed_floats() - (kEncCh + 1)};
     for (int lv = 1; lv < kEncLevels; ++lv) ej.skip[lv] = {dj.dskip[lv], nullptr, nullptr, nullptr};
-    enc_backward(img, dil, residual, separable, enc_packed, n, ws, grad_feats, scratch, grad_enc, st, &ej);
+    enc_backward(img, dil, residual, separable, enc_packed, n, ws, grad_feats, scratch, grad_enc, st, &ej, bn);
 }

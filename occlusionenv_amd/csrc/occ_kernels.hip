@@ -41,6 +41,9 @@
 //   occ_sep_bwd_*       the dense and the separable encoder, per layer the activation step, weight and input gradients;
 //                       the separable layer's own backward kernels (occ_sepenc_bwd.hpp); the joint step with the decoder
 //                       (occ_fullnet_bwd.hpp), one for both encoder forms, has host code only
+//   occ_bn_*            batch-statistics BatchNorm for that joint step (occ_bn_train.hpp): per layer the statistics and y
+//                       after the conv kernel, and a sums pass, a per-channel kernel and an act pass in place of the
+//                       activation step
 //   occ_seg_criterion_* the pretrainer's criterion on that map (occ_criterion.hpp): Dice / BCE sums and the counts in one
 //                       read, fixed-order f64 sums, and the gradient with respect to the prediction
 //
@@ -72,6 +75,7 @@ namespace occ {
 #include "occ_encoder_bwd.hpp"
 #include "occ_sepenc_bwd.hpp"
 #include "occ_fullnet_bwd.hpp"
+#include "occ_bn_train.hpp"
 #include "occ_criterion.hpp"
 
 }  // namespace occ
@@ -860,6 +864,50 @@ extern "C" int occ_sep_fullnet_backward(const OccEncoderConfig* cfg, const float
                                         size_t scratch_bytes, float* grad_enc_packed, float* grad_dec_packed, void* stream) {
     return full_train_bwd(sep_full_train_cfg_ok, true, cfg, enc_packed, dec_packed, n_env, ws, ws_bytes, grad_feats, grad_prob,
                           scratch, scratch_bytes, grad_enc_packed, grad_dec_packed, stream);
+}
+
+// ---- joint training with batch-statistics BatchNorm (occ_bn_train.hpp): one entry point for both encoder forms ----------
+static bool full_bn_cfg_ok(const OccEncoderConfig* c, int n_env) {
+    if (!c) return false;
+    return (c->separable ? sep_full_train_cfg_ok(c, n_env) : full_train_cfg_ok(c, n_env)) && bn_train_shape_ok(c->img, n_env);
+}
+
+extern "C" int occ_fullnet_bn_train_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* ws_bytes,
+                                                    size_t* scratch_bytes) {
+    if (!full_bn_cfg_ok(cfg, n_env) || !non_null(ws_bytes, scratch_bytes)) return OCC_ERR_ARG;
+    const FullBnTrainWs l = full_bn_train_ws_layout(cfg->img, n_env, cfg->separable != 0);
+    *ws_bytes = l.total;
+    *scratch_bytes = l.full.scratch;
+    return OCC_OK;
+}
+
+extern "C" int occ_fullnet_bn_train_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
+                                            const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
+                                            float* bn_stats, void* stream) {
+    if (!full_bn_cfg_ok(cfg, n_env) || !non_null(enc_packed, dec_packed, obs, ws, feats, prob, bn_stats)) return OCC_ERR_ARG;
+    if (!aligned(16, ws, prob) || !aligned(4, enc_packed, dec_packed, obs, feats, bn_stats)) return OCC_ERR_ARG;
+    const FullBnTrainWs l = full_bn_train_ws_layout(cfg->img, n_env, cfg->separable != 0);
+    if (ws_bytes < l.total) return OCC_ERR_ARG;
+    const BnTrain bn = full_bn_ptrs(l, (char*)ws, bn_stats);
+    full_train_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, obs, n_env,
+                       (char*)ws, feats, prob, (hipStream_t)stream, &bn);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_fullnet_bn_backward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, int n_env,
+                                       void* ws, size_t ws_bytes, const float* grad_feats, const float* grad_prob, void* scratch,
+                                       size_t scratch_bytes, float* grad_enc_packed, float* grad_dec_packed, void* stream) {
+    if (!full_bn_cfg_ok(cfg, n_env) ||
+        !non_null(enc_packed, dec_packed, ws, grad_feats, grad_prob, scratch, grad_enc_packed, grad_dec_packed))
+        return OCC_ERR_ARG;
+    if (!aligned(16, ws, scratch, grad_prob) || !aligned(4, enc_packed, dec_packed, grad_feats, grad_enc_packed, grad_dec_packed))
+        return OCC_ERR_ARG;
+    const FullBnTrainWs l = full_bn_train_ws_layout(cfg->img, n_env, cfg->separable != 0);
+    if (ws_bytes < l.total || scratch_bytes < l.full.scratch) return OCC_ERR_ARG;
+    const BnTrain bn = full_bn_ptrs(l, (char*)ws, nullptr);
+    full_backward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, n_env, (char*)ws,
+                  grad_feats, grad_prob, (char*)scratch, grad_enc_packed, grad_dec_packed, (hipStream_t)stream, &bn);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 
 extern "C" int occ_seg_metrics(const float* pred, const float* target, int target_stride, int n_env, int img, int64_t* counts,

@@ -270,9 +270,11 @@ static void sep_launch_dpw(const DwPlan& p, const float* x, const float* du, con
 }
 
 // One separable layer's parameter gradients and, when dx is not null, its input gradient (+ add) from its dY: dU goes to
-// `du` (may be dy itself), dH to `dh`; dx may be du.  8 launches (7 without dx).
+// `du` (may be dy itself), dH to `dh`; dx may be du.  8 launches (7 without dx).  bn: the forward ran with batch
+// statistics; the activation step is bn_bwd_act for layer `index` (2 launches more).
 static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* grad_packed, int n, const float* x, const float* r,
-                          const float* dy, float* du, float* dh, float* dx, const float* add, char* scratch, hipStream_t st) {
+                          const float* dy, float* du, float* dh, float* dx, const float* add, char* scratch, hipStream_t st,
+                          const BnTrain* bn, int index) {
     const int plane = L.H * L.H, chunks = bwd_chunks(plane);
     const float* w = packed + L.woff;
     float* gw = grad_packed + L.woff;
@@ -280,11 +282,16 @@ static void sep_bwd_layer(const EncLayer& L, int d, const float* packed, float* 
     float* gpw = gw + 6 * L.cin;
     float* gbias = gpw + (long long)L.cin * L.cout;
     const float* bns = pw + (long long)L.cin * L.cout + L.cout;
-    hipLaunchKernelGGL((occ_enc_bwd_act_kernel<false>), dim3(chunks, L.cout, n), dim3(256), 0, st, dy, du, r, bns, L.cout, plane,
-                       nullptr, 1.f, (double*)scratch);
-    const BwdActDst dst = {{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
+    if (bn)
+        bn_bwd_act(*bn, index, L.cout, plane, n, BnDy{dy, nullptr, nullptr, nullptr, nullptr, nullptr}, du, r, bns, gbias + L.cout,
+                   gbias + 2 * L.cout, nullptr, scratch, st);
+    else
+        hipLaunchKernelGGL((occ_enc_bwd_act_kernel<false>), dim3(chunks, L.cout, n), dim3(256), 0, st, dy, du, r, bns, L.cout,
+                           plane, nullptr, 1.f, (double*)scratch);
+    const BwdActDst dst = bn ? BwdActDst{{gbias, nullptr, nullptr, nullptr, nullptr}}
+                             : BwdActDst{{gbias + L.cout, gbias + 2 * L.cout, gbias, nullptr, nullptr}};
     const DwPlan p = sep_dpw_plan(L.cin, L.cout, L.H, n);
-    bwd_layer_tail(p, L.cin * L.cout, L.cout, n * chunks, 3, dst, scratch, gpw, st,
+    bwd_layer_tail(p, L.cin * L.cout, L.cout, n * chunks, bn ? 1 : 3, dst, scratch, gpw, st,
                    [&](float* part) { sep_launch_dpw(p, x, du, w, part, L, d, st); });
     const int pblocks = (plane + 255) / 256;
     if (L.cin == 4)

@@ -18,10 +18,21 @@ decoder feature left out, ``(None, segm)``.  ``net.features_and_map(obs)`` is th
 The parameters sit under the checkpoint's keys, so ``net.state_dict()`` drops back into the checkpoint it came from and
 ``enc.with_state(net.state_dict())`` (``with_encoder(sd).with_decoder(sd)``) is the trained network for inference.
 
+BatchNorm: by default it keeps its running statistics (buffers here) in all 21 layers and only its affine parameters
+train, a deviation from pretrainer.py, which trains in train mode.  ``from_encoder(enc, batch_stats=True)`` is the
+reference's train mode (csrc/occ_bn_train.hpp, ``occ_fullnet_bn_*``): while ``net.training`` every layer normalises with
+the mean and the biased variance of the batch, the gradients go through those statistics, and the running buffers move as
+``nn.BatchNorm2d`` moves them (momentum 0.1, unbiased variance; ``num_batches_tracked`` is not kept), so
+``enc.with_state(net.state_dict())`` runs inference on learned statistics.  The envs of a batch are then coupled, feats and
+prob are no longer those of ``enc`` and every layer needs two values per channel: ``N (S / 32)^2 >= 2``, else ``ValueError``
+as in PyTorch.  After ``net.eval()`` the step is the running-statistics one, bit for bit.  Against an f64 model of the
+network in train mode, evaluated with the step's own ReLU gates, the gradients were within 3.3e-5 of each tensor's largest
+element on an MI355X (the tests' bar: max(1e-4, 4 e32) <= 4e-4, e32 being the error of PyTorch's own f32 run of the case;
+tests/test_gpu_bn_train.py).
+
 Limits: dense 3x3 convs only (a separable checkpoint raises) at dilation 1, the pretrainer's default configuration; S a
-multiple of 32.  Deviation from pretrainer.py, which trains in train mode: BatchNorm keeps its running statistics (buffers
-here) in all 21 layers; only its affine parameters train.  A training call is one chunk (``N <= enc.max_chunk``), and the
-kept activations belong to the latest forward: a backward of an earlier forward raises.
+multiple of 32.  A training call is one chunk (``N <= enc.max_chunk``), and the kept activations belong to the latest
+forward: a backward of an earlier forward raises.
 
 The host path (fold, packed layouts, parameters under the checkpoint's keys, workspace, the autograd function) is
 ``nettrain.TrainableNet``'s on two parts, the encoder's and the decoder's; here are the guards, the native symbols and the
@@ -42,11 +53,18 @@ class JointNet(TrainableNet):
     networks share.  A subclass checks its checkpoint and names its encoder part and its native symbols."""
 
     RETURNS = DIFFERENTIABLE = ("feats", "prob")
+    BN_SYMBOLS = ("occ_fullnet_bn_train_workspace_query", "occ_fullnet_bn_train_forward", "occ_fullnet_bn_backward")
 
-    def __init__(self, enc: FrozenEncoder, enc_part):
+    def __init__(self, enc: FrozenEncoder, enc_part, batch_stats: bool = False):
         super().__init__(enc, [enc_part, decoder_part(enc.preset)], {**enc.encoder_state, **enc.decoder_state})
+        self.batch_stats = bool(batch_stats)
         self.grad_prefix = PRESETS[enc.preset][1]
         self.has_grad_head = self.grad_prefix is not None and self.grad_prefix + "weight" in enc.encoder_state
+
+    @classmethod
+    def from_encoder(cls, enc: FrozenEncoder, batch_stats: bool = False):
+        """``batch_stats``: BatchNorm in train mode while ``net.training`` (the module docstring of ``fullnet``)."""
+        return cls(enc, batch_stats=batch_stats)
 
     def features_and_map(self, obs: torch.Tensor):
         """(pooled (N,256), segm (N,1,S,S)) f32 of the network with its current parameters, both differentiable."""
@@ -70,7 +88,7 @@ class TrainableFullNetwork(JointNet):
 
     SYMBOLS = ("occ_fullnet_train_workspace_query", "occ_fullnet_train_forward", "occ_fullnet_backward")
 
-    def __init__(self, enc: FrozenEncoder):
+    def __init__(self, enc: FrozenEncoder, batch_stats: bool = False):
         if not isinstance(enc, FrozenEncoder):
             raise ValueError("TrainableFullNetwork needs a FrozenEncoder")
         if enc.preset not in DECODER_KEYS:
@@ -83,4 +101,4 @@ class TrainableFullNetwork(JointNet):
             raise ValueError("this checkpoint has no segmentation decoder (no 'segmenter.0.features.*' / 'decoder.features.*' keys)")
         if enc.encoder_state is None:
             raise ValueError("this FrozenEncoder keeps no unfolded encoder tensors (build it with from_state_dict)")
-        super().__init__(enc, encoder_part(enc.preset))
+        super().__init__(enc, encoder_part(enc.preset), batch_stats)

@@ -17,7 +17,9 @@
     IoU as the means of the per-batch values.
   * ``pretrain_epoch`` -- pretrainer.py:112-159 (``train``) on a stored dataset: the summed segmentation and gradient loss
     back-propagated through decoder, skips and encoder at once (``fullnet.TrainableFullNetwork``, or
-    ``sepfullnet.TrainableSeparableFullNetwork`` for the separable network the agent runs), AdamW.
+    ``sepfullnet.TrainableSeparableFullNetwork`` for the separable network the agent runs), AdamW.  ``batch_stats=True``:
+    BatchNorm in train mode as in the reference (batch statistics, running averages updated); the default keeps the running
+    statistics.
 """
 from __future__ import annotations
 
@@ -196,7 +198,7 @@ def train_predictor(venv, enc_or_net, steps: int, lr: float = 1e-4, weight_decay
 
 
 def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = False, lr: float = 1e-3, weight_decay: float = 1e-5,
-                   optimizer=None) -> dict:
+                   optimizer=None, batch_stats: bool = False) -> dict:
     """One epoch of ``PreTrainer.train()`` (pretrainer.py:112-159) on the device: ``batches`` is any iterable of
     ``(img, occlusion, grad, _)`` as for ``validate_pretrained``.  Every batch goes through ``net(img)``
     (``fullnet.TrainableFullNetwork`` or ``sepfullnet.TrainableSeparableFullNetwork``: one native forward of encoder, decoder
@@ -205,8 +207,9 @@ def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = Fa
     ``nn.SmoothL1Loss(beta=0.01)`` (``use_l1``) of the gradient prediction, runs ``backward`` (one native joint backward)
     and one ``torch.optim.AdamW`` step (pretrainer.py:91; ``optimizer``: one to carry over epochs, made here when None).
     ``net_or_enc``: a ``TrainableFullNetwork`` or a ``TrainableSeparableFullNetwork``, or a "ppo" ``FrozenEncoder`` with decoder
-    and grad head, from which the one for its form (dense or separable) is made.  BatchNorm keeps its running statistics
-    (``fullnet``).  Returned are ``net``, ``optimizer`` and the five numbers
+    and grad head, from which the one for its form (dense or separable) is made, with ``batch_stats`` passed on:
+    False, BatchNorm keeps its running statistics; True, it runs in train mode as the reference's does (``fullnet``), each
+    batch needing ``N (S / 32)^2 >= 2``.  A net that is passed in keeps its own setting.  Returned are ``net``, ``optimizer`` and the five numbers
     the reference prints, computed its way: ``loss``, ``segm_loss``, ``grad_loss`` = the mean over batches of the per-batch
     losses, ``accuracy`` and ``iou`` = the mean over batches of the per-batch ratios x 100 of the prediction the step learned
     from (``segmentation.seg_criterion``'s counts); also the pooled ``correct``, ``intersection``, ``union``, ``pixels``
@@ -218,9 +221,9 @@ def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = Fa
     if isinstance(net_or_enc, JointNet):
         net = net_or_enc
     elif getattr(net_or_enc, "separable", False):
-        net = TrainableSeparableFullNetwork.from_encoder(net_or_enc)
+        net = TrainableSeparableFullNetwork.from_encoder(net_or_enc, batch_stats=batch_stats)
     else:
-        net = TrainableFullNetwork.from_encoder(net_or_enc)
+        net = TrainableFullNetwork.from_encoder(net_or_enc, batch_stats=batch_stats)
     if not net.has_grad_head or net.enc.preset != "ppo":
         raise ValueError("pretrain_epoch needs a FullNetwork checkpoint (preset 'ppo') with its gradPredictor head")
     opt = optimizer if optimizer is not None else torch.optim.AdamW(net.parameters(), lr=lr, weight_decay=weight_decay)

@@ -6,8 +6,14 @@ and one ``torch.autograd.Function`` runs them all: forward folds the current
 BatchNorm parameters on the device in f64, packs every part in the library's layout and runs the native train forward;
 backward runs the native backward and maps each part's packed gradient back to the parameters.
 
-BatchNorm keeps its running statistics (buffers); only its affine parameters train.  A training call is one chunk
-(``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of an earlier forward raises.
+BatchNorm keeps its running statistics (buffers); only its affine parameters train.  The joint networks
+(``fullnet.JointNet``) also offer ``batch_stats=True``, ``nn.BatchNorm2d`` in train mode as pretrainer.py runs it: while
+``net.training`` the step packs gamma / beta unfolded, runs the ``occ_fullnet_bn_*`` entry points (csrc/occ_bn_train.hpp),
+which normalise every layer with the statistics of the batch and return d gamma / d beta themselves, and moves the running
+buffers towards the batch's mean and unbiased variance (momentum 0.1) without a host sync; every layer must see at least two
+values per channel, ``N (S / 32)^2 >= 2``.  After ``net.eval()`` the step is the running-statistics one, bit for bit.
+A training call is one chunk (``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of
+an earlier forward raises.
 """
 from __future__ import annotations
 
@@ -145,6 +151,19 @@ def align256(b: int) -> int:
     return (b + 255) & ~255
 
 
+BN_MOMENTUM = 0.1  # nn.BatchNorm2d's default, which the reference's layers keep
+
+
+def bn_layer_shapes(img: int):
+    """[(channels, pixels of one env's plane)] of the 21 BatchNorm layers of the joint network on side ``img``, in packed
+    order (16 encoder layers, 5 decoder levels): the layout of ``bn_stats`` (mean[c] | var_biased[c] per layer)."""
+    shapes, h = [], img
+    for _stem, _cin, cout, _sep, stride in layer_plan(False):
+        h = (h + stride - 1) // stride
+        shapes.append((cout, h * h))
+    return shapes + [(cout, ((img // 16) << j) ** 2) for j, _cin, cout in decoder_plan()]
+
+
 def register_under_key(module: torch.nn.Module, key: str, t: torch.Tensor, buffer: bool) -> None:
     """Register a copy of ``t`` on ``module`` under the dotted state-dict key, as a buffer or a parameter, creating the
     container modules on the way (the parameters of a ``TrainableNet`` sit under the checkpoint's keys)."""
@@ -213,6 +232,7 @@ class TrainableNet(torch.nn.Module):
     RETURNS: Tuple[str, ...]           # of "feats" (N,256) and "prob" (N,1,S,S), in the order of the step's outputs
     DIFFERENTIABLE: Tuple[str, ...]    # those the native backward takes a gradient for, in its argument order
     RUNS_DECODER = True                # the decoder needs S a multiple of 32
+    BN_SYMBOLS: Optional[Tuple[str, str, str]] = None  # the three for batch-statistics BatchNorm, where the step offers it
 
     def __init__(self, enc: FrozenEncoder, parts, state):
         super().__init__()
@@ -220,6 +240,7 @@ class TrainableNet(torch.nn.Module):
         self.parts = tuple(parts)
         for key, t in state.items():
             register_under_key(self, key, t.to(enc.device, torch.float32), buffer=key.endswith(("running_mean", "running_var")))
+        self.batch_stats = False  # True (JointNet): while self.training, BatchNorm runs on the batch's statistics
         self._version = 0
         self._latest = None
         self._bufs = {}
@@ -243,27 +264,32 @@ class TrainableNet(torch.nn.Module):
             names += part.tail
         return [(k, self.get_parameter(k)) for k in names]
 
-    def _train_buffers(self, n: int, img: int):
-        """(workspace, scratch) of a training call on n envs of side img, kept per shape."""
-        key = (n, img)
+    def _bn_mode(self) -> bool:
+        """Whether the next step normalises with batch statistics."""
+        return bool(self.batch_stats and self.training)
+
+    def _train_buffers(self, n: int, img: int, bn: bool = False):
+        """(workspace, scratch) of a training call on n envs of side img, kept per shape and BatchNorm mode."""
+        key = (n, img, bn)
         if key not in self._bufs:
             wsb, scb = C.c_size_t(), C.c_size_t()
-            query = self.SYMBOLS[0]
+            query = (self.BN_SYMBOLS if bn else self.SYMBOLS)[0]
             nat.check(getattr(nat.load(), query)(C.byref(self._cfg(img)), n, C.byref(wsb), C.byref(scb)), query)
             dev = self.enc.device
             self._bufs[key] = (torch.empty(int(wsb.value), dtype=torch.uint8, device=dev),
                                torch.empty(max(int(scb.value), 16), dtype=torch.uint8, device=dev))
         return self._bufs[key]
 
-    def _native_forward(self, img, packed, obs, n, ws, outs):
-        """The native train forward on the packed parts; ``outs``: feats and, when the step has one, prob."""
-        name = self.SYMBOLS[1]
+    def _native_forward(self, img, packed, obs, n, ws, outs, bn: bool = False):
+        """The native train forward on the packed parts; ``outs``: feats and, when the step has one, prob (``bn``: and
+        bn_stats)."""
+        name = (self.BN_SYMBOLS if bn else self.SYMBOLS)[1]
         nat.check(getattr(nat.load(), name)(C.byref(self._cfg(img)), *[nat.ptr(p) for p in packed], nat.ptr(obs), n, nat.ptr(ws),
                                             ws.numel(), *[nat.ptr(o) for o in outs], nat.stream_ptr(obs.device)), name)
 
-    def _native_backward(self, img, packed, n, ws, grads_in, scratch, grads_out):
+    def _native_backward(self, img, packed, n, ws, grads_in, scratch, grads_out, bn: bool = False):
         """The native backward of the latest forward: upstream ``grads_in`` -> one packed gradient per part."""
-        name = self.SYMBOLS[2]
+        name = (self.BN_SYMBOLS if bn else self.SYMBOLS)[2]
         nat.check(getattr(nat.load(), name)(C.byref(self._cfg(img)), *[nat.ptr(p) for p in packed], n, nat.ptr(ws), ws.numel(),
                                             *[nat.ptr(g) for g in grads_in], nat.ptr(scratch), scratch.numel(),
                                             *[nat.ptr(g) for g in grads_out], nat.stream_ptr(grads_in[0].device)), name)
@@ -276,8 +302,29 @@ class TrainableNet(torch.nn.Module):
             raise ValueError(f"a training call is one chunk: N = {n} > max_chunk = {self.enc.max_chunk}")
         if n < 1:
             raise ValueError("a training call needs at least one env")
+        if self._bn_mode() and n * (int(obs.shape[2]) // 32) ** 2 < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(obs.shape)}: the "
+                             "deepest BatchNorm sees N (S / 32)^2 values")
         obs = obs.detach().to(torch.float32).contiguous()
         return _NetStep.apply(obs, self, *[p for _k, p in self.ordered_parameters()])
+
+
+def _update_running_stats(net, stats: torch.Tensor, n: int, img: int) -> None:
+    """nn.BatchNorm2d's running-average rule on every layer of ``net`` from the forward's ``bn_stats``: the mean, and the
+    biased variance made unbiased by M / (M - 1).  In place, on the device, no host sync."""
+    stems = [stem for part in net.parts for stem in part.stems]
+    means, variances, unbias, off = [], [], [], 0
+    for c, plane in bn_layer_shapes(img):
+        m = n * plane
+        means.append(stats[off:off + c])
+        variances.append(stats[off + c:off + 2 * c])
+        unbias.append(BN_MOMENTUM * m / (m - 1))
+        off += 2 * c
+    running_mean, running_var = zip(*[net._stats(stem) for stem in stems])
+    with torch.no_grad():
+        torch._foreach_mul_(list(running_mean) + list(running_var), 1.0 - BN_MOMENTUM)
+        torch._foreach_add_(list(running_mean), means, alpha=BN_MOMENTUM)
+        torch._foreach_add_(list(running_var), torch._foreach_mul(variances, unbias))
 
 
 class _NetStep(torch.autograd.Function):
@@ -286,26 +333,36 @@ class _NetStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs, net, *params):
+        bn = net._bn_mode()
         folded, at = [], 0
         for part in net.parts:
             layers = []
             for stem, leaves in zip(part.stems, part.layer_leaves()):
                 *conv, gamma, beta = params[at:at + len(leaves)]
-                scale, shift, _rstd = fold_bn_vectors(gamma, beta, *net._stats(stem))
+                if bn:  # the kernels form scale and shift from the batch's statistics
+                    scale, shift = gamma, beta
+                else:
+                    scale, shift, _rstd = fold_bn_vectors(gamma, beta, *net._stats(stem))
                 layers.append((*conv, scale, shift))
                 at += len(leaves)
             folded.append((layers, params[at:at + len(part.tail)]))
             at += len(part.tail)
         packed = [part.pack(layers, tail).contiguous() for part, (layers, tail) in zip(net.parts, folded)]
         n, img = int(obs.shape[0]), int(obs.shape[2])
-        ws, _scratch = net._train_buffers(n, img)
+        ws, _scratch = net._train_buffers(n, img, bn)
         out = {"feats": torch.empty(n, FEATURES, dtype=torch.float32, device=obs.device)}
         if "prob" in net.RETURNS:
             out["prob"] = torch.empty(n, 1, img, img, dtype=torch.float32, device=obs.device)
         net._version += 1
         net._latest = (n, img)
-        net._native_forward(img, packed, obs, n, ws, list(out.values()))
-        ctx.net, ctx.packed, ctx.version, ctx.shape = net, packed, net._version, (n, img)
+        if bn:
+            stats = torch.empty(2 * sum(c for c, _plane in bn_layer_shapes(img)), dtype=torch.float32, device=obs.device)
+            net._native_forward(img, packed, obs, n, ws, list(out.values()) + [stats], bn=True)
+            _update_running_stats(net, stats, n, img)
+            net.bn_stats = stats  # of the latest train-mode forward: mean[c] | var_biased[c] per layer, packed order
+        else:
+            net._native_forward(img, packed, obs, n, ws, list(out.values()))
+        ctx.net, ctx.packed, ctx.version, ctx.shape, ctx.bn = net, packed, net._version, (n, img), bn
         if len(net.DIFFERENTIABLE) < len(net.RETURNS):
             ctx.mark_non_differentiable(*[out[k] for k in net.RETURNS if k not in net.DIFFERENTIABLE])
         return out[net.RETURNS[0]] if len(net.RETURNS) == 1 else tuple(out[k] for k in net.RETURNS)
@@ -317,16 +374,17 @@ class _NetStep(torch.autograd.Function):
             raise RuntimeError(f"{type(net).__name__}: backward of a forward that a later forward has superseded; the kept "
                                "activations belong to the latest forward (call backward before the next forward)")
         n, img = ctx.shape
-        ws, scratch = net._train_buffers(n, img)
+        ws, scratch = net._train_buffers(n, img, ctx.bn)
         upstream = dict(zip(net.RETURNS, grads))
         grads_in = [upstream[k].to(torch.float32).contiguous() for k in net.DIFFERENTIABLE]
         grads_out = [torch.empty(part.floats, dtype=torch.float32, device=grads_in[0].device) for part in net.parts]
-        net._native_backward(img, ctx.packed, n, ws, grads_in, scratch, grads_out)
+        net._native_backward(img, ctx.packed, n, ws, grads_in, scratch, grads_out, bn=ctx.bn)
         result = [None, None]
         for part, gp in zip(net.parts, grads_out):
             layers, tail = part.unpack(gp)
             for stem, (*dconv, dscale, dshift) in zip(part.stems, layers):
-                dgamma, dbeta = bn_param_grads(dscale, dshift, *net._stats(stem))
+                # batch statistics: the slots hold d gamma / d beta themselves
+                dgamma, dbeta = (dscale.clone(), dshift.clone()) if ctx.bn else bn_param_grads(dscale, dshift, *net._stats(stem))
                 result += [t.clone(memory_format=torch.contiguous_format) for t in dconv]
                 result += [dgamma.to(torch.float32), dbeta.to(torch.float32)]
             result += [t.clone() for t in tail]

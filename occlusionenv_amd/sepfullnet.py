@@ -16,9 +16,14 @@ decoder's and the classifier's), so ``enc.with_state(net.state_dict())`` is the 
 ``BatchedPPO.from_fullnetwork(net.state_dict())`` the agent on it: the checkpoint's ``action_head`` / ``value_head``, which
 pretraining does not touch (the reference feeds them detached features), ride along as buffers when the checkpoint had them.
 
-Limits: S a multiple of 32.  Deviation from pretrainer.py, which trains in train mode: BatchNorm keeps its running
-statistics (buffers here) in all 21 layers; only its affine parameters train.  A training call is one chunk
-(``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of an earlier forward raises.
+BatchNorm: by default it keeps its running statistics (buffers here) in all 21 layers and only its affine parameters
+train, a deviation from pretrainer.py.  ``from_encoder(enc, batch_stats=True)`` is the reference's train mode, as in
+``fullnet``: batch statistics while ``net.training``, running buffers updated as ``nn.BatchNorm2d`` updates them,
+``N (S / 32)^2 >= 2``, and the running-statistics step bit for bit after ``net.eval()``.  This is how a fresh
+``FullNetwork(8, dilation=2, separable=True)`` is pretrained: its statistics are learned, not kept at mean 0, variance 1.
+
+Limits: S a multiple of 32.  A training call is one chunk (``N <= enc.max_chunk``), and the kept activations belong to the
+latest forward: a backward of an earlier forward raises.
 """
 from __future__ import annotations
 
@@ -35,7 +40,7 @@ class TrainableSeparableFullNetwork(JointNet):
 
     SYMBOLS = ("occ_sep_fullnet_train_workspace_query", "occ_sep_fullnet_train_forward", "occ_sep_fullnet_backward")
 
-    def __init__(self, enc: FrozenEncoder):
+    def __init__(self, enc: FrozenEncoder, batch_stats: bool = False):
         if not isinstance(enc, FrozenEncoder):
             raise ValueError("TrainableSeparableFullNetwork needs a FrozenEncoder")
         if enc.preset not in DECODER_KEYS:
@@ -47,7 +52,7 @@ class TrainableSeparableFullNetwork(JointNet):
             raise ValueError("this checkpoint has no segmentation decoder (no 'segmenter.0.features.*' / 'decoder.features.*' keys)")
         if enc.encoder_state is None:
             raise ValueError("this FrozenEncoder keeps no unfolded encoder tensors (build it with from_state_dict)")
-        super().__init__(enc, sep_encoder_part(enc.preset))
+        super().__init__(enc, sep_encoder_part(enc.preset), batch_stats)
         for name, (w, b) in enc.heads.items():  # not trained here: carried so that state_dict() is the agent's checkpoint
             register_under_key(self, name + ".weight", w.to(enc.device, torch.float32), buffer=True)
             register_under_key(self, name + ".bias", b.to(enc.device, torch.float32), buffer=True)

@@ -10,7 +10,10 @@ Shapes: 128 x 256^2 and 64 x 512^2, preset "ppo" at dilation 1 with the residual
 runs BatchNorm with its running statistics, as the native ones do.  Each sample is ``--calls`` steps between two HIP events;
 after ``--warmup`` samples of each path, ``--iters`` samples alternate between the three.  All samples are kept; medians are
 compared, with the larger of the min-max spreads of the two paths compared as the margin.  ``--native-only``: the native joint
-step alone, for a kernel trace.
+step alone, for a kernel trace.  ``--batch-stats``: BatchNorm in train mode instead (scripts/bn_step_bench.py): the native
+``batch_stats=True`` step against torch autograd in train mode and against the running-statistics step:
+
+    python scripts/fullnet_train_bench.py --batch-stats --out profiles/fullnet_bn_train_bench.json
 """
 import argparse
 import ctypes as C
@@ -24,6 +27,7 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 from occlusionenv_amd import _native as nat  # noqa: E402
 from occlusionenv_amd import segmentation  # noqa: E402
@@ -89,12 +93,17 @@ def split_step_fn(head, tenc, obs, occl, grad):
     return step
 
 
-def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only):
+def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only, batch_stats=False):
     base = make_obs(31, 8, img).float()
     obs = base[torch.arange(n) % 8].cuda()
     gen = torch.Generator().manual_seed(7)
     occl = (torch.rand(n, 1, img // 8, img // 8, generator=gen) > 0.5).float().repeat_interleave(8, 2).repeat_interleave(8, 3).cuda()
     grad = F.normalize(torch.randn(n, 2, generator=gen), dim=1).cuda()
+    if batch_stats:
+        import bn_step_bench
+
+        return bn_step_bench.run_shape(TrainableFullNetwork, "dense", lambda k: m.kind("ppo", k), sd32, enc, obs, occl, grad, warmup,
+                                       iters, calls, os.path.join(ROOT, "profiles", "fullnet_train_bench.json"))
     net = TrainableFullNetwork.from_encoder(enc)
     joint = native_step_fn(net, obs, occl, grad)
     wsb, scb = C.c_size_t(), C.c_size_t()
@@ -139,6 +148,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--calls", type=int, default=3, help="steps per timed sample")
     ap.add_argument("--native-only", action="store_true")
+    ap.add_argument("--batch-stats", action="store_true", help="time the train-mode BatchNorm step (scripts/bn_step_bench.py)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "fullnet_train_bench needs a GPU"
@@ -147,7 +157,7 @@ def main():
     shapes = []
     for s in args.shapes.split(","):
         n, img = (int(v) for v in s.split("x"))
-        r = run_shape(sd32, enc, n, img, args.warmup, args.iters, args.calls, args.native_only)
+        r = run_shape(sd32, enc, n, img, args.warmup, args.iters, args.calls, args.native_only, args.batch_stats)
         print(json.dumps({k: v for k, v in r.items() if not k.endswith("_all")}), flush=True)
         shapes.append(r)
         torch.cuda.empty_cache()

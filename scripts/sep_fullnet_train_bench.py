@@ -17,6 +17,11 @@ trace:
         python scripts/sep_fullnet_train_bench.py --native-only --warmup 1 --iters 3 --calls 1
     python scripts/sep_fullnet_train_bench.py --stats-from DIR/.../sepfull_kernel_stats.csv --stats-steps 4 \\
         --out profiles/sep_fullnet_train_kernel_stats.json
+
+``--batch-stats``: BatchNorm in train mode instead (scripts/bn_step_bench.py): the native ``batch_stats=True`` step against
+torch autograd in train mode and against the running-statistics step:
+
+    python scripts/sep_fullnet_train_bench.py --batch-stats --out profiles/sep_fullnet_bn_train_bench.json
 """
 import argparse
 import ctypes as C
@@ -85,7 +90,7 @@ def split_step_fn(head, tenc, obs, occl, grad):
     return step
 
 
-def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only):
+def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only, batch_stats=False):
     from occlusionenv_amd import _native as nat
     from occlusionenv_amd.seghead import SegmentationHead
     from occlusionenv_amd.sepfullnet import TrainableSeparableFullNetwork
@@ -96,6 +101,11 @@ def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only):
     gen = torch.Generator().manual_seed(7)
     occl = (torch.rand(n, 1, img // 8, img // 8, generator=gen) > 0.5).float().repeat_interleave(8, 2).repeat_interleave(8, 3).cuda()
     grad = F.normalize(torch.randn(n, 2, generator=gen), dim=1).cuda()
+    if batch_stats:
+        import bn_step_bench
+
+        return bn_step_bench.run_shape(TrainableSeparableFullNetwork, "separable", m.kind, sd32, enc, obs, occl, grad, warmup, iters,
+                                       calls, os.path.join(ROOT, "profiles", "sep_fullnet_train_bench.json"))
     net = TrainableSeparableFullNetwork.from_encoder(enc)
     joint = native_step_fn(net, obs, occl, grad)
     wsb, scb = C.c_size_t(), C.c_size_t()
@@ -143,6 +153,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--calls", type=int, default=3, help="steps per timed sample")
     ap.add_argument("--native-only", action="store_true")
+    ap.add_argument("--batch-stats", action="store_true", help="time the train-mode BatchNorm step (scripts/bn_step_bench.py)")
     ap.add_argument("--stats-from", default=None, help="summarise a rocprofv3 *_kernel_stats.csv instead of timing")
     ap.add_argument("--stats-steps", type=int, default=4, help="native steps traced per shape")
     ap.add_argument("--out", default=None)
@@ -161,7 +172,7 @@ def main():
         shapes = []
         for s in args.shapes.split(","):
             n, img = (int(v) for v in s.split("x"))
-            r = run_shape(sd32, enc, n, img, args.warmup, args.iters, args.calls, args.native_only)
+            r = run_shape(sd32, enc, n, img, args.warmup, args.iters, args.calls, args.native_only, args.batch_stats)
             print(json.dumps({k: v for k, v in r.items() if not k.endswith("_all")}), flush=True)
             shapes.append(r)
             torch.cuda.empty_cache()
