@@ -630,6 +630,57 @@ int occ_fullnet_bn_backward(const OccEncoderConfig* cfg, const float* enc_packed
                             float* grad_enc_packed, float* grad_dec_packed, void* stream);
 
 /*
+ * The optimizer of the joint training step (additive in ABI 12; csrc/occ_adamw.hpp): torch.optim.AdamW (pretrainer.py:91;
+ * decoupled decay, amsgrad off, maximize off) on the PACKED parameters, so that a training step neither unpacks a gradient
+ * nor packs a parameter.  Per part (the encoder of either form, cfg->separable; the decoder with the classifier) the caller
+ * keeps, all in the packed order of occ_encoder_packed_floats / occ_decoder_packed_floats floats:
+ *   theta   the master: every slot the raw parameter, a layer's scale / shift slots holding gamma and beta;
+ *   m, v    AdamW's two moments;
+ *   grad    the packed gradient exactly as occ_fullnet_backward / occ_sep_fullnet_backward / occ_fullnet_bn_backward wrote it;
+ *   packed  the buffer the next train forward reads, written here.
+ * stats: the running statistics of the 21 BatchNorm layers in packed order (16 encoder layers, 5 decoder levels),
+ * mean[c] | var[c] per layer, the layout of bn_stats: 2 x 1248 floats.
+ *
+ * occ_net_adamw_query(cfg, &enc_floats, &dec_floats, &stat_floats): the three sizes in floats; no GPU is touched.
+ *
+ * occ_net_adamw_step(cfg, enc_theta, enc_m, enc_v, enc_grad, enc_packed, dec_theta, dec_m, dec_v, dec_grad, dec_packed,
+ *                    stats, head_theta, head_m, head_v, head_grad, head_count, lr, beta1, beta2, eps, weight_decay, step,
+ *                    bn_mode, stream)
+ * head_*: an optional plain segment of head_count floats (the grad head) that takes the same step; head_count == 0: the four
+ * pointers are not read.  step is 1-based; the bias corrections bc1 = 1 - beta1^step, bc2 = 1 - beta2^step are formed on the
+ * host in double, as torch.optim.AdamW forms them, and every scalar reaches the kernel rounded to f32 once.  Every slot g, p:
+ *   p *= 1 - lr weight_decay;  m += (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g g;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)                                                   (f32)
+ * with the roundings of torch's foreach implementation on the device written out (every torch op rounds on its own, the
+ * multiply-add inside lerp_, addcmul_ and addcdiv_ is fused), so that from equal inputs it gives torch's bits.
+ * The decay applies to every slot, gamma, beta and the biases included (the reference's single parameter group), to gamma
+ * and never to the folded scale.
+ *   bn_mode 0 (running statistics): a layer's gradient slots hold d scale, d shift.  With rstd = 1 / sqrt(var + 1e-5):
+ *     d gamma = (d scale - mean d shift) rstd, d beta = d shift; after the update packed gets scale = gamma rstd and
+ *     shift = beta - mean scale of the UPDATED gamma, beta.  Both in f64, every operation rounded on its own (no fused
+ *     multiply-add), rounded to f32 once: bitwise what unfused f64 tensor operations give.
+ *   bn_mode 1 (batch statistics, occ_fullnet_bn_*): the slots hold d gamma, d beta; packed gets gamma, beta; stats is not read.
+ * Every other slot of packed is a copy of theta.  One thread owns a channel's (gamma, beta) pair.  ONE launch on `stream` for
+ * both parts and the head; no atomics, no reductions: the result is bitwise the same from call to call.
+ *
+ * occ_net_adamw_fold(cfg, enc_theta, enc_packed, dec_theta, dec_packed, stats, bn_mode, stream): writes both packed buffers
+ * from the masters as the step does after its update, and nothing else: for the first forward, and after a change of the
+ * BatchNorm mode or of the running statistics.  One launch.
+ *
+ * Every pointer is 16-byte aligned.  OCC_ERR_ARG before anything is launched for a bad cfg (img is checked as everywhere,
+ * the layout does not depend on it), a null or misaligned pointer, head_count < 0, step <= 0, eps <= 0, lr < 0,
+ * weight_decay < 0, a beta outside [0, 1) or a bn_mode other than 0 and 1.
+ */
+int occ_net_adamw_query(const OccEncoderConfig* cfg, int64_t* enc_floats, int64_t* dec_floats, int64_t* stat_floats);
+int occ_net_adamw_step(const OccEncoderConfig* cfg, float* enc_theta, float* enc_m, float* enc_v, const float* enc_grad,
+                       float* enc_packed, float* dec_theta, float* dec_m, float* dec_v, const float* dec_grad, float* dec_packed,
+                       const float* stats, float* head_theta, float* head_m, float* head_v, const float* head_grad,
+                       int64_t head_count, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                       int bn_mode, void* stream);
+int occ_net_adamw_fold(const OccEncoderConfig* cfg, const float* enc_theta, float* enc_packed, const float* dec_theta,
+                       float* dec_packed, const float* stats, int bn_mode, void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

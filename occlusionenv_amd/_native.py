@@ -241,6 +241,10 @@ SYMBOLS = {
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "occ_fullnet_bn_backward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "occ_net_adamw_query": (C.c_int, [C.POINTER(OccEncoderConfig)] + [C.POINTER(C.c_int64)] * 3),
+    "occ_net_adamw_step": (C.c_int, [C.POINTER(OccEncoderConfig)] + [C.c_void_p] * 15 + [C.c_int64] + [C.c_double] * 5 +
+                           [C.c_int64, C.c_int, C.c_void_p]),
+    "occ_net_adamw_fold": (C.c_int, [C.POINTER(OccEncoderConfig)] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
     "occ_seg_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "occ_seg_criterion_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "occ_seg_criterion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -46,10 +46,13 @@
 //                       activation step
 //   occ_seg_criterion_* the pretrainer's criterion on that map (occ_criterion.hpp): Dice / BCE sums and the counts in one
 //                       read, fixed-order f64 sums, and the gradient with respect to the prediction
+//   occ_adamw_kernel    the optimizer of that joint step (occ_adamw.hpp): AdamW in packed order on both parts and the grad
+//                       head, the BatchNorm chain rule and the fold of the next forward's packed buffers, one launch
 //
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -77,6 +80,7 @@ namespace occ {
 #include "occ_fullnet_bwd.hpp"
 #include "occ_bn_train.hpp"
 #include "occ_criterion.hpp"
+#include "occ_adamw.hpp"
 
 }  // namespace occ
 
@@ -907,6 +911,65 @@ extern "C" int occ_fullnet_bn_backward(const OccEncoderConfig* cfg, const float*
     const BnTrain bn = full_bn_ptrs(l, (char*)ws, nullptr);
     full_backward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, n_env, (char*)ws,
                   grad_feats, grad_prob, (char*)scratch, grad_enc_packed, grad_dec_packed, (hipStream_t)stream, &bn);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- AdamW on the packed parameters of the joint step (occ_adamw.hpp) ------------------------------------------------------
+extern "C" int occ_net_adamw_query(const OccEncoderConfig* cfg, int64_t* enc_floats, int64_t* dec_floats, int64_t* stat_floats) {
+    if (!enc_cfg_ok(cfg) || !non_null(enc_floats, dec_floats, stat_floats)) return OCC_ERR_ARG;
+    AdamwArgs a = {};
+    int stat = 0;
+    adamw_plan(cfg->separable != 0, 0, &a, &stat);
+    *enc_floats = enc_packed_floats(cfg->separable != 0);
+    *dec_floats = dec_packed_floats();
+    *stat_floats = stat;
+    return OCC_OK;
+}
+
+static bool adamw_parts_ok(const OccEncoderConfig* cfg, const float* enc_theta, const float* enc_packed, const float* dec_theta,
+                           const float* dec_packed, const float* stats, int bn_mode) {
+    return enc_cfg_ok(cfg) && non_null(enc_theta, enc_packed, dec_theta, dec_packed, stats) && (bn_mode == 0 || bn_mode == 1) &&
+           aligned(16, enc_theta, enc_packed, dec_theta, dec_packed, stats);
+}
+
+extern "C" int occ_net_adamw_step(const OccEncoderConfig* cfg, float* enc_theta, float* enc_m, float* enc_v, const float* enc_grad,
+                                  float* enc_packed, float* dec_theta, float* dec_m, float* dec_v, const float* dec_grad,
+                                  float* dec_packed, const float* stats, float* head_theta, float* head_m, float* head_v,
+                                  const float* head_grad, int64_t head_count, double lr, double beta1, double beta2, double eps,
+                                  double weight_decay, int64_t step, int bn_mode, void* stream) {
+    if (!adamw_parts_ok(cfg, enc_theta, enc_packed, dec_theta, dec_packed, stats, bn_mode) ||
+        !non_null(enc_m, enc_v, enc_grad, dec_m, dec_v, dec_grad) || !aligned(16, enc_m, enc_v, enc_grad, dec_m, dec_v, dec_grad))
+        return OCC_ERR_ARG;
+    if (head_count < 0 || head_count > (1 << 24)) return OCC_ERR_ARG;
+    if (head_count > 0 && (!non_null(head_theta, head_m, head_v, head_grad) || !aligned(16, head_theta, head_m, head_v, head_grad)))
+        return OCC_ERR_ARG;
+    // !(x >= 0) also refuses a NaN
+    if (step <= 0 || !(eps > 0.0) || !(lr >= 0.0) || !(weight_decay >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) ||
+        !(beta2 >= 0.0 && beta2 < 1.0))
+        return OCC_ERR_ARG;
+    AdamwArgs a = {};
+    a.part[0] = AdamwPart{enc_theta, enc_m, enc_v, enc_grad, enc_packed};
+    a.part[1] = AdamwPart{dec_theta, dec_m, dec_v, dec_grad, dec_packed};
+    a.part[2] = AdamwPart{head_theta, head_m, head_v, head_grad, nullptr};
+    a.stats = stats;
+    a.fold = bn_mode == 0;
+    // torch.optim.AdamW's scalars (_single_tensor_adam), in double as Python forms them
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    a.k = AdamwCoef{(float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(-(lr / bc1)),
+                    (float)sqrt(bc2), (float)eps};
+    adamw_launch<true>(cfg->separable != 0, (int)head_count, a, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_net_adamw_fold(const OccEncoderConfig* cfg, const float* enc_theta, float* enc_packed, const float* dec_theta,
+                                  float* dec_packed, const float* stats, int bn_mode, void* stream) {
+    if (!adamw_parts_ok(cfg, enc_theta, enc_packed, dec_theta, dec_packed, stats, bn_mode)) return OCC_ERR_ARG;
+    AdamwArgs a = {};
+    a.part[0] = AdamwPart{const_cast<float*>(enc_theta), nullptr, nullptr, nullptr, enc_packed};
+    a.part[1] = AdamwPart{const_cast<float*>(dec_theta), nullptr, nullptr, nullptr, dec_packed};
+    a.stats = stats;
+    a.fold = bn_mode == 0;
+    adamw_launch<false>(cfg->separable != 0, 0, a, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

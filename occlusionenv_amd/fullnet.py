@@ -34,6 +34,9 @@ Limits: dense 3x3 convs only (a separable checkpoint raises) at dilation 1, the 
 multiple of 32.  A training call is one chunk (``N <= enc.max_chunk``), and the kept activations belong to the latest
 forward: a backward of an earlier forward raises.
 
+``netoptim.PackedAdamW(net)`` moves the trainable values into packed masters and takes the optimizer step in one native
+launch; ``net.sync_parameters()`` (and ``net.state_dict()``, which calls it) writes them back under the checkpoint's keys.
+
 The host path (fold, packed layouts, parameters under the checkpoint's keys, workspace, the autograd function) is
 ``nettrain.TrainableNet``'s on two parts, the encoder's and the decoder's; here are the guards, the native symbols and the
 heads.  The heads and ``forward`` are ``JointNet``'s, which ``sepfullnet.TrainableSeparableFullNetwork`` (the separable
@@ -78,9 +81,28 @@ class JointNet(TrainableNet):
             return None, prob
         if not self.has_grad_head:
             raise ValueError("this checkpoint has no gradPredictor head; use features_and_map(obs)")
-        grad_pred = torch.nn.functional.linear(feats, self.get_parameter(self.grad_prefix + "weight"),
-                                               self.get_parameter(self.grad_prefix + "bias"))
-        return feats, prob, grad_pred
+        if self._resident is not None:
+            weight, bias = self._resident.head_views()
+        else:
+            weight, bias = self.get_parameter(self.grad_prefix + "weight"), self.get_parameter(self.grad_prefix + "bias")
+        return feats, prob, torch.nn.functional.linear(feats, weight, bias)
+
+    # ---- under netoptim.PackedAdamW the trained values live in packed masters (net._resident) --------------------------------
+    def sync_parameters(self) -> None:
+        """Write the packed masters of ``netoptim.PackedAdamW`` back to the parameters under the checkpoint's keys; nothing
+        to do for a net without one."""
+        if self._resident is not None:
+            self._resident.sync()
+
+    def state_dict(self, *args, **kwargs):
+        self.sync_parameters()
+        return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        result = super().load_state_dict(*args, **kwargs)
+        if self._resident is not None:
+            self._resident.repack()
+        return result
 
 
 class TrainableFullNetwork(JointNet):

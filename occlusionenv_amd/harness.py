@@ -19,7 +19,9 @@
     back-propagated through decoder, skips and encoder at once (``fullnet.TrainableFullNetwork``, or
     ``sepfullnet.TrainableSeparableFullNetwork`` for the separable network the agent runs), AdamW.  ``batch_stats=True``:
     BatchNorm in train mode as in the reference (batch statistics, running averages updated); the default keeps the running
-    statistics.
+    statistics.  ``native_optimizer=True``: ``netoptim.PackedAdamW``, the AdamW step in packed order in one native launch.
+  * ``pretrain`` -- pretrainer.py:209-259 (``PreTrainer.run``): per epoch ``pretrain_epoch``, ``validate_pretrained`` on the
+    trained network, one step of the cosine schedule; the state dict of the best validation IoU is kept.
 """
 from __future__ import annotations
 
@@ -197,24 +199,8 @@ def train_predictor(venv, enc_or_net, steps: int, lr: float = 1e-4, weight_decay
     return dict(net=net, losses=host, skipped=skipped, steps=len(host))
 
 
-def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = False, lr: float = 1e-3, weight_decay: float = 1e-5,
-                   optimizer=None, batch_stats: bool = False) -> dict:
-    """One epoch of ``PreTrainer.train()`` (pretrainer.py:112-159) on the device: ``batches`` is any iterable of
-    ``(img, occlusion, grad, _)`` as for ``validate_pretrained``.  Every batch goes through ``net(img)``
-    (``fullnet.TrainableFullNetwork`` or ``sepfullnet.TrainableSeparableFullNetwork``: one native forward of encoder, decoder
-    and classifier, the grad head in torch), takes
-    ``segmentation.binary_dice_loss`` (``use_dice``) or ``binary_cross_entropy`` of the map plus ``nn.MSELoss()`` or
-    ``nn.SmoothL1Loss(beta=0.01)`` (``use_l1``) of the gradient prediction, runs ``backward`` (one native joint backward)
-    and one ``torch.optim.AdamW`` step (pretrainer.py:91; ``optimizer``: one to carry over epochs, made here when None).
-    ``net_or_enc``: a ``TrainableFullNetwork`` or a ``TrainableSeparableFullNetwork``, or a "ppo" ``FrozenEncoder`` with decoder
-    and grad head, from which the one for its form (dense or separable) is made, with ``batch_stats`` passed on:
-    False, BatchNorm keeps its running statistics; True, it runs in train mode as the reference's does (``fullnet``), each
-    batch needing ``N (S / 32)^2 >= 2``.  A net that is passed in keeps its own setting.  Returned are ``net``, ``optimizer`` and the five numbers
-    the reference prints, computed its way: ``loss``, ``segm_loss``, ``grad_loss`` = the mean over batches of the per-batch
-    losses, ``accuracy`` and ``iou`` = the mean over batches of the per-batch ratios x 100 of the prediction the step learned
-    from (``segmentation.seg_criterion``'s counts); also the pooled ``correct``, ``intersection``, ``union``, ``pixels``
-    and ``batches``.  One host sync, at the end."""
-    from . import segmentation
+def _pretrain_net(net_or_enc, batch_stats: bool):
+    """The joint network of ``pretrain_epoch`` / ``pretrain``: ``net_or_enc`` itself, or the one for the encoder's form."""
     from .fullnet import JointNet, TrainableFullNetwork
     from .sepfullnet import TrainableSeparableFullNetwork
 
@@ -226,7 +212,43 @@ def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = Fa
         net = TrainableFullNetwork.from_encoder(net_or_enc, batch_stats=batch_stats)
     if not net.has_grad_head or net.enc.preset != "ppo":
         raise ValueError("pretrain_epoch needs a FullNetwork checkpoint (preset 'ppo') with its gradPredictor head")
-    opt = optimizer if optimizer is not None else torch.optim.AdamW(net.parameters(), lr=lr, weight_decay=weight_decay)
+    return net
+
+
+def _pretrain_optimizer(net, lr: float, weight_decay: float, native: bool):
+    """pretrainer.py:91's AdamW for ``net``: ``netoptim.PackedAdamW`` (``native``) or ``torch.optim.AdamW`` on its parameters."""
+    if native:
+        from .netoptim import PackedAdamW
+
+        return PackedAdamW(net, lr=lr, weight_decay=weight_decay)
+    if net._resident is not None:
+        raise ValueError("this net is packed-resident (netoptim.PackedAdamW): pass its optimizer or native_optimizer=True")
+    return torch.optim.AdamW(net.parameters(), lr=lr, weight_decay=weight_decay)
+
+
+def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = False, lr: float = 1e-3, weight_decay: float = 1e-5,
+                   optimizer=None, batch_stats: bool = False, native_optimizer: bool = False) -> dict:
+    """One epoch of ``PreTrainer.train()`` (pretrainer.py:112-159) on the device: ``batches`` is any iterable of
+    ``(img, occlusion, grad, _)`` as for ``validate_pretrained``.  Every batch goes through ``net(img)``
+    (``fullnet.TrainableFullNetwork`` or ``sepfullnet.TrainableSeparableFullNetwork``: one native forward of encoder, decoder
+    and classifier, the grad head in torch), takes
+    ``segmentation.binary_dice_loss`` (``use_dice``) or ``binary_cross_entropy`` of the map plus ``nn.MSELoss()`` or
+    ``nn.SmoothL1Loss(beta=0.01)`` (``use_l1``) of the gradient prediction, runs ``backward`` (one native joint backward)
+    and one ``torch.optim.AdamW`` step (pretrainer.py:91; ``optimizer``: one to carry over epochs, made here when None;
+    ``native_optimizer=True`` makes a ``netoptim.PackedAdamW`` instead, after which the net is packed-resident and only that
+    optimizer trains it).
+    ``net_or_enc``: a ``TrainableFullNetwork`` or a ``TrainableSeparableFullNetwork``, or a "ppo" ``FrozenEncoder`` with decoder
+    and grad head, from which the one for its form (dense or separable) is made, with ``batch_stats`` passed on:
+    False, BatchNorm keeps its running statistics; True, it runs in train mode as the reference's does (``fullnet``), each
+    batch needing ``N (S / 32)^2 >= 2``.  A net that is passed in keeps its own setting.  Returned are ``net``, ``optimizer`` and the five numbers
+    the reference prints, computed its way: ``loss``, ``segm_loss``, ``grad_loss`` = the mean over batches of the per-batch
+    losses, ``accuracy`` and ``iou`` = the mean over batches of the per-batch ratios x 100 of the prediction the step learned
+    from (``segmentation.seg_criterion``'s counts); also the pooled ``correct``, ``intersection``, ``union``, ``pixels``
+    and ``batches``.  One host sync, at the end."""
+    from . import segmentation
+
+    net = _pretrain_net(net_or_enc, batch_stats)
+    opt = optimizer if optimizer is not None else _pretrain_optimizer(net, lr, weight_decay, native_optimizer)
     dev = net.enc.device
     rows, totals, pixels = [], None, 0
     for img, occlusion, grad, *_ in batches:
@@ -253,6 +275,40 @@ def pretrain_epoch(net_or_enc, batches, use_dice: bool = True, use_l1: bool = Fa
     correct, inter, union = (int(x) for x in host[5:])
     return dict(net=net, optimizer=opt, loss=loss, segm_loss=segm_loss, grad_loss=grad_loss, accuracy=100.0 * acc, iou=100.0 * iou,
                 correct=correct, intersection=inter, union=union, pixels=pixels, batches=len(rows))
+
+
+def pretrain(net_or_enc, train_batches, val_batches, epochs: int, use_dice: bool = True, use_l1: bool = False, lr: float = 1e-3,
+             weight_decay: float = 1e-5, batch_stats: bool = False, native_optimizer: bool = True) -> dict:
+    """``PreTrainer.run()`` (pretrainer.py:209-259) on the device: ``epochs`` times ``pretrain_epoch`` on ``train_batches``,
+    ``validate_pretrained`` of the trained network (``enc.with_state(net.state_dict())``) on ``val_batches``, and one step of
+    ``CosineAnnealingLR(optimizer, epochs, eta_min=0.1 * lr)``; the state dict after the epoch with the best validation IoU
+    so far is kept (a copy, as the reference saves a file).  ``train_batches`` / ``val_batches``: a callable returning the
+    epoch's iterable of batches, or a re-iterable (a list, a DataLoader), so that every epoch sees its batches again.
+    ``native_optimizer``: ``netoptim.PackedAdamW`` (the default here) or ``torch.optim.AdamW``; the other arguments are
+    ``pretrain_epoch``'s.  Returns ``net``, ``optimizer``, ``rows`` (per epoch ``epoch``, ``lr`` = the rate the epoch trained
+    with, ``train`` and ``val`` = the two dicts of numbers), ``best_epoch``, ``best_iou`` and ``best_state``.  A validation
+    IoU of nan (a batch with an empty union) never counts as best; without any other, the first epoch's state is returned."""
+    if int(epochs) < 1:
+        raise ValueError("pretrain: epochs must be >= 1")
+
+    def each(batches):
+        return batches() if callable(batches) else batches
+
+    net = _pretrain_net(net_or_enc, batch_stats)
+    opt = _pretrain_optimizer(net, lr, weight_decay, native_optimizer)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, int(epochs), eta_min=0.1 * lr)
+    rows, best_iou, best_epoch, best_state = [], float("-inf"), None, None
+    for epoch in range(int(epochs)):
+        trained = float(opt.param_groups[0]["lr"])
+        res = pretrain_epoch(net, each(train_batches), use_dice=use_dice, use_l1=use_l1, optimizer=opt)
+        state = {k: v.detach().clone() for k, v in net.state_dict().items()}
+        val = validate_pretrained(net.enc.with_state(state), each(val_batches), use_dice=use_dice, use_l1=use_l1)
+        sched.step()
+        rows.append(dict(epoch=epoch, lr=trained, train={k: v for k, v in res.items() if k not in ("net", "optimizer")}, val=val))
+        if val["iou"] > best_iou or best_state is None:
+            best_epoch, best_state = epoch, state
+            best_iou = val["iou"] if val["iou"] == val["iou"] else best_iou
+    return dict(net=net, optimizer=opt, rows=rows, best_epoch=best_epoch, best_iou=best_iou, best_state=best_state)
 
 
 @torch.no_grad()

@@ -14,6 +14,10 @@ buffers towards the batch's mean and unbiased variance (momentum 0.1) without a 
 values per channel, ``N (S / 32)^2 >= 2``.  After ``net.eval()`` the step is the running-statistics one, bit for bit.
 A training call is one chunk (``N <= enc.max_chunk``), and the kept activations belong to the latest forward: a backward of
 an earlier forward raises.
+
+A joint network under ``netoptim.PackedAdamW`` is packed-resident (``net._resident``): its trainable leaves are one packed
+master tensor per part, and a second autograd function, ``_PackedStep``, hands the packed buffers the optimizer's kernel
+wrote to the same native forward and returns the packed gradients as they are; nothing is folded, packed or sliced per key.
 """
 from __future__ import annotations
 
@@ -244,6 +248,7 @@ class TrainableNet(torch.nn.Module):
         self._version = 0
         self._latest = None
         self._bufs = {}
+        self._resident = None  # netoptim.PackedState once a PackedAdamW owns the parameters
 
     @classmethod
     def from_encoder(cls, enc: FrozenEncoder):
@@ -306,6 +311,8 @@ class TrainableNet(torch.nn.Module):
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(obs.shape)}: the "
                              "deepest BatchNorm sees N (S / 32)^2 values")
         obs = obs.detach().to(torch.float32).contiguous()
+        if self._resident is not None:
+            return _PackedStep.apply(obs, self, *self._resident.theta)
         return _NetStep.apply(obs, self, *[p for _k, p in self.ordered_parameters()])
 
 
@@ -325,6 +332,44 @@ def _update_running_stats(net, stats: torch.Tensor, n: int, img: int) -> None:
         torch._foreach_mul_(list(running_mean) + list(running_var), 1.0 - BN_MOMENTUM)
         torch._foreach_add_(list(running_mean), means, alpha=BN_MOMENTUM)
         torch._foreach_add_(list(running_var), torch._foreach_mul(variances, unbias))
+
+
+def _native_step_forward(ctx, net, obs, packed, bn):
+    """The native train forward of ``net`` on the ``packed`` parts (and, ``bn``, the move of the running buffers), kept on
+    ``ctx`` for the backward -> the outputs ``net.RETURNS``."""
+    n, img = int(obs.shape[0]), int(obs.shape[2])
+    ws, _scratch = net._train_buffers(n, img, bn)
+    out = {"feats": torch.empty(n, FEATURES, dtype=torch.float32, device=obs.device)}
+    if "prob" in net.RETURNS:
+        out["prob"] = torch.empty(n, 1, img, img, dtype=torch.float32, device=obs.device)
+    net._version += 1
+    net._latest = (n, img)
+    if bn:
+        stats = torch.empty(2 * sum(c for c, _plane in bn_layer_shapes(img)), dtype=torch.float32, device=obs.device)
+        net._native_forward(img, packed, obs, n, ws, list(out.values()) + [stats], bn=True)
+        _update_running_stats(net, stats, n, img)
+        net.bn_stats = stats  # of the latest train-mode forward: mean[c] | var_biased[c] per layer, packed order
+    else:
+        net._native_forward(img, packed, obs, n, ws, list(out.values()))
+    ctx.net, ctx.packed, ctx.version, ctx.shape, ctx.bn = net, packed, net._version, (n, img), bn
+    if len(net.DIFFERENTIABLE) < len(net.RETURNS):
+        ctx.mark_non_differentiable(*[out[k] for k in net.RETURNS if k not in net.DIFFERENTIABLE])
+    return out[net.RETURNS[0]] if len(net.RETURNS) == 1 else tuple(out[k] for k in net.RETURNS)
+
+
+def _native_step_backward(ctx, grads):
+    """The native backward of the forward kept on ``ctx`` -> one packed gradient per part."""
+    net = ctx.net
+    if ctx.version != net._version:
+        raise RuntimeError(f"{type(net).__name__}: backward of a forward that a later forward has superseded; the kept "
+                           "activations belong to the latest forward (call backward before the next forward)")
+    n, img = ctx.shape
+    ws, scratch = net._train_buffers(n, img, ctx.bn)
+    upstream = dict(zip(net.RETURNS, grads))
+    grads_in = [upstream[k].to(torch.float32).contiguous() for k in net.DIFFERENTIABLE]
+    grads_out = [torch.empty(part.floats, dtype=torch.float32, device=grads_in[0].device) for part in net.parts]
+    net._native_backward(img, ctx.packed, n, ws, grads_in, scratch, grads_out, bn=ctx.bn)
+    return grads_out
 
 
 class _NetStep(torch.autograd.Function):
@@ -348,37 +393,11 @@ class _NetStep(torch.autograd.Function):
             folded.append((layers, params[at:at + len(part.tail)]))
             at += len(part.tail)
         packed = [part.pack(layers, tail).contiguous() for part, (layers, tail) in zip(net.parts, folded)]
-        n, img = int(obs.shape[0]), int(obs.shape[2])
-        ws, _scratch = net._train_buffers(n, img, bn)
-        out = {"feats": torch.empty(n, FEATURES, dtype=torch.float32, device=obs.device)}
-        if "prob" in net.RETURNS:
-            out["prob"] = torch.empty(n, 1, img, img, dtype=torch.float32, device=obs.device)
-        net._version += 1
-        net._latest = (n, img)
-        if bn:
-            stats = torch.empty(2 * sum(c for c, _plane in bn_layer_shapes(img)), dtype=torch.float32, device=obs.device)
-            net._native_forward(img, packed, obs, n, ws, list(out.values()) + [stats], bn=True)
-            _update_running_stats(net, stats, n, img)
-            net.bn_stats = stats  # of the latest train-mode forward: mean[c] | var_biased[c] per layer, packed order
-        else:
-            net._native_forward(img, packed, obs, n, ws, list(out.values()))
-        ctx.net, ctx.packed, ctx.version, ctx.shape, ctx.bn = net, packed, net._version, (n, img), bn
-        if len(net.DIFFERENTIABLE) < len(net.RETURNS):
-            ctx.mark_non_differentiable(*[out[k] for k in net.RETURNS if k not in net.DIFFERENTIABLE])
-        return out[net.RETURNS[0]] if len(net.RETURNS) == 1 else tuple(out[k] for k in net.RETURNS)
+        return _native_step_forward(ctx, net, obs, packed, bn)
 
     @staticmethod
     def backward(ctx, *grads):
-        net = ctx.net
-        if ctx.version != net._version:
-            raise RuntimeError(f"{type(net).__name__}: backward of a forward that a later forward has superseded; the kept "
-                               "activations belong to the latest forward (call backward before the next forward)")
-        n, img = ctx.shape
-        ws, scratch = net._train_buffers(n, img, ctx.bn)
-        upstream = dict(zip(net.RETURNS, grads))
-        grads_in = [upstream[k].to(torch.float32).contiguous() for k in net.DIFFERENTIABLE]
-        grads_out = [torch.empty(part.floats, dtype=torch.float32, device=grads_in[0].device) for part in net.parts]
-        net._native_backward(img, ctx.packed, n, ws, grads_in, scratch, grads_out, bn=ctx.bn)
+        net, grads_out = ctx.net, _native_step_backward(ctx, grads)
         result = [None, None]
         for part, gp in zip(net.parts, grads_out):
             layers, tail = part.unpack(gp)
@@ -389,3 +408,18 @@ class _NetStep(torch.autograd.Function):
                 result += [dgamma.to(torch.float32), dbeta.to(torch.float32)]
             result += [t.clone() for t in tail]
         return tuple(result)
+
+
+class _PackedStep(torch.autograd.Function):
+    """(obs, net, the packed master of every part) -> the outputs ``net.RETURNS`` of a packed-resident net: the forward reads
+    the packed buffers ``net._resident`` keeps for the step's BatchNorm mode, the gradient of a master is the packed gradient
+    of the native backward, unchanged (``netoptim.PackedAdamW``'s kernel takes it as it is)."""
+
+    @staticmethod
+    def forward(ctx, obs, net, *_theta):
+        bn = net._bn_mode()
+        return _native_step_forward(ctx, net, obs, net._resident.packed_for(bn), bn)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None, None, *_native_step_backward(ctx, grads))
