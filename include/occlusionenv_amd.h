@@ -681,6 +681,64 @@ int occ_net_adamw_fold(const OccEncoderConfig* cfg, const float* enc_theta, floa
                        float* dec_packed, const float* stats, int bn_mode, void* stream);
 
 /*
+ * The pretraining input pipeline (additive in ABI 12; csrc/occ_augment.hpp): what dataset.py:53-92 does per item between
+ * the decoded, resized frame and the tensors of a batch, for a dataset that is resident on the device.  Decoding and
+ * resizing are deterministic and happen once, on the host; what is random per epoch (the shuffle, ColorJitter(0.3, 0.3,
+ * 0.2, 0.1), the flip) is a gather by frame index plus point arithmetic here.
+ *
+ * The store (device memory, only read), M frames of S x S pixels (S = img):
+ *   rgbl   uint32[M][S][S]  one word per pixel, R | G << 8 | B << 16 | label << 24, label 0 or 1
+ *   depth  int16[M][S][S]   the mode-"I" depth image as resized (PIL's bicubic filter can leave [0, 255])
+ *   pos    float[M][2]      dataset.py:62
+ *   grad   float[M][2]      the gradient label as the caller wants it returned (dataset.py:84-89: (sin a, cos a))
+ *
+ * OccAugmentParams, one per sample: what ColorJitter.get_params and dataset.py:72 draw.  order holds the four ops of the
+ * jitter, 2 bits each, the first op in the low bits: 0 brightness, 1 contrast, 2 saturation, 3 hue (every op once).
+ * hue_shift is the byte torchvision adds to the H band, int(hue_factor * 255) & 255.  jitter == 0 skips all four ops.
+ *
+ * occ_augment_query(img, n, &workspace_bytes): the size of the workspace of a call (4-byte aligned device memory, the
+ * per-block luminance sums; its contents mean nothing between calls); no GPU is touched.
+ *
+ * occ_augment_batch(rgbl, depth, pos, grad, m_frames, img, idx, params, n, normalize, out_img, out_label, out_grad, out_pos,
+ *                   workspace, stream)
+ * idx: int64[n] on the device, frame numbers in [0, m_frames), in any order, repeats allowed.  Keeping them in range is the
+ * caller's duty; the kernels clamp them, so that no address outside the store is ever formed.  Sample i gets
+ *   out_img[i]    float[4][S][S]  R, G, B after the jitter, and the depth; level / 255, with normalize != 0 then
+ *                                 (c - 0.5) / 0.25 on all four planes (dataset.py:28-31,77-81)
+ *   out_label[i]  float[1][S][S]  0 or 1 (dataset.py:82 divides by 255 once more; this does not)
+ *   out_grad[i], out_pos[i]  float[2]  the frame's rows
+ * and with params[i].flip != 0 output column x of the three images is source column S - 1 - x.  Arithmetic of the jitter,
+ * per channel on 8-bit levels, which is PIL's (torchvision's PIL path) rounding for rounding:
+ *   L = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16                                               convert("L")
+ *   blend(deg, x, f): t = (float)deg + f * (float)(x - deg) in f32, product and sum rounded separately; for 0 <= f <= 1
+ *     the truncation of t, else 0 for t <= 0, 255 for t >= 255, else the truncation                ImagingBlend
+ *   brightness: deg = 0.  saturation: deg = L of the pixel.  contrast: deg = (int)(sum L / (double)(S S) + 0.5) over the
+ *     whole image as it stands when contrast's turn comes.
+ *   hue: RGB -> HSV as PIL's rgb2hsv_row (f32 divisions; 2.0 + rc - bc, h / 6.0 + 1.0, h * 255.0 and s * 255.0 in f64),
+ *     h = (h + hue_shift) & 255, HSV -> RGB as PIL's hsv2rgb_row (all f32, floor(x + 0.5)).
+ * No multiply-add of these is fused.  tests/augment_model.py is this arithmetic in numpy, checked against PIL.
+ *
+ * params may be NULL: no sample is jittered or flipped (a validation batch), and workspace is not used and may be NULL.
+ * At most two launches on `stream`: the luminance-sum pass (samples with jitter == 0 leave it at once; skipped altogether
+ * for params == NULL, the one case the host can see) and the output pass.  Nothing is allocated or synchronised, no atomics,
+ * no memset, integer sums: the outputs are bitwise the same from call to call.
+ * OCC_ERR_ARG before any launch for a null pointer (other than the two above), img < 1, img * img > 2^24 (the u32
+ * luminance sum must not overflow), n < 1, n > 65535, m_frames < 1.
+ */
+typedef struct OccAugmentParams {
+    float brightness, contrast, saturation; /* the three blend factors */
+    int32_t hue_shift;                      /* 0..255 */
+    int32_t order;                          /* four 2-bit op codes, first op in the low bits */
+    int32_t jitter;                         /* 0: none of the four ops */
+    int32_t flip;                           /* != 0: mirrored left to right */
+    int32_t pad;
+} OccAugmentParams;
+int occ_augment_query(int img, int n, size_t* workspace_bytes);
+int occ_augment_batch(const uint32_t* rgbl, const int16_t* depth, const float* pos, const float* grad, int m_frames, int img,
+                      const int64_t* idx, const OccAugmentParams* params, int n, int normalize, float* out_img,
+                      float* out_label, float* out_grad, float* out_pos, void* workspace, void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

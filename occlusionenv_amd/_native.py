@@ -161,6 +161,13 @@ class OccEncoderConfig(C.Structure):
 ENCODER_FEATURES = 256
 CRITERION_DICE, CRITERION_BCE = 0, 1
 
+
+class OccAugmentParams(C.Structure):
+    """include/occlusionenv_amd.h: OccAugmentParams (one sample's draws of the colour jitter and the flip), 32 bytes."""
+    _fields_ = [("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float), ("hue_shift", C.c_int32),
+                ("order", C.c_int32), ("jitter", C.c_int32), ("flip", C.c_int32), ("pad", C.c_int32)]
+
+
 #: every symbol include/occlusionenv_amd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "occ_abi_version": (C.c_int, []),
@@ -245,6 +252,9 @@ SYMBOLS = {
     "occ_net_adamw_step": (C.c_int, [C.POINTER(OccEncoderConfig)] + [C.c_void_p] * 15 + [C.c_int64] + [C.c_double] * 5 +
                            [C.c_int64, C.c_int, C.c_void_p]),
     "occ_net_adamw_fold": (C.c_int, [C.POINTER(OccEncoderConfig)] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
+    "occ_augment_query": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "occ_augment_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] +
+                          [C.c_void_p] * 6),
     "occ_seg_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "occ_seg_criterion_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "occ_seg_criterion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

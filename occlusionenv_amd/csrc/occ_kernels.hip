@@ -48,6 +48,9 @@
 //                       read, fixed-order f64 sums, and the gradient with respect to the prediction
 //   occ_adamw_kernel    the optimizer of that joint step (occ_adamw.hpp): AdamW in packed order on both parts and the grad
 //                       head, the BatchNorm chain rule and the fold of the next forward's packed buffers, one launch
+//   occ_augment_*       the pretrainer's input pipeline on a device-resident dataset (occ_augment.hpp): gather by frame
+//                       index, torchvision's colour jitter with PIL's roundings, flip, /255 and Normalize: a luminance-
+//                       sum pass for contrast's mean and an output pass
 //
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
@@ -81,6 +84,7 @@ namespace occ {
 #include "occ_bn_train.hpp"
 #include "occ_criterion.hpp"
 #include "occ_adamw.hpp"
+#include "occ_augment.hpp"
 
 }  // namespace occ
 
@@ -970,6 +974,30 @@ extern "C" int occ_net_adamw_fold(const OccEncoderConfig* cfg, const float* enc_
     a.stats = stats;
     a.fold = bn_mode == 0;
     adamw_launch<false>(cfg->separable != 0, 0, a, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- the pretraining input pipeline (occ_augment.hpp) ----------------------------------------------------------------------
+static bool augment_shape_ok(int img, int n) { return img >= 1 && (int64_t)img * img <= (int64_t)kAugMaxPixels && n >= 1 && n <= 65535; }
+
+extern "C" int occ_augment_query(int img, int n, size_t* workspace_bytes) {
+    if (!augment_shape_ok(img, n) || !workspace_bytes) return OCC_ERR_ARG;
+    *workspace_bytes = (size_t)n * aug_blocks_per_image(img) * sizeof(uint32_t);
+    return OCC_OK;
+}
+
+extern "C" int occ_augment_batch(const uint32_t* rgbl, const int16_t* depth, const float* pos, const float* grad, int m_frames,
+                                 int img, const int64_t* idx, const OccAugmentParams* params, int n, int normalize, float* out_img,
+                                 float* out_label, float* out_grad, float* out_pos, void* workspace, void* stream) {
+    if (!augment_shape_ok(img, n) || m_frames < 1) return OCC_ERR_ARG;
+    if (!non_null(rgbl, depth, pos, grad, idx, out_img, out_label, out_grad, out_pos) || (params && !workspace)) return OCC_ERR_ARG;
+    const dim3 grid(aug_blocks_per_image(img), n);
+    hipStream_t st = (hipStream_t)stream;
+    if (params)
+        hipLaunchKernelGGL(occ_augment_sum_kernel, grid, dim3(kAugBlock), 0, st, rgbl, m_frames, img * img, idx, params,
+                           (uint32_t*)workspace);
+    hipLaunchKernelGGL(occ_augment_out_kernel, grid, dim3(kAugBlock), 0, st, rgbl, depth, pos, grad, m_frames, img, idx, params,
+                       (const uint32_t*)workspace, normalize, out_img, out_label, out_grad, out_pos);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

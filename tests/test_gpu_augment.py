@@ -1,0 +1,320 @@
+"""GPU tests of the device input pipeline (csrc/occ_augment.hpp, ``occ_augment_batch``; occlusionenv_amd/devdata.py) against
+tests/augment_model.py, the numpy model that tests/test_augment_model.py pins to PIL.  Every output is compared bit for
+bit.  The kernel tests call the C ABI directly: every buffer the call writes starts as seeded random bits and runs GUARD
+words past what the ABI names, and the guards are compared afterwards.
+
+Sizes.  The kernels take BLOCK = 256 pixels per block.  S = 32: rows shorter than a wave, so the flip crosses lanes, four
+full blocks.  S = 40: 1600 pixels, six full blocks and a quarter.  S_ODD = 23: the smallest image that spans three blocks of
+the sum pass with a partial last one.  S_WIDE = 264: 273 blocks per image, more than one block's threads, so the output
+pass sums the partials in two rounds.
+"""
+import ctypes as C
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+from tests import augment_model as am
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64
+BLOCK = 256
+S_ODD = next(s for s in range(1, 64) if s * s > 2 * BLOCK and (s * s) % BLOCK)
+S_WIDE = next(s for s in range(8, 1024, 8) if (s * s + BLOCK - 1) // BLOCK > BLOCK)
+ORDERS = list(itertools.permutations(range(4)))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from occlusionenv_amd import _native as nat
+
+    return nat.load()
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def make_store(M, S, seed):
+    """Seeded frames: random colours with patches of 0 and 255, depth with -20 and 300 in it, random labels."""
+    rng = np.random.default_rng(seed)
+    rgb = rng.integers(0, 256, (M, S, S, 3), dtype=np.uint8)
+    rgb[:, 0, : S // 2] = 0
+    rgb[:, 1, : S // 2] = 255
+    depth = rng.integers(0, 256, (M, S, S)).astype(np.int16)
+    depth[:, 2, ::3] = -20
+    depth[:, 3, ::3] = 300
+    label = (rng.random((M, S, S)) < 0.4).astype(np.uint8)
+    pos = rng.normal(size=(M, 2)).astype(np.float32)
+    grad = rng.normal(size=(M, 2)).astype(np.float32)
+    return rgb, depth, label, pos, grad
+
+
+def pack_words(rgb, label):
+    c = rgb.astype(np.uint32)
+    return (c[..., 0] | c[..., 1] << 8 | c[..., 2] << 16 | (label != 0).astype(np.uint32) << 24).view(np.int32)
+
+
+def _guarded(words, gen):
+    return torch.randint(-2 ** 31, 2 ** 31 - 1, (words + GUARD,), dtype=torch.int32, device="cuda", generator=gen)
+
+
+def run_native(lib, store, idx, params, normalize, null_workspace=False):
+    """One occ_augment_batch on guarded buffers -> (img, label, grad, pos) as numpy, and the workspace before / after."""
+    from occlusionenv_amd import _native as nat
+
+    rgb, depth, label, pos, grad = store
+    M, S = rgb.shape[0], rgb.shape[1]
+    n = len(idx)
+    gen = torch.Generator(device="cuda").manual_seed(1000 + n + S)
+    d_rgbl = torch.from_numpy(pack_words(rgb, label)).cuda()
+    d_depth, d_pos, d_grad = torch.from_numpy(depth).cuda(), torch.from_numpy(pos).cuda(), torch.from_numpy(grad).cuda()
+    d_idx = torch.from_numpy(np.asarray(idx, np.int64)).cuda()
+    d_params = None if params is None else torch.from_numpy(np.ascontiguousarray(params).view(np.int32).copy()).cuda()
+    need = C.c_size_t()
+    nat.check(lib.occ_augment_query(S, n, C.byref(need)), "occ_augment_query")
+    sizes = dict(img=n * 4 * S * S, label=n * S * S, grad=n * 2, pos=n * 2, ws=need.value // 4)
+    bufs = {k: _guarded(w, gen) for k, w in sizes.items()}
+    before = {k: b.cpu().numpy().copy() for k, b in bufs.items()}
+    rc = lib.occ_augment_batch(_p(d_rgbl), _p(d_depth), _p(d_pos), _p(d_grad), M, S, _p(d_idx), _p(d_params), n, int(normalize),
+                               _p(bufs["img"]), _p(bufs["label"]), _p(bufs["grad"]), _p(bufs["pos"]),
+                               None if null_workspace else _p(bufs["ws"]), _stream())
+    nat.check(rc, "occ_augment_batch")
+    torch.cuda.synchronize()
+    after = {k: b.cpu().numpy() for k, b in bufs.items()}
+    for k, w in sizes.items():
+        assert np.array_equal(after[k][w:], before[k][w:]), f"guard words of {k} were written"
+    out = (after["img"][: sizes["img"]].view(np.float32).reshape(n, 4, S, S), after["label"][: sizes["label"]].view(np.float32).reshape(n, 1, S, S),
+           after["grad"][: sizes["grad"]].view(np.float32).reshape(n, 2), after["pos"][: sizes["pos"]].view(np.float32).reshape(n, 2))
+    return out, before["ws"][: sizes["ws"]], after["ws"][: sizes["ws"]]
+
+
+def assert_same_bits(got, want):
+    for name, g, w in zip(("img", "label", "grad", "pos"), got, want):
+        assert g.dtype == np.float32 and w.dtype == np.float32 and g.shape == w.shape, name
+        bad = g.view(np.uint32) != w.view(np.uint32)
+        assert not bad.any(), f"{name}: {int(bad.sum())} of {bad.size} words differ, first at {tuple(np.argwhere(bad)[0])}"
+
+
+def mixed_params(n, seed, orders=None):
+    """n jittered records with seeded factors over the jitter's ranges, mixed flips, the given orders."""
+    rng = np.random.default_rng(seed)
+    p = am.make_params(n)
+    p["brightness"], p["contrast"] = rng.uniform(0.7, 1.3, n), rng.uniform(0.7, 1.3, n)
+    p["saturation"], p["hue_shift"] = rng.uniform(0.8, 1.2, n), rng.integers(0, 256, n)
+    p["jitter"], p["flip"] = 1, np.arange(n) % 2
+    for i in range(n):
+        p["order"][i] = am.pack_order(orders[i] if orders else ORDERS[int(rng.integers(24))])
+    return p
+
+
+def check(lib, store, idx, params, normalize):
+    got, _, _ = run_native(lib, store, idx, params, normalize)
+    assert_same_bits(got, am.batch(*store, idx, params, normalize))
+    return got
+
+
+@pytest.mark.parametrize("normalize", [True, False])
+def test_rows_shorter_than_a_wave(lib, normalize):
+    """S = 32, n = 5: contrast first, in the middle (twice) and last, one sample without jitter, mixed flips, a repeated
+    frame and frames out of order."""
+    store = make_store(6, 32, 1)
+    orders = [(1, 0, 2, 3), (0, 1, 3, 2), (3, 2, 1, 0), (2, 3, 0, 1), (0, 2, 3, 1)]
+    p = mixed_params(5, 2, orders)
+    p["jitter"][3] = 0
+    p["flip"] = [1, 0, 1, 1, 0]
+    got = check(lib, store, [4, 1, 4, 0, 5], p, normalize)
+    assert not np.array_equal(got[0][0], got[0][2])  # the same frame under two draws
+
+
+def test_every_order_at_a_size_off_the_block(lib):
+    """S = 40: 1600 pixels are six blocks and a quarter; all 24 orders."""
+    store = make_store(3, 40, 3)
+    p = mixed_params(24, 4, ORDERS)
+    check(lib, store, [i % 3 for i in range(24)], p, True)
+
+
+def test_three_blocks_with_a_partial_last_one(lib):
+    assert (S_ODD * S_ODD + BLOCK - 1) // BLOCK == 3 and S_ODD == 23
+    store = make_store(2, S_ODD, 5)
+    check(lib, store, [1, 0, 1], mixed_params(3, 6, [(0, 3, 1, 2), (2, 1, 0, 3), (3, 0, 2, 1)]), True)
+
+
+def test_more_partials_than_threads(lib):
+    assert S_WIDE == 264 and (S_WIDE * S_WIDE + BLOCK - 1) // BLOCK == 273
+    store = make_store(2, S_WIDE, 7)
+    check(lib, store, [1, 0], mixed_params(2, 8, [(0, 2, 1, 3), (3, 1, 2, 0)]), True)
+
+
+def test_contrast_mean_rounding_edge(lib):
+    """Mean L exactly k + 0.5 (rounds up) and k + 0.5 - 1 / S^2 (rounds down), contrast first in the chain."""
+    S, k = 32, 101
+    rgb = np.stack([am.mean_edge_image(S, k, False), am.mean_edge_image(S, k, True)])
+    z = np.zeros((2, S, S))
+    store = (rgb, z.astype(np.int16), z.astype(np.uint8), np.zeros((2, 2), np.float32), np.zeros((2, 2), np.float32))
+    for f in (0.7, 1.3):
+        p = am.make_params(2)
+        p["contrast"], p["jitter"], p["order"] = f, 1, am.pack_order((1, 0, 2, 3))
+        got = check(lib, store, [0, 1], p, False)
+        # away from the one pixel that differs, the two images differ only through the rounded mean
+        assert not np.array_equal(got[0][0][:, 1:], got[0][1][:, 1:])
+
+
+def test_factors_at_the_ends_of_their_ranges(lib):
+    store = make_store(2, 32, 9)
+    assert store[0].min() == 0 and store[0].max() == 255
+    p = am.make_params(4)
+    p["jitter"] = 1
+    p["brightness"], p["contrast"], p["saturation"] = [0.7, 1.3, 0.7, 1.3], [0.7, 1.3, 1.3, 0.7], [0.8, 1.2, 1.2, 0.8]
+    p["hue_shift"] = [231, 25, 25, 231]
+    for i, o in enumerate([(0, 1, 2, 3), (1, 2, 3, 0), (2, 3, 0, 1), (3, 0, 1, 2)]):
+        p["order"][i] = am.pack_order(o)
+    check(lib, store, [0, 1, 1, 0], p, True)
+
+
+def test_hue_shifts(lib):
+    store = make_store(1, 32, 10)
+    p = am.make_params(4)
+    p["jitter"], p["hue_shift"] = 1, [0, 1, 230, 255]
+    got = check(lib, store, [0, 0, 0, 0], p, False)
+    # even a shift of 0 goes through HSV and back, which is not the identity
+    plain = am.batch(*store, [0], None, False)[0]
+    assert not np.array_equal(got[0][0], plain[0])
+
+
+def test_depth_outside_a_byte_passes_unclipped(lib):
+    store = make_store(2, 32, 11)
+    got = check(lib, store, [0, 1], None, False)
+    f32 = np.float32
+    assert np.all(got[0][:, 3, 2, ::3] == f32(-20) / f32(255)) and np.all(got[0][:, 3, 3, ::3] == f32(300) / f32(255))
+    got = check(lib, store, [0, 1], None, True)
+    assert np.all(got[0][:, 3, 3, ::3] == (f32(300) / f32(255) - f32(0.5)) / f32(0.25))
+
+
+def test_no_params_is_one_launch_with_the_bits_of_jitter_off(lib):
+    """params == NULL: the sum pass cannot run (it reads params), the workspace is neither needed nor written, and the
+    outputs are those of records with jitter = 0 and flip = 0."""
+    store = make_store(3, 40, 12)
+    idx = [2, 0, 2, 1]
+    off = mixed_params(4, 13)
+    off["jitter"], off["flip"] = 0, 0
+    a, ws_before, ws_after = run_native(lib, store, idx, None, True)
+    assert np.array_equal(ws_before, ws_after)
+    b, ws_before, ws_after = run_native(lib, store, idx, off, True)
+    assert np.array_equal(ws_before, ws_after)  # samples without jitter leave the sum pass before they write
+    c, _, _ = run_native(lib, store, idx, None, True, null_workspace=True)
+    assert_same_bits(a, b)
+    assert_same_bits(a, c)
+    assert_same_bits(a, am.batch(*store, idx, None, True))
+    on = mixed_params(4, 13)
+    _, ws_before, ws_after = run_native(lib, store, idx, on, True)
+    assert not np.array_equal(ws_before, ws_after)
+
+
+def test_two_calls_give_the_same_bits(lib):
+    store = make_store(3, 40, 14)
+    p = mixed_params(6, 15)
+    a, _, _ = run_native(lib, store, [0, 1, 2, 2, 1, 0], p, True)
+    b, _, _ = run_native(lib, store, [0, 1, 2, 2, 1, 0], p, True)
+    assert_same_bits(a, b)
+
+
+@pytest.fixture(scope="module")
+def dataset():
+    from occlusionenv_amd.devdata import DeviceDataset
+
+    store = make_store(11, 32, 20)
+    ds = DeviceDataset.from_arrays(*store, "cuda", split="train", grad_mode="raw")
+    return store, ds
+
+
+def test_batch_through_the_python_layer(dataset):
+    from occlusionenv_amd import devdata
+
+    store, ds = dataset
+    idx = [7, 3, 7, 10, 0]
+    p = devdata.draw_params(5, torch.Generator().manual_seed(21))
+    for params in (p, None):
+        for normalize in (True, False):
+            got = ds.batch(torch.tensor(idx), params, normalize=normalize)
+            assert all(t.is_cuda and t.dtype == torch.float32 for t in got)
+            assert_same_bits([t.cpu().numpy() for t in got], am.batch(*store, idx, params, normalize))
+    for bad in ([11], [-1], []):
+        with pytest.raises(ValueError):
+            ds.batch(bad)
+    with pytest.raises(ValueError):
+        ds.batch([0, 1], p)
+
+
+def _epoch(loader):
+    return [[t.cpu() for t in b] for b in loader]
+
+
+def test_loader_epochs(dataset):
+    store, ds = dataset
+    loader = ds.loader(batch_size=4, generator=torch.Generator().manual_seed(31))
+    assert len(loader) == 3 and loader.train
+    first, second = _epoch(loader), _epoch(loader)
+    assert [b[0].shape[0] for b in first] == [4, 4, 3]
+    again = _epoch(ds.loader(batch_size=4, generator=torch.Generator().manual_seed(31)))
+    for a, b in zip(first, again):
+        assert all(torch.equal(x, y) for x, y in zip(a, b))  # the same seed repeats the epoch
+    assert not all(torch.equal(a[0], b[0]) for a, b in zip(first, second))  # two epochs differ
+    # pos identifies the frame (grad_mode="raw" keeps it apart from grad): every frame exactly once per epoch
+    for epoch in (first, second):
+        pos = torch.cat([b[3] for b in epoch]).numpy()
+        order = [int(np.flatnonzero((store[3] == row).all(1))[0]) for row in pos]
+        assert sorted(order) == list(range(11))
+    assert len(_epoch(ds.loader(batch_size=4, drop_last=True))) == 2
+    # a validation loader: in order, no jitter, no flip
+    val = _epoch(ds.loader(batch_size=11, shuffle=False, train=False))
+    assert_same_bits([t.numpy() for t in val[0]], am.batch(*store, np.arange(11), None, True))
+    # a kept batch is not touched by later ones
+    it = iter(ds.loader(batch_size=4, generator=torch.Generator().manual_seed(31)))
+    kept = next(it)
+    copies = [t.clone() for t in kept]
+    for _ in it:
+        pass
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(kept, copies))
+
+
+def test_pretrain_epoch_runs_from_a_loader_batch(dataset):
+    """One step of harness.pretrain_epoch at N = 2, S = 32 on what the loader yields, harness.py unchanged."""
+    from occlusionenv_amd import harness
+    from occlusionenv_amd.devdata import DeviceDataset
+    from occlusionenv_amd.encoder import FrozenEncoder
+    from tests import bn_train_model as btm
+
+    store, _ = dataset
+    ds = DeviceDataset.from_arrays(*(a[:2] for a in store), "cuda", split="train")
+    assert torch.allclose((ds.grad ** 2).sum(1), torch.ones(2, device="cuda"))  # (sin, cos)
+    enc = FrozenEncoder.from_state_dict(btm.state_dict("golden", "separable"), preset="ppo", dilation=2, residual=True)
+    res = harness.pretrain_epoch(enc, ds.loader(batch_size=2, generator=torch.Generator().manual_seed(41)), native_optimizer=True)
+    assert res["batches"] == 1 and res["pixels"] == 2 * 32 * 32 and np.isfinite(res["loss"])
+
+
+def test_pretrain_runs_an_epoch_from_two_loaders(dataset):
+    """harness.pretrain(net, ds_train.loader(), ds_val.loader(), epochs) as it stands: a training epoch of two batches with
+    jitter and flip, then the validation pass over a loader without them."""
+    from occlusionenv_amd import harness
+    from occlusionenv_amd.devdata import DeviceDataset
+    from occlusionenv_amd.encoder import FrozenEncoder
+    from tests import bn_train_model as btm
+
+    store, _ = dataset
+    train = DeviceDataset.from_arrays(*(a[:4] for a in store), "cuda", split="train")
+    val = DeviceDataset.from_arrays(*(a[4:7] for a in store), "cuda", split="val")
+    enc = FrozenEncoder.from_state_dict(btm.state_dict("golden", "separable"), preset="ppo", dilation=2, residual=True)
+    tl, vl = train.loader(batch_size=2, generator=torch.Generator().manual_seed(42)), val.loader(batch_size=3)
+    assert tl.train and not vl.train
+    out = harness.pretrain(enc, tl, vl, epochs=1)
+    row = out["rows"][0]
+    assert row["train"]["batches"] == 2 and row["val"]["batches"] == 1 and row["val"]["pixels"] == 3 * 32 * 32
+    assert np.isfinite(row["train"]["loss"]) and np.isfinite(row["val"]["loss"]) and out["best_epoch"] == 0
