@@ -739,6 +739,45 @@ int occ_augment_batch(const uint32_t* rgbl, const int16_t* depth, const float* p
                       float* out_label, float* out_grad, float* out_pos, void* workspace, void* stream);
 
 /*
+ * Packing rendered frames into the resident dataset (additive in ABI 12; csrc/occ_datapack.hpp): what
+ * dataset_io.RunWriter.write_frame (datasetGenerator.py:102-112) followed by DeviceDataset.from_directory at the same size
+ * does to a frame between the engine's step and the store above, without the files and without the JPEG.
+ *
+ * occ_dataset_pack(obs, alpha, alpha_stride, n, img, slot, rgbl, depth, m_frames, label_mode, stream)
+ *   obs    float[n][4][S][S]  the engine's observation (S = img): three colour planes and the view depth, -1 = background
+ *   alpha  read at alpha[(env * S * S + pixel) * alpha_stride]: 1 = an (n,S,S) image, 4 = the alpha channel of the
+ *          (n,S,S,4) full_state when the pointer is that of its channel 3 (the convention of occ_seg_metrics)
+ *   slot   int64[n] on the device: the frame of the store env i writes.  Any value outside [0, m_frames) skips env i; no
+ *          address is formed from it.  Keeping the in-range slots of one call distinct is the caller's duty.
+ *   rgbl, depth  the store of occ_augment_batch, m_frames frames; frames no slot names are not touched
+ * Per written pixel, with u8(x) = clip(rint((double)x * 255.0), 0, 255), round-half-even, NaN -> 0 (skimage's
+ * img_as_ubyte as dataset_io._ubyte states it):
+ *   colours  the word's R byte is u8(obs[2]), G is u8(obs[1]), B is u8(obs[0]): the writer saves BGR (cv2.imwrite of an
+ *            RGB array), the reader opens the file as RGB
+ *   depth    d = obs[3], d == -1 -> 0; t = d * 51.0f, one f32 product; stored (int16) is the truncation of t, with what the
+ *            C cast leaves undefined defined: t <= 0 or NaN -> 0, t >= 255 -> 255
+ *   label    a8 = u8(alpha), then with
+ *            label_mode 0: PIL's convert("1") of the S x S image a8, which is what the reader applies to the Occl file:
+ *              Floyd-Steinberg error diffusion exactly as Convert.c tobilevel does it.  int errors[S + 1] starts at zero
+ *              and persists across rows; per row l = l0 = l1 = 0, and for x = 0 .. S - 1:
+ *                l = clip8(a8[x] + (l + errors[x + 1]) / 16)        (C division: toward zero)
+ *                out = l > 128 ? 255 : 0;  e = l - out
+ *                errors[x] = 3 e + l0;  l0 = 5 e + l1;  l1 = e;  l = 7 e
+ *              and errors[S] = l0 after the row.  The label is out != 0.
+ *            label_mode 1: alpha > 0.5f, the rule pretrainer.py:134 and occ_seg_metrics apply to a target (NOT what the
+ *              files give: soft silhouette edges dither)
+ *            stored as 0 or 1 in bits 24..31 of the word.
+ * At most two launches on `stream`: a point pass over the pixels, which for label_mode 0 parks a8 in the label byte, and
+ * the dither pass in place on that byte (one wave per frame, rows of a 64-row band two columns apart; skipped for
+ * label_mode 1).  Nothing is allocated or synchronised, no atomics, integer arithmetic after the three conversions: the
+ * store is bitwise the same from call to call.  tests/datapack_model.py is this arithmetic in numpy, checked against PIL.
+ * OCC_ERR_ARG before any launch for a null pointer, img < 1, img * img > 2^24, n < 1, n > 65535, m_frames < 1,
+ * alpha_stride < 1 or a label_mode other than 0 and 1.
+ */
+int occ_dataset_pack(const float* obs, const float* alpha, int alpha_stride, int n, int img, const int64_t* slot,
+                     uint32_t* rgbl, int16_t* depth, int m_frames, int label_mode, void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

@@ -51,6 +51,8 @@
 //   occ_augment_*       the pretrainer's input pipeline on a device-resident dataset (occ_augment.hpp): gather by frame
 //                       index, torchvision's colour jitter with PIL's roundings, flip, /255 and Normalize: a luminance-
 //                       sum pass for contrast's mean and an output pass
+//   occ_datapack_*      rendered frames into that dataset's store (occ_datapack.hpp): img_as_ubyte, depth * 51 and the
+//                       occlusion label per pixel, then PIL's convert("1") error diffusion in place, one wave per frame
 //
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
@@ -85,6 +87,7 @@ namespace occ {
 #include "occ_criterion.hpp"
 #include "occ_adamw.hpp"
 #include "occ_augment.hpp"
+#include "occ_datapack.hpp"
 
 }  // namespace occ
 
@@ -998,6 +1001,23 @@ extern "C" int occ_augment_batch(const uint32_t* rgbl, const int16_t* depth, con
                            (uint32_t*)workspace);
     hipLaunchKernelGGL(occ_augment_out_kernel, grid, dim3(kAugBlock), 0, st, rgbl, depth, pos, grad, m_frames, img, idx, params,
                        (const uint32_t*)workspace, normalize, out_img, out_label, out_grad, out_pos);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- rendered frames into the resident dataset (occ_datapack.hpp) ----------------------------------------------------------
+extern "C" int occ_dataset_pack(const float* obs, const float* alpha, int alpha_stride, int n, int img, const int64_t* slot,
+                                uint32_t* rgbl, int16_t* depth, int m_frames, int label_mode, void* stream) {
+    if (!non_null(obs, alpha, slot, rgbl, depth)) return OCC_ERR_ARG;
+    if (img < 1 || (int64_t)img * img > (int64_t)kPackMaxPixels || n < 1 || n > 65535 || m_frames < 1 || alpha_stride < 1 ||
+        (label_mode != 0 && label_mode != 1))
+        return OCC_ERR_ARG;
+    static_assert((int64_t)kDitherMaxImg * kDitherMaxImg == (int64_t)kPackMaxPixels, "the errors row in LDS covers every legal img");
+    hipStream_t st = (hipStream_t)stream;
+    const int pixels = img * img;
+    hipLaunchKernelGGL(occ_datapack_point_kernel, dim3((pixels + kPackBlock - 1) / kPackBlock, n), dim3(kPackBlock), 0, st, obs, alpha,
+                       alpha_stride, pixels, slot, rgbl, depth, m_frames, label_mode);
+    if (label_mode == 0)
+        hipLaunchKernelGGL(occ_datapack_dither_kernel, dim3(n), dim3(kDitherRows), 0, st, slot, rgbl, img, m_frames);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

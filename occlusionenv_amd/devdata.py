@@ -14,6 +14,14 @@ is 0 or 1, as ``dataset_io.OcclusionDataset`` returns it.
 Batches are ``(img, occlusion, grad, pos)``, the reference's order, which is what ``harness.pretrain_epoch`` and
 ``harness.validate_pretrained`` unpack.  There is no CPU path: a store on the CPU (``device="cpu"``) can be inspected
 (``unpack``) but ``batch`` raises.
+
+The store can also be filled on the device (csrc/occ_datapack.hpp, ``occ_dataset_pack``): ``DeviceDataset.empty`` plus
+``put`` per engine step, which is what ``generate_resident`` does in ``dataset_io.generate``'s loop.  ``put`` gives a frame
+the bits the writer and ``from_directory`` at the same size would (``tests/datapack_model.py``), the JPEG apart.  Not
+reproduced there: the resize (the env renders at the dataset's size; the reference renders 512 x 512 and resizes to
+256 x 256 with PIL's bicubic filter), and the pairing ``from_directory`` inherits from the reference's lexicographic file
+sort (``0, 1, 10, .., 19, 2, ..`` against numerically ordered labels: images of runs with more than 10 frames get other
+frames' ``pos`` / ``grad``); a generated store is run-major, frame ``j`` numeric, every image with its own labels.
 """
 from __future__ import annotations
 
@@ -32,6 +40,9 @@ from . import _native as nat
 PARAMS_DTYPE = np.dtype([("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue_shift", "<i4"),
                          ("order", "<i4"), ("jitter", "<i4"), ("flip", "<i4"), ("pad", "<i4")])
 assert PARAMS_DTYPE.itemsize == C.sizeof(nat.OccAugmentParams) == 32
+
+#: ``label_mode`` of ``occ_dataset_pack``
+LABEL_MODES = {"dither": 0, "threshold": 1}
 
 
 def draw_params(n: int, generator: torch.Generator, jitter=(0.3, 0.3, 0.2, 0.1), flip: float = 0.5) -> np.ndarray:
@@ -82,7 +93,8 @@ def sincos_grad(grad: np.ndarray) -> np.ndarray:
 
 class DeviceDataset:
     """A decoded, resized dataset resident on ``device``: ``rgbl`` (M,S,S) int32 words ``R | G << 8 | B << 16 | label << 24``,
-    ``depth`` (M,S,S) int16, ``pos`` and ``grad`` (M,2) f32.  Build it with ``from_directory`` or ``from_arrays``."""
+    ``depth`` (M,S,S) int16, ``pos`` and ``grad`` (M,2) f32.  Build it with ``from_directory`` or ``from_arrays``, or
+    ``empty`` and ``put`` (``generate_resident``)."""
 
     def __init__(self, rgbl: torch.Tensor, depth: torch.Tensor, pos: torch.Tensor, grad: torch.Tensor, split: str = ""):
         M, S = rgbl.shape[0], rgbl.shape[1]
@@ -151,6 +163,58 @@ class DeviceDataset:
             lab[i] = np.asarray(Image.open(labels[i]).convert("1").resize(size))
         return cls.from_arrays(rgb, dep, lab, np.concatenate(pos, 0), np.concatenate(grad, 0), device, split=split,
                                grad_mode=grad_mode)
+
+    @classmethod
+    def empty(cls, m_frames: int, size: int, device, split: str = ""):
+        """A zeroed store of ``m_frames`` frames of ``size`` x ``size`` pixels on ``device``, to be filled with ``put``."""
+        M, S, dev = int(m_frames), int(size), torch.device(device)
+        if M < 1 or S < 1:
+            raise ValueError("DeviceDataset.empty: at least one frame of at least one pixel")
+        return cls(torch.zeros((M, S, S), dtype=torch.int32, device=dev), torch.zeros((M, S, S), dtype=torch.int16, device=dev),
+                   torch.zeros((M, 2), dtype=torch.float32, device=dev), torch.zeros((M, 2), dtype=torch.float32, device=dev),
+                   split=split)
+
+    def put(self, obs: torch.Tensor, full_state: torch.Tensor, slots, pos=None, grad=None, label: str = "dither") -> None:
+        """Write the frames of one engine step into the store, on the device, in one ``occ_dataset_pack`` call
+        (csrc/occ_datapack.hpp): env ``i`` of ``obs`` (n,4,S,S) and ``full_state`` (n,S,S,4; its alpha channel is the
+        occlusion image; an (n,S,S) alpha image is taken too) becomes frame ``slots[i]`` with the bits
+        ``dataset_io.RunWriter`` and ``from_directory`` at the same size would give it, the JPEG apart: ``img_as_ubyte``
+        colours with B and R swapped, ``depth * 51`` truncated, and the label by ``label="dither"`` (PIL's
+        ``convert("1")`` of the 8-bit alpha, what the reader does to the file) or ``"threshold"`` (``alpha > 0.5``, the
+        rule of ``pretrainer.py:134``).  ``slots``: n int64 on the device or the host; an env whose slot is outside
+        ``[0, len(self))`` is skipped, in-range slots must be distinct.  ``pos`` / ``grad``: (n,2) rows stored as they are
+        for the slots in range (an indexed copy; selecting the rows reads the mask back, so a caller that must not
+        synchronise keeps its labels itself, as ``generate_resident`` does).  There is no resize: ``obs`` has the
+        store's size."""
+        if label not in LABEL_MODES:
+            raise ValueError("label: 'dither' or 'threshold'")
+        S = self.size
+        if obs.ndim != 4 or obs.shape[1] != 4 or obs.shape[-1] != S or obs.shape[-2] != S:
+            raise ValueError("put: obs (n,4,%d,%d): the env renders at the dataset's size, there is no resize" % (S, S))
+        n = int(obs.shape[0])
+        if tuple(full_state.shape) not in ((n, S, S, 4), (n, S, S)):
+            raise ValueError("put: full_state (n,%d,%d,4) or an alpha image (n,%d,%d)" % (S, S, S, S))
+        if not 1 <= n <= 65535:
+            raise ValueError("put: 1 .. 65535 envs")
+        s = torch.as_tensor(slots)
+        if s.is_floating_point() or s.dtype == torch.bool or s.numel() != n:
+            raise ValueError("put: slots are n integers")
+        if self.device.type != "cuda":
+            raise nat.NativeError("DeviceDataset.put runs on the GPU only (this store is on %s); there is no CPU path" % self.device)
+        s = s.reshape(n).to(self.device, torch.int64).contiguous()
+        obs = obs.detach().to(self.device, torch.float32).contiguous()
+        fs = full_state.detach().to(self.device, torch.float32).contiguous()
+        stride = 4 if fs.ndim == 4 else 1
+        with torch.cuda.device(self.device):
+            nat.check(nat.load().occ_dataset_pack(nat.ptr(obs), nat.ptr(fs, 12 if stride == 4 else 0), stride, n, S, nat.ptr(s),
+                                                  nat.ptr(self.rgbl), nat.ptr(self.depth), len(self), LABEL_MODES[label],
+                                                  nat.stream_ptr(self.device)), "occ_dataset_pack")
+            if pos is not None or grad is not None:
+                ok = (s >= 0) & (s < len(self))
+                for dst, src in ((self.pos, pos), (self.grad, grad)):
+                    if src is not None:
+                        src = torch.as_tensor(src).to(self.device, torch.float32).reshape(n, 2)
+                        dst[s[ok]] = src[ok]
 
     def unpack(self, i: int):
         """Frame ``i`` of the store on the host: ``(rgb (S,S,3) uint8, depth (S,S) int16, label (S,S) uint8)``."""
@@ -242,3 +306,66 @@ class EpochLoader:
         for b in range(len(self)):
             lo, hi = b * B, min(M, (b + 1) * B)
             yield ds._run(order[lo:hi], None if params is None else params[lo:hi], self.normalize)
+
+
+def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5e-2, generator=None, max_steps: int = 0,
+                      label: str = "dither", grad_mode: str = "sincos", split: str = "train") -> DeviceDataset:
+    """``dataset_io.generate``'s loop (datasetGenerator.py:76-124) into a ``DeviceDataset`` instead of files: ``num_runs``
+    runs of ``num_frames`` frames at the env's own size, frame ``j`` of run ``r`` at index ``r * num_frames + j`` with its
+    own ``pos`` (elevation, azimuth) and ``grad``.  Nothing of a frame leaves the device: every step is one
+    ``DeviceDataset.put``, and the frame counters, the mask of written frames and the slots are device tensors; one scalar
+    per step comes back, for the loop condition.
+
+    The semantics are ``generate``'s: one scene per run, the engine stepped directly after ``reset()`` and ``_drain()``, a
+    frame whose gradient is NaN retried with the SAME action without advancing that run's counter, a fresh action only
+    after a written frame, ``RuntimeError`` after ``max_steps`` (default ``50 * num_frames``) steps of a round.  With the
+    same ``generator`` and ``num_runs == venv.num_envs`` the actions are the ones ``generate`` draws.  ``num_runs`` above
+    ``venv.num_envs`` runs in rounds of ``num_envs`` with a ``reset()`` between them; the envs of a last partial round
+    beyond ``num_runs`` write nothing.  ``grad_mode="sincos"`` turns the raw f32 gradients into ``sincos_grad`` at the end
+    (M x 2 values, on the host: the bits ``from_directory`` computes from the pickled values), ``"raw"`` keeps them."""
+    if grad_mode not in ("sincos", "raw"):
+        raise ValueError("grad_mode: 'sincos' or 'raw'")
+    if label not in LABEL_MODES:
+        raise ValueError("label: 'dither' or 'threshold'")
+    num_runs, num_frames = int(num_runs), int(num_frames)
+    if num_runs < 1 or num_frames < 1:
+        raise ValueError("generate_resident: at least one run of one frame")
+    eng, N = venv.engine, venv.num_envs
+    dev, M = eng.device, num_runs * num_frames
+    ds = DeviceDataset.empty(M, eng.S, dev, split=split)
+    # row M takes what the envs without a frame in a step scatter
+    elaz = torch.zeros((M + 1, 2), dtype=torch.float32, device=dev)
+    graw = torch.zeros((M + 1, 2), dtype=torch.float32, device=dev)
+    limit = max_steps or 50 * num_frames
+    for first in range(0, num_runs, N):
+        venv.reset()
+        venv._drain()  # no auto-reset report may be pending while the engine is driven directly
+        run = first + torch.arange(N, dtype=torch.int64, device=dev)
+        live = run < num_runs
+        frame = torch.zeros(N, dtype=torch.int64, device=dev)
+        action = lr * torch.randn(N, 2, device=dev, generator=generator)
+        steps = 0
+        while True:
+            pending = live & (frame < num_frames)
+            if not bool(pending.any()):  # the one value read back per step
+                break
+            if steps >= limit:
+                raise RuntimeError("generate_resident(): gradients stayed NaN for %d steps" % steps)
+            steps += 1
+            a = action.clone().requires_grad_(True)
+            obs, rewards, dones, full_state, loss = eng.step(a)
+            rewards.sum().backward()
+            g = a.grad.detach()
+            good = pending & ~torch.isnan(g).any(1)
+            slot = torch.where(good, run * num_frames + frame, torch.full_like(frame, -1))
+            ds.put(obs, full_state, slot, label=label)
+            row = torch.where(good, slot, torch.full_like(frame, M))
+            elaz[row] = torch.stack([eng.elevation.reshape(N), eng.azimuth.reshape(N)], 1).to(torch.float32)
+            graw[row] = g.to(torch.float32)
+            fresh = lr * torch.randn(N, 2, device=dev, generator=generator)
+            frame = frame + good.to(torch.int64)
+            action = torch.where(good[:, None], fresh, action)  # a new action only after a frame was written
+    ds.pos = elaz[:M].contiguous()
+    g = graw[:M].cpu().numpy().astype(np.float64)
+    ds.grad = torch.from_numpy(np.ascontiguousarray(sincos_grad(g) if grad_mode == "sincos" else g.astype(np.float32))).to(dev)
+    return ds
