@@ -1,10 +1,10 @@
 """Host-side checks of the joint training step with batch-statistics BatchNorm (csrc/occ_bn_train.hpp,
 ``from_encoder(enc, batch_stats=True)``): the A / B / C form of the BatchNorm backward is the gradient, the running-average
-rule of ``nettrain`` is nn.BatchNorm2d's, the three entry points are exported and reject what they do not support before
-anything is launched, the workspace query is the documented layout, and every case whose gradients the GPU test judges is
-well conditioned: PyTorch's own f32 run of it agrees with the f64 model within 1e-4 for every tensor.  No GPU."""
+rule of ``nettrain`` is nn.BatchNorm2d's, the workspace query is the documented layout, and every case whose gradients the GPU
+test judges is well conditioned: PyTorch's own f32 run of it agrees with the f64 model within 1e-4 for every tensor.  The
+argument contract of the three entry points is checked from the table of tests/train_abi.py by
+tests/test_train_abi_host.py.  No GPU."""
 import ctypes as C
-import os
 
 import pytest
 import torch
@@ -15,7 +15,6 @@ from tests import bn_train_model as m
 from tests import fullnet_train_model as ftm
 
 SYMBOLS = ("occ_fullnet_bn_train_workspace_query", "occ_fullnet_bn_train_forward", "occ_fullnet_bn_backward")
-P16 = C.c_void_p(4096)  # never dereferenced: every call below is rejected before a launch
 FORMS = {"dense": dict(dilation=1, separable=0), "separable": dict(dilation=2, separable=1)}
 
 
@@ -85,19 +84,6 @@ def test_running_average_rule_is_batchnorm2d():
             assert torch.allclose(buffers[st][1], bn.running_var, rtol=1e-12, atol=1e-14), st
 
 
-def test_symbols_declared_exported_and_abi_stays_12():
-    lib = C.CDLL(nat.LIB_PATH)
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "occlusionenv_amd.h")).read()
-    for name in SYMBOLS:
-        assert hasattr(lib, name) and name in nat.SYMBOLS and f"int {name}(" in header
-    assert nat.load().occ_abi_version() == 12 == nat.ABI_VERSION
-    # the arguments of occ_fullnet_*, the forward with bn_stats in front of the stream
-    assert nat.SYMBOLS[SYMBOLS[0]] == nat.SYMBOLS["occ_fullnet_train_workspace_query"]
-    fwd = nat.SYMBOLS["occ_fullnet_train_forward"][1]
-    assert nat.SYMBOLS[SYMBOLS[1]][1] == fwd[:-1] + [C.c_void_p] + fwd[-1:]
-    assert nat.SYMBOLS[SYMBOLS[2]] == nat.SYMBOLS["occ_fullnet_backward"]
-
-
 @pytest.mark.parametrize("form", sorted(FORMS))
 def test_workspace_query_is_the_documented_layout(form):
     lib = nat.load()
@@ -114,61 +100,6 @@ def test_workspace_query_is_the_documented_layout(form):
     assert m.extra_ws_bytes(256, 8) == 29952 + 3072 + 256 * 8 * 1 * 2 * 8
     assert m.extra_ws_bytes(1024, 2) == 29952 + 3072 + 8 * 2 * 256 * 2 * 8
     assert m.extra_ws_bytes(32, 2) == 29952 + 3072 + 256 * 2 * 1 * 2 * 8
-
-
-@pytest.mark.parametrize("form", sorted(FORMS))
-def test_argument_checks_need_no_gpu(form):
-    lib = nat.load()
-    kw = FORMS[form]
-    good = _cfg(64, **kw)
-    big = 1 << 40
-    rc, need_ws, need_sc = _query(lib, SYMBOLS[0], 64, 2, **kw)
-    assert rc == 0
-    # every BatchNorm needs two values per channel: N (S / 32)^2 >= 2
-    assert _query(lib, SYMBOLS[0], 32, 1, **kw)[0] == 1 and _query(lib, SYMBOLS[0], 32, 2, **kw)[0] == 0
-    assert _query(lib, SYMBOLS[0], 64, 1, **kw)[0] == 0
-    assert _query(lib, SYMBOLS[0], 48, 2, **kw)[0] == 1 and _query(lib, SYMBOLS[0], 16, 8, **kw)[0] == 1  # S % 32, S < 32
-    assert _query(lib, SYMBOLS[0], 64, 0, **kw)[0] == 1 and _query(lib, SYMBOLS[0], 64, 65536, **kw)[0] == 1
-    ws, sc = C.c_size_t(), C.c_size_t()
-    assert lib.occ_fullnet_bn_train_workspace_query(None, 2, C.byref(ws), C.byref(sc)) == 1
-    assert lib.occ_fullnet_bn_train_workspace_query(C.byref(good), 2, None, C.byref(sc)) == 1
-    assert lib.occ_fullnet_bn_train_workspace_query(C.byref(good), 2, C.byref(ws), None) == 1
-    bad_cfgs = [_cfg(48, **kw), _cfg(16, **kw), _cfg(64, residual=2, **kw), _cfg(64, dilation=3, separable=kw["separable"]),
-                _cfg(64, dilation=2, separable=0), _cfg(64, dilation=1, separable=2)]
-    # occ_fullnet_bn_train_forward(cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, bn_stats, stream)
-    full = [C.byref(good), P16, P16, P16, 2, P16, big, P16, P16, P16, None]
-    for i in (0, 1, 2, 3, 5, 7, 8, 9):
-        args = list(full)
-        args[i] = None
-        assert lib.occ_fullnet_bn_train_forward(*args) == 1, i
-    for bad in bad_cfgs:
-        assert lib.occ_fullnet_bn_train_forward(C.byref(bad), *full[1:]) == 1
-    for n in (0, 65536):
-        assert lib.occ_fullnet_bn_train_forward(*full[:4], n, *full[5:]) == 1
-    assert lib.occ_fullnet_bn_train_forward(C.byref(_cfg(32, **kw)), P16, P16, P16, 1, *full[5:]) == 1  # (S, N) = (32, 1)
-    assert lib.occ_fullnet_bn_train_forward(*full[:6], need_ws - 1, *full[7:]) == 1
-    assert lib.occ_fullnet_bn_train_forward(*full[:5], C.c_void_p(4096 + 8), *full[6:]) == 1  # ws not 16-byte aligned
-    assert lib.occ_fullnet_bn_train_forward(*full[:8], C.c_void_p(4096 + 8), P16, None) == 1  # prob not 16-byte aligned
-    # occ_fullnet_bn_backward(cfg, enc_packed, dec_packed, n_env, ws, ws_bytes, grad_feats, grad_prob, scratch,
-    #                         scratch_bytes, grad_enc_packed, grad_dec_packed, stream)
-    full = [C.byref(good), P16, P16, 2, P16, big, P16, P16, P16, big, P16, P16, None]
-    for i in (0, 1, 2, 4, 6, 7, 8, 10, 11):
-        args = list(full)
-        args[i] = None
-        assert lib.occ_fullnet_bn_backward(*args) == 1, i
-    for bad in bad_cfgs:
-        assert lib.occ_fullnet_bn_backward(C.byref(bad), *full[1:]) == 1
-    for n in (0, 65536):
-        assert lib.occ_fullnet_bn_backward(*full[:3], n, *full[4:]) == 1
-    assert lib.occ_fullnet_bn_backward(C.byref(_cfg(32, **kw)), P16, P16, 1, *full[4:]) == 1
-    for i, short in ((5, need_ws - 1), (9, need_sc - 1)):
-        args = list(full)
-        args[i] = short
-        assert lib.occ_fullnet_bn_backward(*args) == 1, i
-    for i in (4, 7, 8):  # ws, grad_prob, scratch: 16-byte aligned
-        args = list(full)
-        args[i] = C.c_void_p(4096 + 8)
-        assert lib.occ_fullnet_bn_backward(*args) == 1, i
 
 
 def test_python_keyword_and_modes_need_no_gpu():

@@ -1,8 +1,8 @@
-"""Host-side checks of the separable-encoder training path (csrc/occ_sepenc_bwd.hpp, occlusionenv_amd/septrain.py): the three
-entry points are exported and reject what they do not support before anything is launched, the separable packed layout is
-``encoder.pack_state_dict``'s and round-trips, the restated K split of the pointwise weight gradient is what the library's
-query sizes its scratch for, the split case of the GPU test reaches what its description claims, and the decomposition of one
-separable layer's backward that the kernels implement equals torch autograd in f64.  No GPU."""
+"""Host-side checks of the separable-encoder training path (csrc/occ_sepenc_bwd.hpp, occlusionenv_amd/septrain.py): the
+separable packed layout is ``encoder.pack_state_dict``'s and round-trips, the restated K split of the pointwise weight gradient
+is what the library's query sizes its scratch for, the split case of the GPU test reaches what its description claims, and the
+decomposition of one separable layer's backward that the kernels implement equals torch autograd in f64.  The argument
+contract of the three entry points is checked from the table of tests/train_abi.py by tests/test_train_abi_host.py.  No GPU."""
 import ctypes as C
 import os
 
@@ -16,8 +16,6 @@ from tests import encoder_model
 from tests import encoder_train_model as etm
 from tests import sep_encoder_train_model as m
 
-SYMBOLS = ("occ_sep_encoder_train_workspace_query", "occ_sep_encoder_train_forward", "occ_sep_encoder_backward")
-P16 = C.c_void_p(4096)  # never dereferenced: every call below is rejected before a launch
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "encoder_golden.npz")
 
 
@@ -31,13 +29,6 @@ def _query(lib, img, n, **kw):
     ws, sc = C.c_size_t(), C.c_size_t()
     rc = lib.occ_sep_encoder_train_workspace_query(C.byref(_cfg(img, **kw)), n, C.byref(ws), C.byref(sc))
     return rc, int(ws.value), int(sc.value)
-
-
-def test_symbols_exported_and_abi_stays_12():
-    lib = C.CDLL(nat.LIB_PATH)
-    for name in SYMBOLS:
-        assert hasattr(lib, name) and name in nat.SYMBOLS
-    assert nat.load().occ_abi_version() == 12 == nat.ABI_VERSION
 
 
 def test_queries_equal_the_model():
@@ -67,52 +58,6 @@ def test_queries_equal_the_model():
         assert {p["tps"] for p in m.dpw_plans(img, n)} == {1}
     # the timing shape 128 x 256^2: 256 16-pixel tiles per env at level 0, 32 per slice
     assert col(256, 128, "tps")[:3] == [32, 32, 32] and col(256, 128, "slices")[:3] == [1024] * 3
-
-
-def test_bad_configs_and_arguments_are_rejected_before_a_launch():
-    lib = nat.load()
-    assert _query(lib, 64, 2)[0] == 0 and _query(lib, 64, 2, dilation=1, residual=0)[0] == 0
-    bad_cfgs = (_cfg(64, separable=0), _cfg(64, dilation=3), _cfg(64, residual=2), _cfg(31), _cfg(1025))
-    ws, sc = C.c_size_t(), C.c_size_t()
-    for bad in bad_cfgs:
-        assert lib.occ_sep_encoder_train_workspace_query(C.byref(bad), 2, C.byref(ws), C.byref(sc)) == 1
-    assert _query(lib, 64, 0)[0] == 1 and _query(lib, 64, 65536)[0] == 1
-    assert lib.occ_sep_encoder_train_workspace_query(None, 2, C.byref(ws), C.byref(sc)) == 1
-    assert lib.occ_sep_encoder_train_workspace_query(C.byref(_cfg()), 2, None, C.byref(sc)) == 1
-    assert lib.occ_sep_encoder_train_workspace_query(C.byref(_cfg()), 2, C.byref(ws), None) == 1
-    good = _cfg(64)
-    big = 1 << 40
-    _rc, need_ws, need_sc = _query(lib, 64, 2)
-    # occ_sep_encoder_train_forward(cfg, packed, obs, n_env, ws, ws_bytes, feats, stream)
-    full = [C.byref(good), P16, P16, 2, P16, big, P16, None]
-    for i in (0, 1, 2, 4, 6):
-        args = list(full)
-        args[i] = None
-        assert lib.occ_sep_encoder_train_forward(*args) == 1, i
-    for bad in bad_cfgs:
-        assert lib.occ_sep_encoder_train_forward(C.byref(bad), *full[1:]) == 1
-    for n in (0, 65536):
-        assert lib.occ_sep_encoder_train_forward(*full[:3], n, *full[4:]) == 1
-    assert lib.occ_sep_encoder_train_forward(*full[:5], need_ws - 1, *full[6:]) == 1
-    assert lib.occ_sep_encoder_train_forward(*full[:4], C.c_void_p(4096 + 8), *full[5:]) == 1  # ws not 16-byte aligned
-    # occ_sep_encoder_backward(cfg, packed, n_env, ws, ws_bytes, grad_feats, scratch, scratch_bytes, grad_packed, stream)
-    full = [C.byref(good), P16, 2, P16, big, P16, P16, big, P16, None]
-    for i in (0, 1, 3, 5, 6, 8):
-        args = list(full)
-        args[i] = None
-        assert lib.occ_sep_encoder_backward(*args) == 1, i
-    for bad in bad_cfgs:
-        assert lib.occ_sep_encoder_backward(C.byref(bad), *full[1:]) == 1
-    for n in (0, 65536):
-        assert lib.occ_sep_encoder_backward(*full[:2], n, *full[3:]) == 1
-    for i, short in ((4, need_ws - 1), (7, need_sc - 1)):
-        args = list(full)
-        args[i] = short
-        assert lib.occ_sep_encoder_backward(*args) == 1, i
-    for i in (3, 6):
-        args = list(full)
-        args[i] = C.c_void_p(4096 + 8)
-        assert lib.occ_sep_encoder_backward(*args) == 1, i
 
 
 def test_separable_pack_is_pack_state_dict_and_round_trips():

@@ -1,8 +1,9 @@
 """Host-side checks of the joint training path of the separable network (csrc/occ_fullnet_bwd.hpp,
-occlusionenv_amd/sepfullnet.py): the three entry points are exported and reject what they do not support before anything is
-launched, the workspace query is the restated layout, the two parts' packed layouts round-trip from the whole checkpoint,
-the f64 model of tests/sep_fullnet_train_model.py is the composition of the separable encoder's and the decoder's models,
-the split cases of the GPU test reach what they claim, and every GPU case keeps its gate band small.  No GPU."""
+occlusionenv_amd/sepfullnet.py): the workspace query is the restated layout, the two parts' packed layouts round-trip from
+the whole checkpoint, the f64 model of tests/sep_fullnet_train_model.py is the composition of the separable encoder's and the
+decoder's models, the split cases of the GPU test reach what they claim, and every GPU case keeps its gate band small.  The
+argument contract of the three entry points is checked from the table of tests/train_abi.py by
+tests/test_train_abi_host.py.  No GPU."""
 import ctypes as C
 
 import numpy as np
@@ -16,8 +17,6 @@ from tests import segmenter_model
 from tests import sep_encoder_train_model as stm
 from tests import sep_fullnet_train_model as m
 
-SYMBOLS = ("occ_sep_fullnet_train_workspace_query", "occ_sep_fullnet_train_forward", "occ_sep_fullnet_backward")
-P16 = C.c_void_p(4096)  # never dereferenced: every call below is rejected before a launch
 BAND_CAP = 0.005
 
 
@@ -31,19 +30,6 @@ def _query(lib, img, n, **kw):
     ws, sc = C.c_size_t(), C.c_size_t()
     rc = lib.occ_sep_fullnet_train_workspace_query(C.byref(_cfg(img, **kw)), n, C.byref(ws), C.byref(sc))
     return rc, int(ws.value), int(sc.value)
-
-
-def test_symbols_declared_exported_and_abi_stays_12():
-    import os
-
-    lib = C.CDLL(nat.LIB_PATH)
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "occlusionenv_amd.h")).read()
-    for name in SYMBOLS:
-        assert hasattr(lib, name) and name in nat.SYMBOLS and f"int {name}(" in header
-    assert nat.load().occ_abi_version() == 12 == nat.ABI_VERSION
-    # the arguments are those of the dense joint entry points
-    for sep, dense in zip(SYMBOLS, ("occ_fullnet_train_workspace_query", "occ_fullnet_train_forward", "occ_fullnet_backward")):
-        assert nat.SYMBOLS[sep] == nat.SYMBOLS[dense]
 
 
 def test_workspace_query_is_the_restated_layout():
@@ -68,66 +54,6 @@ def test_workspace_query_is_the_restated_layout():
         assert int(e_ws.value) == m.encoder_ws_bytes(img, n)
         assert sc_b == max(int(e_sc.value), int(d_sc.value))
         assert ws_b < int(e_ws.value) + int(d_ws.value)  # one encoder pass, 0.94 kept d skip buffers
-
-
-def test_query_rejects_what_is_not_supported():
-    lib = nat.load()
-    assert _query(lib, 64, 2)[0] == 0 and _query(lib, 64, 2, dilation=1, residual=0)[0] == 0 and _query(lib, 32, 1)[0] == 0
-    assert _query(lib, 64, 2, separable=0)[0] == 1 and _query(lib, 64, 2, separable=0, dilation=1)[0] == 1  # dense configs
-    assert _query(lib, 64, 2, separable=2)[0] == 1
-    assert _query(lib, 64, 2, dilation=0)[0] == 1 and _query(lib, 64, 2, dilation=3)[0] == 1
-    assert _query(lib, 64, 2, residual=2)[0] == 1
-    assert _query(lib, 48, 2)[0] == 1  # S % 32
-    assert _query(lib, 16, 2)[0] == 1 and _query(lib, 0, 2)[0] == 1 and _query(lib, 1056, 2)[0] == 1
-    assert _query(lib, 64, 0)[0] == 1 and _query(lib, 64, -1)[0] == 1 and _query(lib, 64, 65536)[0] == 1
-    assert _query(lib, 32, 65535)[0] == 0
-    ws, sc = C.c_size_t(), C.c_size_t()
-    assert lib.occ_sep_fullnet_train_workspace_query(None, 2, C.byref(ws), C.byref(sc)) == 1
-    assert lib.occ_sep_fullnet_train_workspace_query(C.byref(_cfg()), 2, None, C.byref(sc)) == 1
-    assert lib.occ_sep_fullnet_train_workspace_query(C.byref(_cfg()), 2, C.byref(ws), None) == 1
-    # the dense entry points keep refusing this network
-    assert lib.occ_fullnet_train_workspace_query(C.byref(_cfg()), 2, C.byref(ws), C.byref(sc)) == 1
-
-
-def test_argument_checks_need_no_gpu():
-    lib = nat.load()
-    good = _cfg(64)
-    big = 1 << 40
-    _rc, need_ws, need_sc = _query(lib, 64, 2)
-    bad_cfgs = (_cfg(64, separable=0), _cfg(64, separable=0, dilation=1), _cfg(64, dilation=3), _cfg(64, dilation=0), _cfg(48),
-                _cfg(16), _cfg(64, residual=2))
-    # occ_sep_fullnet_train_forward(cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, stream)
-    full = [C.byref(good), P16, P16, P16, 2, P16, big, P16, P16, None]
-    for i in (0, 1, 2, 3, 5, 7, 8):
-        args = list(full)
-        args[i] = None
-        assert lib.occ_sep_fullnet_train_forward(*args) == 1, i
-    for bad in bad_cfgs:
-        assert lib.occ_sep_fullnet_train_forward(C.byref(bad), *full[1:]) == 1
-    for n in (0, 65536):
-        assert lib.occ_sep_fullnet_train_forward(*full[:4], n, *full[5:]) == 1
-    assert lib.occ_sep_fullnet_train_forward(*full[:6], need_ws - 1, *full[7:]) == 1
-    assert lib.occ_sep_fullnet_train_forward(*full[:5], C.c_void_p(4096 + 8), *full[6:]) == 1  # ws not 16-byte aligned
-    assert lib.occ_sep_fullnet_train_forward(*full[:8], C.c_void_p(4096 + 4), None) == 1  # prob not 8-byte aligned
-    # occ_sep_fullnet_backward(cfg, enc_packed, dec_packed, n_env, ws, ws_bytes, grad_feats, grad_prob, scratch,
-    #                          scratch_bytes, grad_enc_packed, grad_dec_packed, stream)
-    full = [C.byref(good), P16, P16, 2, P16, big, P16, P16, P16, big, P16, P16, None]
-    for i in (0, 1, 2, 4, 6, 7, 8, 10, 11):
-        args = list(full)
-        args[i] = None
-        assert lib.occ_sep_fullnet_backward(*args) == 1, i
-    for bad in bad_cfgs:
-        assert lib.occ_sep_fullnet_backward(C.byref(bad), *full[1:]) == 1
-    for n in (0, 65536):
-        assert lib.occ_sep_fullnet_backward(*full[:3], n, *full[4:]) == 1
-    for i, short in ((5, need_ws - 1), (9, need_sc - 1)):
-        args = list(full)
-        args[i] = short
-        assert lib.occ_sep_fullnet_backward(*args) == 1, i
-    for i in (4, 7, 8):  # ws, grad_prob, scratch: 16-byte aligned
-        args = list(full)
-        args[i] = C.c_void_p(4096 + 8)
-        assert lib.occ_sep_fullnet_backward(*args) == 1, i
 
 
 @pytest.mark.parametrize("weights", ["golden", "seeded"])

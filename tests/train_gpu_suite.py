@@ -1,0 +1,478 @@
+"""The bodies shared by the GPU tests of the four native training paths that exist in a dense and a separable form:
+tests/test_gpu_encoder_train.py and tests/test_gpu_sep_encoder_train.py (the encoder through its pooled feature), and
+tests/test_gpu_fullnet_train.py and tests/test_gpu_sep_fullnet_train.py (the joint step).  Each body is a plain function of a
+``Form``, what varies between those modules; the modules keep their fixtures, their cases and their ``WORST`` dictionary and
+call in here.  Nothing is cached in this module: what lives on the device is what the calling module's fixtures hold.
+
+A case is a tuple that ends in (img, n); what is in front of it selects the weights (the key of the module's ``nets``, whose
+entries end in the FrozenEncoder).  A joint form's step has two outputs, (feats, prob), and two upstream gradients; an
+encoder form's has feats alone."""
+import ctypes as C
+from typing import Any, Callable, NamedTuple, Optional, Tuple
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import decoder_split_model as dsm
+from tests.encoder_model import make_obs
+from tests.train_utils import GUARD, bce64, dice64, grads, guarded
+
+FEATURES = 256
+NAN = 0x7FC00000
+
+
+class Form(NamedTuple):
+    model: Any                    # the f64 host model's module
+    net: type                     # the trainable net
+    joint: bool                   # the step returns (feats, prob), else feats
+    symbols: Tuple[str, str, str]  # workspace query, train forward, backward
+    separable: bool               # of encoder.packed_floats
+    host: Callable                # (entry of nets, case, f64 obs) -> the module's HostModel
+    label: Callable               # case -> what a printed line starts with
+    kind: Callable                # (case, key) -> the parameter kind WORST is kept by
+    n_params: int                 # tensors that receive a gradient, without the head's two
+    seed: int                     # 7000 or 9000: a case's seed is seed + img + n
+    steps: int                    # AdamW steps of ``trained``
+    tol: float
+    encoder_net: Optional[type] = None   # joint: the single encoder pass the joint step is compared with
+    enc_keys: Optional[Callable] = None  # joint: case -> the encoder's keys
+    dec_keys: Optional[Callable] = None  # joint: case -> the decoder's and the classifier's keys
+    gate_label: Optional[Callable] = None  # case -> the start of a gate line, where it is not ``label``
+    # what one form asserts and the other does not
+    nonzero_scale: bool = False       # no wanted gradient is all zero
+    band_cap: Optional[float] = None  # the largest share of a layer's pixels inside the gate band
+    head_is_the_decoder: bool = False  # SegmentationHead's gradients are exactly the decoder keys
+    finite_losses: bool = False       # the losses of ``trained`` are finite, not only not NaN
+
+
+def case_seed(f, case):
+    return f.seed + case[-2] + case[-1]
+
+
+def _step(f, net, obs):
+    return net.features_and_map(obs) if f.joint else (net(obs),)
+
+
+def _total(outs):
+    total = outs[0].sum()
+    for o in outs[1:]:
+        total = total + o.sum()
+    return total
+
+
+def _kept(f, net, i):
+    return f.model.kept_relu(net, i) if f.joint else net._kept_relu(i)
+
+
+def _n_relu(f):
+    return 21 if f.joint else 16
+
+
+def gates_of(f, net):
+    return [(_kept(f, net, i).cpu() > 0).double() for i in range(_n_relu(f))]
+
+
+def _host_outs(f, host, gates, us=None):
+    return host.forward(gates, us)[:2] if f.joint else (host.feats(gates, us),)
+
+
+def _dot(outs64, ups):
+    loss = (outs64[0] * ups[0].double()).sum()
+    for o, u in zip(outs64[1:], ups[1:]):
+        loss = loss + (o * u.double()).sum()
+    return loss
+
+
+def _shapes(f, img, n):
+    return [(n, FEATURES), (n, 1, img, img)][:2 if f.joint else 1]
+
+
+def make_runs(f, nets):
+    """The ``runs`` fixture of a module: case -> computed once and left unchanged, one native forward + backward with seeded
+    randn upstream gradients, the kept relu outputs and their gates, and the host model."""
+    cache = {}
+
+    def get(*case):
+        if case not in cache:
+            img, n = case[-2:]
+            key = case[:-2]
+            entry = nets[key if len(key) > 1 else key[0]]
+            enc = entry[-1]
+            obs = make_obs(case_seed(f, case), n, img).float().cuda()
+            net = f.net.from_encoder(enc)
+            outs = _step(f, net, obs)
+            gen = torch.Generator().manual_seed(case_seed(f, case) + 1)
+            ups = [torch.randn(*s, generator=gen) for s in _shapes(f, img, n)]
+            net.zero_grad()
+            torch.autograd.backward(list(outs), [u.cuda() for u in ups])
+            kept = [_kept(f, net, i).cpu().clone() for i in range(_n_relu(f))]
+            cache[case] = dict(enc=enc, net=net, obs=obs, outs=[o.detach() for o in outs], feats=outs[0].detach(), ups=ups,
+                               kept=kept, gates=[(k > 0).double() for k in kept],
+                               grads={k: v.cpu() for k, v in grads(net).items()}, host=f.host(entry, case, obs.double().cpu()))
+        return cache[case]
+
+    return get
+
+
+def check_grads(f, worst, what, case, got, want):
+    for k, w in want.items():
+        scale = float(w.abs().max())
+        if f.nonzero_scale:
+            assert scale > 0.0, (what, k, "the oracle's gradient is all zero")
+        err = float((got[k].double().cpu() - w).abs().max()) / scale
+        kind = f.kind(case, k)
+        worst[kind] = max(worst.get(kind, 0.0), err)
+        print(f"{what} {k}: max|want| {scale:.3g}, relative error {err:.3g}")
+    for k, w in want.items():
+        assert got[k].shape == w.shape and got[k].dtype == torch.float32
+        assert float((got[k].double().cpu() - w).abs().max()) <= f.tol * float(w.abs().max()), (what, k)
+    print("worst so far:", {k: f"{v:.3g}" for k, v in sorted(worst.items())})
+
+
+def forward_identity(f, r, case):
+    img, n = case[-2:]
+    assert [tuple(o.shape) for o in r["outs"]] == _shapes(f, img, n)
+    assert torch.equal(r["outs"][0], r["enc"](r["obs"]))
+    if f.joint:
+        assert torch.equal(r["outs"][1], r["enc"].segment(r["obs"]))
+
+
+def kept_relu_and_gates(f, r, case):
+    us = []
+    with torch.no_grad():
+        _host_outs(f, r["host"], None, us)
+    assert len(us) == len(r["kept"]) == _n_relu(f)
+    start = (f.gate_label or f.label)(case)
+    total, worst_band, worst_err = 0, 0.0, 0.0
+    for i, (u64, got) in enumerate(zip(us, r["kept"])):
+        assert got.shape == u64.shape
+        r64 = torch.relu(u64)
+        err = float((got.double() - r64).abs().max()) / max(1.0, float(r64.abs().max()))
+        band = u64.abs() <= f.tol * max(1.0, float(u64.abs().max()))
+        share = float(band.double().mean())
+        differ = (got > 0) != (u64 > 0)
+        total += int(differ.sum())
+        worst_band, worst_err = max(worst_band, share), max(worst_err, err)
+        print(f"{start} layer {i}: relu error {err:.3g}, band share {share:.3g}, gates differing {int(differ.sum())}")
+        assert err <= f.tol, (i, err)
+        if f.band_cap is not None:
+            assert share <= f.band_cap, (i, share)
+        assert not bool((differ & ~band).any()), (i, int((differ & ~band).sum()))
+    print(f"{f.label(case)}: relu error {worst_err:.3g}, {total} gates differ from the f64 model's, "
+          f"worst band share {worst_band:.3g}")
+
+
+def gradients_against_f64_autograd(f, worst, r, case):
+    host = r["host"]
+    want = host.grads(_dot(_host_outs(f, host, r["gates"]), r["ups"]))
+    assert len(want) == f.n_params and set(want) <= set(r["grads"])
+    check_grads(f, worst, f.label(case), case, r["grads"], want)
+
+
+def gradients_through_the_head_and_mse(f, worst, r, case):
+    img, n = case[-2:]
+    net, host = r["net"], r["host"]
+    target = torch.randn(n, 2, generator=torch.Generator().manual_seed(case_seed(f, case) + 2)).clamp(-1, 1)
+    net.zero_grad()
+    loss = F.mse_loss(net.predict_grad(r["obs"]), target.cuda())
+    loss.backward()
+    got = grads(net)
+    loss64 = F.mse_loss(host.predict(gates_of(f, net)), target.double())
+    want = host.grads(loss64, head=True)
+    assert len(want) == f.n_params + 2
+    assert abs(float(loss.detach()) - float(loss64.detach())) <= f.tol * max(1.0, abs(float(loss64.detach())))
+    check_grads(f, worst, f"mse {f.label(case)}", case, got, want)
+
+
+def gradients_through_the_real_losses(f, worst, r, case, losses):
+    from occlusionenv_amd import segmentation
+
+    img, n = case[-2:]
+    net, host = r["net"], r["host"]
+    gen = torch.Generator().manual_seed(case_seed(f, case) + 2)
+    occl = (torch.rand(n, 1, img, img, generator=gen) > 0.5).float()
+    grad = torch.randn(n, 2, generator=gen) * 0.05  # both sides of SmoothL1's beta = 0.01
+    net.zero_grad()
+    _pooled, segm, pred = net(r["obs"])
+    if losses == "dice+mse":
+        loss = segmentation.binary_dice_loss(segm, occl.cuda()) + F.mse_loss(pred, grad.cuda())
+    else:
+        loss = segmentation.binary_cross_entropy(segm, occl.cuda()) + F.smooth_l1_loss(pred, grad.cuda(), beta=0.01)
+    loss.backward()
+    got = grads(net)
+    _p64, prob64, pred64 = host.forward(gates_of(f, net))
+    if losses == "dice+mse":
+        loss64 = dice64(prob64, occl) + F.mse_loss(pred64, grad.double())
+    else:
+        loss64 = bce64(prob64, occl) + F.smooth_l1_loss(pred64, grad.double(), beta=0.01)
+    want = host.grads(loss64, head=True)
+    assert len(want) == f.n_params + 2
+    assert abs(float(loss.detach()) - float(loss64.detach())) <= f.tol * max(1.0, abs(float(loss64.detach())))
+    check_grads(f, worst, f"{losses} {case[0]} S={img} N={n}", case, got, want)
+
+
+def gradients_of_one_env(f, worst, r, case, env):
+    """Every upstream gradient is randn in one env and zero in the others: a tile given to the wrong env or dropped from a
+    short last slice is the whole signal."""
+    img, n = case[-2:]
+    net, host = r["net"], r["host"]
+    gen = torch.Generator().manual_seed(case_seed(f, case) + 3 + env)
+    ups = [torch.zeros(*s) for s in _shapes(f, img, n)]
+    for u in ups:
+        u[env] = torch.randn(*u.shape[1:], generator=gen)
+    net.zero_grad()
+    outs = _step(f, net, r["obs"])
+    assert torch.equal(outs[-1].detach(), r["outs"][-1])
+    torch.autograd.backward(list(outs), [u.cuda() for u in ups])
+    got = grads(net)
+    want = host.grads(_dot(_host_outs(f, host, gates_of(f, net)), ups))
+    what = f"env {env} alone {case[0]} S={img} N={n}" if f.joint else f"one-hot env {env} {f.label(case)}"
+    check_grads(f, worst, what, case, got, want)
+
+
+def reproducible_and_accumulating(r):
+    net, obs, up = r["net"], r["obs"], r["ups"][0].cuda()
+    net.zero_grad()
+    net(obs).backward(up)
+    once = grads(net)
+    assert all(torch.equal(once[k].cpu(), r["grads"][k]) for k in once)  # the same bits as the fixture's call
+    net(obs).backward(up)  # without zero_grad the second pass accumulates as torch does: g + g, exact
+    assert all(torch.equal(v, once[k] + once[k]) for k, v in grads(net).items())
+    net.zero_grad()
+
+
+def the_join_itself(f, worst, r, case):
+    """grad_feats absent: whatever reaches the encoder came through the decoder's skip and input gradients."""
+    net, host = r["net"], r["host"]
+    net.zero_grad()
+    _feats, prob = net.features_and_map(r["obs"])
+    prob.backward(r["ups"][1].cuda())  # the absent gradient of feats arrives as zeros
+    got = grads(net)
+    assert all(float(got[k].abs().max()) > 0.0 for k in f.enc_keys(case))
+    _pooled64, prob64, _pred = host.forward(gates_of(f, net))
+    want = host.grads((prob64 * r["ups"][1].double()).sum())
+    check_grads(f, worst, f"join {f.label(case)}", case, got, want)
+
+
+def bitwise_against_the_single_passes(f, r, case):
+    from occlusionenv_amd.seghead import SegmentationHead
+
+    net, enc, obs = r["net"], r["enc"], r["obs"]
+    gf, gp = (u.cuda() for u in r["ups"])
+    n_dec = len(f.dec_keys(case))
+    # the decoder and classifier gradients are SegmentationHead's for the same grad_prob, whatever grad_feats is
+    head = SegmentationHead.from_encoder(enc)
+    head(obs).backward(gp)
+    hg = grads(head)
+    assert len(hg) == n_dec == 22 and all(torch.equal(v.cpu(), r["grads"][k]) for k, v in hg.items())
+    if f.head_is_the_decoder:
+        assert set(hg) == set(f.dec_keys(case))
+    # with grad_prob absent the encoder gradients are the single encoder pass's and the decoder's exactly zero
+    tenc = f.encoder_net.from_encoder(enc)
+    tenc(obs).backward(gf)
+    eg = {k: v for k, v in grads(tenc).items() if k in f.enc_keys(case)}
+    net.zero_grad()
+    feats, _prob = net.features_and_map(obs)
+    feats.backward(gf)
+    got = grads(net)
+    assert len(eg) == f.n_params - n_dec and all(torch.equal(v, got[k]) for k, v in eg.items())
+    assert all(float(got[k].abs().max()) == 0.0 for k in f.dec_keys(case))
+    # two joint backward calls give the same bits
+    net.zero_grad()
+    feats, prob = net.features_and_map(obs)
+    torch.autograd.backward([feats, prob], [gf, gp])
+    again = grads(net)
+    assert len(again) >= f.n_params and all(torch.equal(v.cpu(), r["grads"][k]) for k, v in again.items())
+
+
+def no_stale_reads_and_nothing_outside_the_reported_sizes(f, r, case):
+    """The native calls on buffers of exactly the queried sizes, each the middle of a larger allocation that is inspected
+    afterwards; then the backward again after everything it may only write (scratch, the gradient buffers of the workspace,
+    the packed gradients; in a joint form also dlast / dskip and the forward's outputs, which it must neither read nor write)
+    has been filled with NaNs: the same bits, so nothing read was left over from before."""
+    from occlusionenv_amd import _native as nat
+    from occlusionenv_amd.encoder import decoder_packed_floats, packed_floats
+
+    img, n = case[-2:]
+    m, enc, net, obs = f.model, r["enc"], r["net"], r["obs"]
+    ups = [u.cuda() for u in r["ups"]]
+    packed = [enc.packed, enc.dec_packed] if f.joint else [enc.packed]
+    out_names = ["feats", "prob"] if f.joint else ["feats"]
+    grad_names = ["grad_enc", "grad_dec"] if f.joint else ["grad_packed"]
+    lib, cfg, st = nat.load(), enc._cfg(img), nat.stream_ptr(obs.device)
+    query, forward_name, backward_name = f.symbols
+    wsb, scb = C.c_size_t(), C.c_size_t()
+    nat.check(getattr(lib, query)(C.byref(cfg), n, C.byref(wsb), C.byref(scb)), query)
+    sizes = dict(ws=int(wsb.value), scratch=int(scb.value))
+    sizes.update(zip(grad_names, (4 * packed_floats(f.separable), 4 * decoder_packed_floats())))
+    sizes.update(zip(out_names, (4 * n * FEATURES, 4 * n * img * img)))
+    assert sizes["scratch"] == m.scratch_bytes(img, n)
+    if f.joint:
+        assert sizes["ws"] == m.ws_bytes(img, n)
+    bufs = {k: guarded(b) for k, b in sizes.items()}
+    mid = {k: whole[lo:lo + sizes[k]] for k, (whole, lo) in bufs.items()}
+    assert all(v.data_ptr() % 256 == 0 for v in mid.values())
+
+    def backward():
+        nat.check(getattr(lib, backward_name)(C.byref(cfg), *[nat.ptr(p) for p in packed], n, nat.ptr(mid["ws"]), sizes["ws"],
+                                              *[nat.ptr(u) for u in ups], nat.ptr(mid["scratch"]), sizes["scratch"],
+                                              *[nat.ptr(mid[k]) for k in grad_names], st), backward_name)
+        return [mid[k].view(torch.float32).clone() for k in grad_names]
+
+    nat.check(getattr(lib, forward_name)(C.byref(cfg), *[nat.ptr(p) for p in packed], nat.ptr(obs), n, nat.ptr(mid["ws"]),
+                                         sizes["ws"], *[nat.ptr(mid[k]) for k in out_names], st), forward_name)
+    outs = [mid[k].clone() for k in out_names]
+    for o, want in zip(outs, r["outs"]):
+        assert torch.equal(o.view(torch.float32).view(want.shape), want)
+    a = backward()
+    again = a if f.joint else backward()
+    # what the backward only writes: g0 | g1 | g2 at the end of the encoder's workspace (include/occlusionenv_amd.h) and, in a
+    # joint form, dlast | dskip at the end of the whole
+    buf = dsm.align(4 * n * 8 * img * img)
+    e_end = m.encoder_ws_bytes(img, n) if f.joint else sizes["ws"]
+    mid["ws"][e_end - 3 * buf:e_end].view(torch.int32).fill_(NAN)
+    if f.joint:
+        tail = dsm.align(4 * n * 256 * (img // 32) ** 2) + sum(dsm.level_bytes(img, n)[:4])
+        mid["ws"][sizes["ws"] - tail:].view(torch.int32).fill_(NAN)
+    for k in ["scratch"] + grad_names + (out_names if f.joint else []):  # the outputs too: the backward reads the prob kept in ws
+        mid[k].view(torch.int32).fill_(NAN)
+    b = backward()
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(t).all()) for t in a)
+    assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) and torch.equal(x.view(torch.int32), z.view(torch.int32))
+               for x, y, z in zip(a, again, b))
+    if f.joint:
+        assert all(bool((mid[k].view(torch.int32) == NAN).all()) for k in out_names)  # writes neither
+    else:
+        assert torch.equal(mid["feats"], outs[0])  # the backward does not write it
+    # the packed gradients are the module's, the same bits as through the autograd function: every conv leaf and the
+    # classifier as they are (the BN affine goes through the fold)
+    assert len(net.parts) == len(a)
+    for part, packed_grad in zip(net.parts, a):
+        layers, tail = part.unpack(packed_grad.cpu())
+        for layer, stem, leaves in zip(layers, part.stems, part.layer_leaves()):
+            for t, leaf in zip(layer[:-2], leaves[:-2]):
+                assert torch.equal(t, r["grads"][stem + leaf]), stem + leaf
+        assert len(tail) == len(part.tail) and all(torch.equal(t, r["grads"][k]) for t, k in zip(tail, part.tail))
+    for k, (whole, lo) in bufs.items():
+        assert lo >= GUARD and whole.numel() - (lo + sizes[k]) >= GUARD
+        assert bool((whole[:lo] == 0xA5).all()), f"bytes in front of {k} were written"
+        assert bool((whole[lo + sizes[k]:] == 0xA5).all()), f"bytes behind {k} were written"
+
+
+def errors_tail(f, r):
+    """What every form refuses in the same words, on a case's net: a chunk limit below the batch, a side that is no multiple
+    of 32 (where the decoder runs), a CPU tensor, and the backward of a forward that a later one has superseded."""
+    from occlusionenv_amd._native import NativeError
+
+    net, enc = r["net"], r["enc"]
+    enc.max_chunk = 2
+    try:
+        with pytest.raises(ValueError, match="max_chunk"):
+            net(r["obs"])
+    finally:
+        enc.max_chunk = 256
+    if f.joint:
+        with pytest.raises(ValueError, match="multiple of 32"):
+            net(torch.zeros(1, 4, 48, 48, device="cuda"))
+    with pytest.raises(NativeError):
+        net(torch.zeros(1, 4, 64, 64))
+    first = _step(f, net, r["obs"])
+    second = _step(f, net, r["obs"][:1])
+    with pytest.raises(RuntimeError, match="superseded"):
+        _total(first).backward()
+    net.zero_grad()
+    _total(second).backward()  # the latest forward still has its activations
+    assert all(p.grad is not None for _k, p in net.ordered_parameters())
+    net.zero_grad()
+
+
+def _train(f, net, loss_of, **adamw):
+    """``f.steps`` AdamW steps at lr 1e-3 on a fixed batch -> (the parameters before, the loss in front of every step and after
+    the last one)."""
+    before = {k: v.detach().clone() for k, v in net.named_parameters()}
+    opt = torch.optim.AdamW(net.parameters(), lr=1e-3, **adamw)
+    losses = []
+    for _ in range(f.steps + 1):
+        opt.zero_grad()
+        loss = loss_of(net)
+        losses.append(loss.detach())
+        if len(losses) <= f.steps:
+            loss.backward()
+            opt.step()
+    return before, torch.stack(losses).cpu().tolist()
+
+
+def trained_encoder(f, r):
+    """The ``trained`` fixture of an encoder form, on the case of ``r``, towards fixed unit targets."""
+    net = f.net.from_encoder(r["enc"])
+    target = F.normalize(torch.randn(3, 2, generator=torch.Generator().manual_seed(5)), dim=1).cuda()
+    before, losses = _train(f, net, lambda net: F.mse_loss(net.predict_grad(r["obs"]), target))
+    return dict(net=net, before=before, losses=losses, obs=r["obs"], enc=r["enc"], feats0=r["feats"])
+
+
+def _blocky(n, img, gen):
+    """A random occlusion map of 8 x 8 blocks."""
+    return (torch.rand(n, 1, img // 8, img // 8, generator=gen) > 0.5).float().repeat_interleave(8, 2).repeat_interleave(8, 3)
+
+
+def trained_joint(f, enc):
+    """The ``trained`` fixture of a joint form: a fixed batch (N=4, S=64), Dice + MSE as in pretrainer.py."""
+    from occlusionenv_amd import segmentation
+
+    n, img = 4, 64
+    obs = make_obs(f.seed + img + n, n, img).float().cuda()
+    gen = torch.Generator().manual_seed(f.seed + img + n + 5)
+    occl = _blocky(n, img, gen).cuda()
+    grad = (torch.randn(n, 2, generator=gen) * 0.5).cuda()
+    net = f.net.from_encoder(enc)
+
+    def loss_of(net):
+        _pooled, segm, pred = net(obs)
+        return segmentation.binary_dice_loss(segm, occl) + F.mse_loss(pred, grad)
+
+    before, losses = _train(f, net, loss_of, weight_decay=1e-5)
+    return dict(net=net, enc=enc, obs=obs, before=before, losses=losses)
+
+
+def learning(f, trained):
+    losses = trained["losses"]
+    assert all(np.isfinite(v) if f.finite_losses else v == v for v in losses) and losses[-1] < losses[0]
+    assert all(not torch.equal(v, trained["before"][k]) for k, v in trained["net"].named_parameters())
+
+
+def pretrain_epoch(f, enc):
+    """harness.pretrain_epoch on three stored batches against the same steps taken by hand -> (the first epoch's result, a
+    second epoch's on its net and optimizer with the other two losses)."""
+    from occlusionenv_amd import harness, segmentation
+
+    n, img = 4, 64
+    gen = torch.Generator().manual_seed(77)
+    batches = []
+    for b in range(3):  # the stored format: (img, occlusion, grad, _) on the host
+        occl = _blocky(n, img, gen)
+        batches.append((make_obs(500 + b, n, img).float(), occl, torch.randn(n, 2, generator=gen) * 0.5, None))
+    # the predictions each step learns from, by the same steps taken by hand
+    ref = f.net.from_encoder(enc)
+    opt = torch.optim.AdamW(ref.parameters(), lr=1e-3, weight_decay=1e-5)
+    acc, iou = [], []
+    for obs, occl, grad, _ in batches:
+        opt.zero_grad()
+        _pooled, segm, pred = ref(obs.cuda())
+        (segmentation.binary_dice_loss(segm, occl.cuda()) + F.mse_loss(pred, grad.cuda())).backward()
+        opt.step()
+        c = segmentation.seg_criterion(segm.detach(), occl.cuda())
+        acc.append(float(c["correct"].sum()) / segm.numel())
+        iou.append(float(c["intersection"].sum()) / float(c["union"].sum()))
+    res = harness.pretrain_epoch(enc, batches)  # from an encoder: the net of its form is made
+    assert isinstance(res["net"], f.net) and res["batches"] == 3 and res["pixels"] == 3 * n * img * img
+    for k in ("loss", "segm_loss", "grad_loss", "accuracy", "iou"):
+        assert res[k] == res[k] and abs(res[k]) < float("inf"), k
+    assert abs(res["loss"] - (res["segm_loss"] + res["grad_loss"])) <= 1e-6
+    assert abs(res["accuracy"] - 100.0 * sum(acc) / 3) <= 1e-9 and abs(res["iou"] - 100.0 * sum(iou) / 3) <= 1e-9
+    assert all(torch.equal(v, dict(ref.named_parameters())[k]) for k, v in res["net"].named_parameters())
+    res2 = harness.pretrain_epoch(res["net"], batches, use_dice=False, use_l1=True, optimizer=res["optimizer"])
+    assert res2["net"] is res["net"] and all(res2[k] == res2[k] for k in ("loss", "segm_loss", "grad_loss", "accuracy", "iou"))
+    return res, res2

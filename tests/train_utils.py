@@ -1,5 +1,7 @@
-"""Helpers shared by the GPU tests of the three native training paths (tests/test_gpu_decoder_train.py,
-tests/test_gpu_encoder_train.py, tests/test_gpu_fullnet_train.py)."""
+"""Helpers shared by the GPU tests of the native training paths: tests/test_gpu_decoder_train.py, tests/test_gpu_bn_train.py
+and, through the shared bodies of tests/train_gpu_suite.py, the dense and separable pairs
+tests/test_gpu_encoder_train.py / test_gpu_sep_encoder_train.py and tests/test_gpu_fullnet_train.py /
+test_gpu_sep_fullnet_train.py."""
 import torch
 
 GUARD = 4096
