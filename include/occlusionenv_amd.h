@@ -778,6 +778,52 @@ int occ_dataset_pack(const float* obs, const float* alpha, int alpha_stride, int
                      uint32_t* rgbl, int16_t* depth, int m_frames, int label_mode, void* stream);
 
 /*
+ * Resizing frames between resident stores (additive in ABI 12; csrc/occ_resize.hpp): PIL's Image.resize(size) without a
+ * filter argument, which is what the reference's reader applies to every item (dataset.py:65-67; it renders at 512 x 512
+ * and trains at 256 x 256): BICUBIC for the "RGB" and the "I" image, NEAREST for the "1" image.  With occ_dataset_pack at
+ * the rendering size in front of it, a frame gets the bits of RunWriter followed by from_directory at another size (the
+ * JPEG apart): the dither runs at the rendering size and the resize picks from its result.
+ *
+ * occ_dataset_resize_query(src_img, dst_img, n, &workspace_bytes): the size of the workspace of a call; no GPU is touched.
+ *
+ * occ_dataset_resize(src_rgbl, src_depth, n, src_img, slot, dst_rgbl, dst_depth, m_frames, dst_img, workspace, stream)
+ *   src_rgbl, src_depth  n frames of R x R pixels (R = src_img), the words and int16 planes of occ_augment_batch; only read
+ *   slot   int64[n] on the device: the frame of the destination source frame i is resized into.  Any value outside
+ *          [0, m_frames) skips frame i; no address is formed from it.  Keeping the in-range slots distinct is the caller's duty.
+ *   dst_rgbl, dst_depth  m_frames frames of S x S pixels (S = dst_img); frames no slot names are not touched.  The two
+ *          stores must not overlap.
+ *   workspace  8-byte aligned device memory of the queried size.  The call fills it itself, in its first launch:
+ *          with K = min((int)ceil(support) * 2 + 1, R), in this order and without padding
+ *            double k[S][K], int32 kk[S][K], int32 bounds[S][2] (xmin, count), int32 nearest[S]
+ *          as below.  Its contents mean nothing between calls.
+ * The table, one for both axes (Resample.c precompute_coeffs; f64, every operation rounded on its own):
+ *   scale = R / S, fs = max(scale, 1.0), support = 2.0 * fs, ss = 1.0 / fs; per output index xx
+ *   center = (xx + 0.5) * scale; xmin = max((int)(center - support + 0.5), 0);
+ *   count = min((int)(center + support + 0.5), R) - xmin; w[x] = f((x + xmin - center + 0.5) * ss) for x < count, ww their
+ *   sum in that order, k[x] = w[x] / ww (0 from count on), with f(x) for x = |x| and a = -0.5:
+ *   x < 1: ((a + 2) x - (a + 3)) x x + 1; x < 2: (((x - 5) x + 8) x - 4) a; else 0.
+ *   kk[x] = (int)(k[x] * 2^22 + (k[x] < 0 ? -0.5 : 0.5))                                     normalize_coeffs_8bpc
+ *   nearest: a = R / S; xo = a * 0.5; nearest[x] = (int)xo; xo += a -- a running sum (Geometry.c ImagingScaleAffine),
+ *   clamped to [0, R - 1]
+ * Per pixel, the horizontal pass first, its result feeding the vertical pass:
+ *   R, G, B  acc = 2^21 + sum pixel * kk[x] in int32; clip(acc >> 22, 0, 255), an arithmetic shift
+ *   depth    acc = 0.0; acc = acc + (double)pixel * k[x] in tap order, product and sum rounded separately;
+ *            (int)(acc + (acc < 0 ? -0.5 : 0.5)), an int32 between the passes; the final value saturated to int16 (PIL's
+ *            wherever PIL's fits; anything that came from occ_dataset_pack does)
+ *   label    the label of source pixel (nearest[y], nearest[x])
+ * Supported sizes: min(R, ceil((min(32, S) - 1) * R / S + 4 * max(R / S, 1)) + 2) <= 72, the input window of one 32 x 32
+ * output tile in LDS: every R / S <= 2, integer or not, upscaling by any factor, and any S for R <= 72.
+ * Two launches on `stream`: the table, then one fused pass (window into LDS, horizontal pass into LDS, vertical pass).
+ * Nothing is allocated or synchronised, no atomics, plain stores, sums in a fixed order: the store is bitwise the same from
+ * call to call.  tests/resize_model.py is this arithmetic in numpy, checked against PIL.
+ * OCC_ERR_ARG before any launch for a null pointer, a workspace that is not 8-byte aligned, a size < 1, a size with
+ * img * img > 2^24, n < 1, n > 65535, m_frames < 1 or an unsupported pair of sizes.
+ */
+int occ_dataset_resize_query(int src_img, int dst_img, int n, size_t* workspace_bytes);
+int occ_dataset_resize(const uint32_t* src_rgbl, const int16_t* src_depth, int n, int src_img, const int64_t* slot,
+                       uint32_t* dst_rgbl, int16_t* dst_depth, int m_frames, int dst_img, void* workspace, void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

@@ -88,6 +88,7 @@ namespace occ {
 #include "occ_adamw.hpp"
 #include "occ_augment.hpp"
 #include "occ_datapack.hpp"
+#include "occ_resize.hpp"
 
 }  // namespace occ
 
@@ -1018,6 +1019,32 @@ extern "C" int occ_dataset_pack(const float* obs, const float* alpha, int alpha_
                        alpha_stride, pixels, slot, rgbl, depth, m_frames, label_mode);
     if (label_mode == 0)
         hipLaunchKernelGGL(occ_datapack_dither_kernel, dim3(n), dim3(kDitherRows), 0, st, slot, rgbl, img, m_frames);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- PIL's resize between two resident stores (occ_resize.hpp) -------------------------------------------------------------
+static bool resize_shape_ok(int src_img, int dst_img, int n) {
+    return src_img >= 1 && dst_img >= 1 && (int64_t)src_img * src_img <= (int64_t)kResizeMaxPixels &&
+           (int64_t)dst_img * dst_img <= (int64_t)kResizeMaxPixels && n >= 1 && n <= 65535 && resize_ratio_ok(src_img, dst_img);
+}
+
+extern "C" int occ_dataset_resize_query(int src_img, int dst_img, int n, size_t* workspace_bytes) {
+    if (!resize_shape_ok(src_img, dst_img, n) || !workspace_bytes) return OCC_ERR_ARG;
+    *workspace_bytes = resize_table_bytes(src_img, dst_img);
+    return OCC_OK;
+}
+
+extern "C" int occ_dataset_resize(const uint32_t* src_rgbl, const int16_t* src_depth, int n, int src_img, const int64_t* slot,
+                                  uint32_t* dst_rgbl, int16_t* dst_depth, int m_frames, int dst_img, void* workspace, void* stream) {
+    if (!non_null(src_rgbl, src_depth, slot, dst_rgbl, dst_depth, workspace) || ((uintptr_t)workspace & 7) != 0) return OCC_ERR_ARG;
+    if (!resize_shape_ok(src_img, dst_img, n) || m_frames < 1) return OCC_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int R = src_img, S = dst_img, K = resize_taps(R, S);
+    const ResizeTables t = resize_tables(workspace, R, S);
+    const int tiles = (S + kResizeTile - 1) / kResizeTile;
+    hipLaunchKernelGGL(occ_resize_table_kernel, dim3((S + 63) / 64), dim3(64), 0, st, R, S, K, t);
+    hipLaunchKernelGGL(occ_resize_kernel, dim3(tiles * tiles, n), dim3(kResizeBlock), 0, st, src_rgbl, src_depth, R, slot, dst_rgbl,
+                       dst_depth, m_frames, S, K, t);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

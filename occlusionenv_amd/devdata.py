@@ -17,11 +17,18 @@ Batches are ``(img, occlusion, grad, pos)``, the reference's order, which is wha
 
 The store can also be filled on the device (csrc/occ_datapack.hpp, ``occ_dataset_pack``): ``DeviceDataset.empty`` plus
 ``put`` per engine step, which is what ``generate_resident`` does in ``dataset_io.generate``'s loop.  ``put`` gives a frame
-the bits the writer and ``from_directory`` at the same size would (``tests/datapack_model.py``), the JPEG apart.  Not
-reproduced there: the resize (the env renders at the dataset's size; the reference renders 512 x 512 and resizes to
-256 x 256 with PIL's bicubic filter), and the pairing ``from_directory`` inherits from the reference's lexicographic file
-sort (``0, 1, 10, .., 19, 2, ..`` against numerically ordered labels: images of runs with more than 10 frames get other
-frames' ``pos`` / ``grad``); a generated store is run-major, frame ``j`` numeric, every image with its own labels.
+the bits the writer and ``from_directory`` at the same size would (``tests/datapack_model.py``), the JPEG apart.
+
+The resize is reproduced too (csrc/occ_resize.hpp, ``occ_dataset_resize``): the reference renders 512 x 512 and its reader
+shrinks every item to 256 x 256 with ``Image.resize`` (``dataset.py:65-67``: bicubic for the colours and the depth, nearest
+for the dithered label).  ``put(resize=True)`` packs at the rendering size and resizes into the store,
+``generate_resident(size=256)`` does that for every step of an env that renders at 512, and ``resized`` does it to a whole
+store; the arithmetic is PIL's bit for bit (``tests/resize_model.py``, checked against PIL and against the files).  So from
+the engine's step to the batch everything is on the device, with the bits the reference's files-and-PIL path would give.
+Still not reproduced: the JPEG, the worker RNG stream (above), and the pairing ``from_directory`` inherits from the
+reference's lexicographic file sort (``0, 1, 10, .., 19, 2, ..`` against numerically ordered labels: images of runs with
+more than 10 frames get other frames' ``pos`` / ``grad``); a generated store is run-major, frame ``j`` numeric, every image
+with its own labels.
 """
 from __future__ import annotations
 
@@ -91,6 +98,17 @@ def sincos_grad(grad: np.ndarray) -> np.ndarray:
     return torch.stack([torch.sin(alpha), torch.cos(alpha)], 1).float().numpy()
 
 
+def resize_workspace_bytes(src_size: int, dst_size: int, n: int = 1) -> int:
+    """``occ_dataset_resize_query``: the workspace of a resize of ``n`` frames from ``src_size`` to ``dst_size``, or
+    ``ValueError`` for a pair of sizes the kernel does not take (csrc/occ_resize.hpp: ``src / dst <= 2``, any upscaling,
+    any ``dst`` for ``src <= 72``; both within 1 .. 4096).  No GPU is touched."""
+    need = C.c_size_t()
+    if nat.load().occ_dataset_resize_query(int(src_size), int(dst_size), int(n), C.byref(need)) != 0:
+        raise ValueError("resize %d -> %d of %d frames is not supported: sizes in 1 .. 4096, src / dst <= 2 or src <= 72, "
+                         "1 .. 65535 frames" % (src_size, dst_size, n))
+    return int(need.value)
+
+
 class DeviceDataset:
     """A decoded, resized dataset resident on ``device``: ``rgbl`` (M,S,S) int32 words ``R | G << 8 | B << 16 | label << 24``,
     ``depth`` (M,S,S) int16, ``pos`` and ``grad`` (M,2) f32.  Build it with ``from_directory`` or ``from_arrays``, or
@@ -106,6 +124,7 @@ class DeviceDataset:
             raise ValueError("DeviceDataset: at least one frame, S^2 <= 2^24")
         self.rgbl, self.depth, self.pos, self.grad = (t.contiguous() for t in (rgbl, depth, pos, grad))
         self.split, self.size, self.device = split, S, rgbl.device
+        self._staging = {}  # (n, R) -> the store put(resize=True) packs n frames of R x R into
 
     def __len__(self) -> int:
         return self.rgbl.shape[0]
@@ -174,7 +193,39 @@ class DeviceDataset:
                    torch.zeros((M, 2), dtype=torch.float32, device=dev), torch.zeros((M, 2), dtype=torch.float32, device=dev),
                    split=split)
 
-    def put(self, obs: torch.Tensor, full_state: torch.Tensor, slots, pos=None, grad=None, label: str = "dither") -> None:
+    def _resize_into(self, src_rgbl: torch.Tensor, src_depth: torch.Tensor, slots_dev: torch.Tensor) -> None:
+        """One ``occ_dataset_resize``: frame ``i`` of the (n,R,R) pair on this store's device into frame ``slots_dev[i]``."""
+        n, R = int(src_rgbl.shape[0]), int(src_rgbl.shape[1])
+        lib = nat.load()
+        with torch.cuda.device(self.device):
+            ws = torch.empty(resize_workspace_bytes(R, self.size, n) // 4, dtype=torch.int32, device=self.device)
+            nat.check(lib.occ_dataset_resize(nat.ptr(src_rgbl), nat.ptr(src_depth), n, R, nat.ptr(slots_dev), nat.ptr(self.rgbl),
+                                             nat.ptr(self.depth), len(self), self.size, nat.ptr(ws), nat.stream_ptr(self.device)),
+                      "occ_dataset_resize")
+
+    def resized(self, size: int) -> "DeviceDataset":
+        """A new store of ``size`` x ``size`` frames on the same device: every frame through ``occ_dataset_resize``
+        (csrc/occ_resize.hpp), which is PIL's ``Image.resize`` as the reference's reader calls it (bicubic colours and
+        depth, nearest label; tests/resize_model.py); ``pos``, ``grad`` and ``split`` are carried over.
+        ``size == self.size`` gives a copy."""
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)):
+            raise ValueError("resized: size is an integer")
+        S = int(size)
+        if S == self.size:
+            return DeviceDataset(self.rgbl.clone(), self.depth.clone(), self.pos.clone(), self.grad.clone(), split=self.split)
+        resize_workspace_bytes(self.size, S)  # ValueError for sizes the kernel does not take
+        if self.device.type != "cuda":
+            raise nat.NativeError("DeviceDataset.resized runs on the GPU only (this store is on %s); there is no CPU path" % self.device)
+        out = DeviceDataset.empty(len(self), S, self.device, split=self.split)
+        out.pos.copy_(self.pos)
+        out.grad.copy_(self.grad)
+        for lo, rows in nat.row_chunks(len(self), 65535):
+            out._resize_into(self.rgbl[lo:lo + rows], self.depth[lo:lo + rows],
+                             torch.arange(lo, lo + rows, dtype=torch.int64, device=self.device))
+        return out
+
+    def put(self, obs: torch.Tensor, full_state: torch.Tensor, slots, pos=None, grad=None, label: str = "dither",
+            resize: bool = False) -> None:
         """Write the frames of one engine step into the store, on the device, in one ``occ_dataset_pack`` call
         (csrc/occ_datapack.hpp): env ``i`` of ``obs`` (n,4,S,S) and ``full_state`` (n,S,S,4; its alpha channel is the
         occlusion image; an (n,S,S) alpha image is taken too) becomes frame ``slots[i]`` with the bits
@@ -184,21 +235,28 @@ class DeviceDataset:
         rule of ``pretrainer.py:134``).  ``slots``: n int64 on the device or the host; an env whose slot is outside
         ``[0, len(self))`` is skipped, in-range slots must be distinct.  ``pos`` / ``grad``: (n,2) rows stored as they are
         for the slots in range (an indexed copy; selecting the rows reads the mask back, so a caller that must not
-        synchronise keeps its labels itself, as ``generate_resident`` does).  There is no resize: ``obs`` has the
-        store's size."""
+        synchronise keeps its labels itself, as ``generate_resident`` does).
+
+        ``resize=False``: there is no resize, ``obs`` has the store's size.  ``resize=True``: an ``obs`` of another size
+        R x R is packed at R (either label rule; the dither runs at R) into a staging store of ``n`` frames that the
+        dataset keeps per ``(n, R)``, and the staged frames go through ``occ_dataset_resize`` (csrc/occ_resize.hpp) into
+        ``slots``: the bits of the writer at R and ``from_directory`` at the store's size, the JPEG apart.  With R equal
+        to the store's size it is the single pack call."""
         if label not in LABEL_MODES:
             raise ValueError("label: 'dither' or 'threshold'")
         S = self.size
-        if obs.ndim != 4 or obs.shape[1] != 4 or obs.shape[-1] != S or obs.shape[-2] != S:
-            raise ValueError("put: obs (n,4,%d,%d): the env renders at the dataset's size, there is no resize" % (S, S))
-        n = int(obs.shape[0])
-        if tuple(full_state.shape) not in ((n, S, S, 4), (n, S, S)):
-            raise ValueError("put: full_state (n,%d,%d,4) or an alpha image (n,%d,%d)" % (S, S, S, S))
+        if obs.ndim != 4 or obs.shape[1] != 4 or obs.shape[-1] != obs.shape[-2] or (not resize and obs.shape[-1] != S):
+            raise ValueError("put: obs (n,4,%d,%d): the env renders at the dataset's size (resize=True: at any square size)" % (S, S))
+        n, R = int(obs.shape[0]), int(obs.shape[-1])
+        if tuple(full_state.shape) not in ((n, R, R, 4), (n, R, R)):
+            raise ValueError("put: full_state (n,%d,%d,4) or an alpha image (n,%d,%d)" % (R, R, R, R))
         if not 1 <= n <= 65535:
             raise ValueError("put: 1 .. 65535 envs")
         s = torch.as_tensor(slots)
         if s.is_floating_point() or s.dtype == torch.bool or s.numel() != n:
             raise ValueError("put: slots are n integers")
+        if R != S:
+            resize_workspace_bytes(R, S, n)  # ValueError for sizes the kernel does not take
         if self.device.type != "cuda":
             raise nat.NativeError("DeviceDataset.put runs on the GPU only (this store is on %s); there is no CPU path" % self.device)
         s = s.reshape(n).to(self.device, torch.int64).contiguous()
@@ -206,9 +264,18 @@ class DeviceDataset:
         fs = full_state.detach().to(self.device, torch.float32).contiguous()
         stride = 4 if fs.ndim == 4 else 1
         with torch.cuda.device(self.device):
-            nat.check(nat.load().occ_dataset_pack(nat.ptr(obs), nat.ptr(fs, 12 if stride == 4 else 0), stride, n, S, nat.ptr(s),
-                                                  nat.ptr(self.rgbl), nat.ptr(self.depth), len(self), LABEL_MODES[label],
-                                                  nat.stream_ptr(self.device)), "occ_dataset_pack")
+            into, into_slots = self, s
+            if R != S:
+                into = self._staging.get((n, R))
+                if into is None:
+                    into = self._staging[(n, R)] = DeviceDataset.empty(n, R, self.device)
+                ok = (s >= 0) & (s < len(self))
+                into_slots = torch.where(ok, torch.arange(n, dtype=torch.int64, device=self.device), torch.full_like(s, -1))
+            nat.check(nat.load().occ_dataset_pack(nat.ptr(obs), nat.ptr(fs, 12 if stride == 4 else 0), stride, n, R,
+                                                  nat.ptr(into_slots), nat.ptr(into.rgbl), nat.ptr(into.depth), len(into),
+                                                  LABEL_MODES[label], nat.stream_ptr(self.device)), "occ_dataset_pack")
+            if R != S:
+                self._resize_into(into.rgbl, into.depth, s)
             if pos is not None or grad is not None:
                 ok = (s >= 0) & (s < len(self))
                 for dst, src in ((self.pos, pos), (self.grad, grad)):
@@ -309,7 +376,7 @@ class EpochLoader:
 
 
 def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5e-2, generator=None, max_steps: int = 0,
-                      label: str = "dither", grad_mode: str = "sincos", split: str = "train") -> DeviceDataset:
+                      label: str = "dither", grad_mode: str = "sincos", split: str = "train", size=None) -> DeviceDataset:
     """``dataset_io.generate``'s loop (datasetGenerator.py:76-124) into a ``DeviceDataset`` instead of files: ``num_runs``
     runs of ``num_frames`` frames at the env's own size, frame ``j`` of run ``r`` at index ``r * num_frames + j`` with its
     own ``pos`` (elevation, azimuth) and ``grad``.  Nothing of a frame leaves the device: every step is one
@@ -322,7 +389,11 @@ def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5
     same ``generator`` and ``num_runs == venv.num_envs`` the actions are the ones ``generate`` draws.  ``num_runs`` above
     ``venv.num_envs`` runs in rounds of ``num_envs`` with a ``reset()`` between them; the envs of a last partial round
     beyond ``num_runs`` write nothing.  ``grad_mode="sincos"`` turns the raw f32 gradients into ``sincos_grad`` at the end
-    (M x 2 values, on the host: the bits ``from_directory`` computes from the pickled values), ``"raw"`` keeps them."""
+    (M x 2 values, on the host: the bits ``from_directory`` computes from the pickled values), ``"raw"`` keeps them.
+
+    ``size``: None stores the frames at the env's own size.  Another ``size`` gives a store of that size, every step going
+    through ``put(resize=True)``: rendered at the env's size (the reference: 512), packed there, resized on the device as
+    the reference's reader resizes its files (to 256), see ``DeviceDataset.put``."""
     if grad_mode not in ("sincos", "raw"):
         raise ValueError("grad_mode: 'sincos' or 'raw'")
     if label not in LABEL_MODES:
@@ -332,7 +403,14 @@ def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5
         raise ValueError("generate_resident: at least one run of one frame")
     eng, N = venv.engine, venv.num_envs
     dev, M = eng.device, num_runs * num_frames
-    ds = DeviceDataset.empty(M, eng.S, dev, split=split)
+    if size is not None:
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)):
+            raise ValueError("generate_resident: size is an integer or None")
+        if int(size) != eng.S:
+            resize_workspace_bytes(eng.S, int(size), N)  # ValueError for sizes the kernel does not take
+            if dev.type != "cuda":
+                raise nat.NativeError("generate_resident(size=) runs on the GPU only (the engine is on %s); there is no CPU path" % dev)
+    ds = DeviceDataset.empty(M, eng.S if size is None else int(size), dev, split=split)
     # row M takes what the envs without a frame in a step scatter
     elaz = torch.zeros((M + 1, 2), dtype=torch.float32, device=dev)
     graw = torch.zeros((M + 1, 2), dtype=torch.float32, device=dev)
@@ -358,7 +436,7 @@ def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5
             g = a.grad.detach()
             good = pending & ~torch.isnan(g).any(1)
             slot = torch.where(good, run * num_frames + frame, torch.full_like(frame, -1))
-            ds.put(obs, full_state, slot, label=label)
+            ds.put(obs, full_state, slot, label=label, resize=size is not None)
             row = torch.where(good, slot, torch.full_like(frame, M))
             elaz[row] = torch.stack([eng.elevation.reshape(N), eng.azimuth.reshape(N)], 1).to(torch.float32)
             graw[row] = g.to(torch.float32)
