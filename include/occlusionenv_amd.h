@@ -824,6 +824,54 @@ int occ_dataset_resize(const uint32_t* src_rgbl, const int16_t* src_depth, int n
                        uint32_t* dst_rgbl, int16_t* dst_depth, int m_frames, int dst_img, void* workspace, void* stream);
 
 /*
+ * JPEG round trip in the resident store (additive in ABI 12; csrc/occ_jpeg.hpp): what writing a frame's colours as a
+ * baseline JPEG and decoding the file again does to them, which is what the reference trains on (datasetGenerator.py:104
+ * writes every colour image as a 4:2:0 JPEG at the rendering size).  Entropy coding is lossless, so the round trip is a
+ * function of the pixels and the two quantisation tables.  With occ_dataset_pack in front of it (and occ_dataset_resize
+ * behind it) a frame gets the bits of RunWriter followed by from_directory, colours included.
+ *
+ * occ_dataset_jpeg_query(img, n, quality, &workspace_bytes): the size of the workspace of a call, n * cs * cs * 2 bytes
+ *   with cs = 8 * ceil(img / 16); no GPU is touched.  OCC_ERR_ARG for img outside 1 .. 4096, n outside 1 .. 65535, quality
+ *   outside 1 .. 100 or a null pointer.
+ *
+ * occ_dataset_jpeg(rgbl, m_frames, img, slot, n, quality, workspace, stream)
+ *   rgbl   the words of the store of occ_augment_batch, m_frames frames of S x S pixels (S = img), changed in place: the
+ *          three colour bytes of frame slot[i] are replaced by the round trip of those same three bytes taken as the file's
+ *          R, G, B (the store holds them in file order; occ_dataset_pack has swapped B and R).  The label byte is kept; the
+ *          depth plane is not an argument.  Frames no slot names are not touched.
+ *   slot   int64[n] on the device.  Any value outside [0, m_frames) skips entry i; no address is formed from it.  Keeping
+ *          the in-range slots distinct is the caller's duty.
+ *   workspace  2-byte aligned device memory of the queried size: per entry i a cs x cs plane of Cb' | Cr' << 8, the
+ *          reconstructed chroma samples between the two launches.  Its contents mean nothing between calls.
+ * The arithmetic is libjpeg's with its defaults (YCbCr, 2x2 luminance sampling, the slow-integer DCT, fancy upsampling), in
+ * int32 with arithmetic shifts, no floating point; D(x, n) = (x + (1 << (n - 1))) >> n:
+ *   tables   the luminance and chrominance tables of the JPEG specification, Annex K; scale = 5000 / quality below 50, else
+ *            200 - 2 quality; entry = clip((base * scale + 50) / 100, 1, 255).  Computed on the host in the call and
+ *            handed to the kernel by value.
+ *   convert  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *            Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   edges    columns past the image replicate the last column (out to a multiple of 16); input rows replicate the last row
+ *            up to an even height only; C = (the 2 x 2 sum + bias) >> 2 with bias 1 in even and 2 in odd chroma columns;
+ *            then every plane, the downsampled chroma planes too, is padded to a multiple of 8 rows with its own last row
+ *   DCT      jfdctint.c on sample - 128, rows then columns; quantisation c = (|v| + 4 q) / (8 q) with the sign of v put
+ *            back, truncating; coefficient = c * q; jidctint.c, columns (D(., 11)) then rows (D(., 18)), + 128, clipped
+ *   upsample jdsample.c h2v2_fancy_upsample on the chroma planes cropped to ceil(S / 2): for row 2 r + v,
+ *            s[x] = 3 C[r][x] + C[r - 1 + 2 v][x]; out[2 x] = (3 s[x] + s[x - 1] + 8) >> 4,
+ *            out[2 x + 1] = (3 s[x] + s[x + 1] + 7) >> 4; a missing row or column is the row or column itself
+ *   convert  with u = Cb - 128, v = Cr - 128: R = Y + ((91881 v + 32768) >> 16), B = Y + ((116130 u + 32768) >> 16),
+ *            G = Y + ((-22554 u - 46802 v + 32768) >> 16), clipped to 0 .. 255
+ * Two launches on `stream`: one block per 32 x 32 tile (convert, downsample, both transforms through LDS; Y' into the
+ * word's low byte, Cb' and Cr' into the workspace), then the upsampling and conversion back per pixel.  Nothing is
+ * allocated or synchronised, no atomics, plain stores: the store is bitwise the same from call to call.
+ * tests/jpeg_model.py is this arithmetic in numpy, checked against PIL (Pillow with libjpeg-turbo).
+ * OCC_ERR_ARG before any launch for a null pointer, a workspace at an odd address, img outside 1 .. 4096, n outside
+ * 1 .. 65535, quality outside 1 .. 100 or m_frames < 1.
+ */
+int occ_dataset_jpeg_query(int img, int n, int quality, size_t* workspace_bytes);
+int occ_dataset_jpeg(uint32_t* rgbl, int m_frames, int img, const int64_t* slot, int n, int quality, void* workspace,
+                     void* stream);
+
+/*
  * The counts of pretrainer.py:133-139 per env: with p = pred > 0.5 and t = target > 0.5 over the img x img pixels,
  * counts[env] = { #(p == t), #(p and t), #(p or t) } (int64).  pred is (n_env,img,img) contiguous; target is read at
  * target[(env * img * img + pixel) * target_stride] (1 = contiguous, 4 = the alpha channel of an (n_env,img,img,4)

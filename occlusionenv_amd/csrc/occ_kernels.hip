@@ -53,6 +53,8 @@
 //                       sum pass for contrast's mean and an output pass
 //   occ_datapack_*      rendered frames into that dataset's store (occ_datapack.hpp): img_as_ubyte, depth * 51 and the
 //                       occlusion label per pixel, then PIL's convert("1") error diffusion in place, one wave per frame
+//   occ_jpeg_*          the JPEG round trip in place in that store (occ_jpeg.hpp): libjpeg's 4:2:0 encode and decode without
+//                       the entropy coding, a pass per 32 x 32 tile through LDS and the chroma upsampling pass
 //
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
@@ -89,6 +91,7 @@ namespace occ {
 #include "occ_augment.hpp"
 #include "occ_datapack.hpp"
 #include "occ_resize.hpp"
+#include "occ_jpeg.hpp"
 
 }  // namespace occ
 
@@ -1045,6 +1048,32 @@ extern "C" int occ_dataset_resize(const uint32_t* src_rgbl, const int16_t* src_d
     hipLaunchKernelGGL(occ_resize_table_kernel, dim3((S + 63) / 64), dim3(64), 0, st, R, S, K, t);
     hipLaunchKernelGGL(occ_resize_kernel, dim3(tiles * tiles, n), dim3(kResizeBlock), 0, st, src_rgbl, src_depth, R, slot, dst_rgbl,
                        dst_depth, m_frames, S, K, t);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// ---- the JPEG round trip in place in the resident store (occ_jpeg.hpp) ------------------------------------------------------
+static bool jpeg_shape_ok(int img, int n, int quality) {
+    return img >= 1 && img <= kJpegMaxImg && n >= 1 && n <= 65535 && quality >= 1 && quality <= 100;
+}
+
+extern "C" int occ_dataset_jpeg_query(int img, int n, int quality, size_t* workspace_bytes) {
+    if (!jpeg_shape_ok(img, n, quality) || !workspace_bytes) return OCC_ERR_ARG;
+    const size_t cs = (size_t)jpeg_chroma_side(img);
+    *workspace_bytes = (size_t)n * cs * cs * sizeof(uint16_t);
+    return OCC_OK;
+}
+
+extern "C" int occ_dataset_jpeg(uint32_t* rgbl, int m_frames, int img, const int64_t* slot, int n, int quality, void* workspace,
+                                void* stream) {
+    if (!non_null(rgbl, slot, workspace) || ((uintptr_t)workspace & 1) != 0) return OCC_ERR_ARG;
+    if (!jpeg_shape_ok(img, n, quality) || m_frames < 1) return OCC_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const JpegTables tab = jpeg_tables(quality);
+    const int tiles = (img + kJpegTile - 1) / kJpegTile, cs = jpeg_chroma_side(img);
+    hipLaunchKernelGGL(occ_jpeg_block_kernel, dim3(tiles * tiles, n), dim3(kJpegBlock), 0, st, rgbl, m_frames, img, slot, tab,
+                       (uint16_t*)workspace, cs);
+    hipLaunchKernelGGL(occ_jpeg_upsample_kernel, dim3((img * img + kJpegBlock - 1) / kJpegBlock, n), dim3(kJpegBlock), 0, st, rgbl,
+                       m_frames, img, slot, (const uint16_t*)workspace, cs);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

@@ -27,9 +27,11 @@ def _ubyte(a: np.ndarray) -> np.ndarray:
 
 
 class RunWriter:
-    """One ``run_%d`` directory."""
+    """One ``run_%d`` directory.  ``jpeg_quality``: None writes the colour image with PIL's default quality (75), an
+    integer is passed to ``Image.save(quality=)``; ``cv2.imwrite``, the reference's writer, defaults to 95."""
 
-    def __init__(self, root: str, run: int):
+    def __init__(self, root: str, run: int, jpeg_quality=None):
+        self.jpeg_quality = None if jpeg_quality is None else int(jpeg_quality)
         self.dir = osp.join(root, "run_%d" % run)
         for sub in ("Depth", "RGB", "Occl"):
             os.makedirs(osp.join(self.dir, sub), exist_ok=True)
@@ -38,7 +40,8 @@ class RunWriter:
     def write_frame(self, j: int, obs_chw: np.ndarray, occl_hw: np.ndarray, elevation: float, azimuth: float, grad) -> None:
         img = np.transpose(obs_chw, (1, 2, 0))  # (S,S,4), datasetGenerator.py:102
         rgb = _ubyte(img[..., :3])
-        Image.fromarray(rgb[..., ::-1].copy()).save(osp.join(self.dir, "RGB", "%d.jpg" % j))  # cv2 writes BGR
+        opt = {} if self.jpeg_quality is None else {"quality": self.jpeg_quality}
+        Image.fromarray(rgb[..., ::-1].copy()).save(osp.join(self.dir, "RGB", "%d.jpg" % j), **opt)  # cv2 writes BGR
         Image.fromarray(_ubyte(occl_hw)).save(osp.join(self.dir, "Occl", "%d.png" % j))
         depth = img[..., 3].copy()
         depth[depth == -1] = 0
@@ -51,8 +54,9 @@ class RunWriter:
 
 
 def generate(venv, root: str, num_frames: int = 20, lr: float = 2.5e-2, first_run: int = 0, generator=None,
-             max_steps: int = 0) -> int:
-    """datasetGenerator.py:76-124 for all envs of ``venv`` at once; returns the number of runs written.
+             max_steps: int = 0, jpeg_quality=None) -> int:
+    """datasetGenerator.py:76-124 for all envs of ``venv`` at once; returns the number of runs written.  ``jpeg_quality``
+    goes to every ``RunWriter``.
 
     Like the reference, every run stays on ONE scene for all its frames: the envs are stepped through the engine
     directly (``OcclusionEnv.step`` semantics, datasetGenerator.py:88), not through ``SimpleVecEnv.step`` whose
@@ -62,7 +66,7 @@ def generate(venv, root: str, num_frames: int = 20, lr: float = 2.5e-2, first_ru
     os.makedirs(root, exist_ok=True)
     N = venv.num_envs
     eng = venv.engine
-    writers = [RunWriter(root, first_run + i) for i in range(N)]
+    writers = [RunWriter(root, first_run + i, jpeg_quality=jpeg_quality) for i in range(N)]
     venv.reset()
     venv._drain()  # no auto-reset report may be pending while the engine is driven directly
     frame = np.zeros(N, dtype=np.int64)

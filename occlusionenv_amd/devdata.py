@@ -17,15 +17,24 @@ Batches are ``(img, occlusion, grad, pos)``, the reference's order, which is wha
 
 The store can also be filled on the device (csrc/occ_datapack.hpp, ``occ_dataset_pack``): ``DeviceDataset.empty`` plus
 ``put`` per engine step, which is what ``generate_resident`` does in ``dataset_io.generate``'s loop.  ``put`` gives a frame
-the bits the writer and ``from_directory`` at the same size would (``tests/datapack_model.py``), the JPEG apart.
+the bits the writer and ``from_directory`` at the same size would (``tests/datapack_model.py``), the JPEG apart unless
+``put(jpeg=quality)`` asks for it (below).
 
 The resize is reproduced too (csrc/occ_resize.hpp, ``occ_dataset_resize``): the reference renders 512 x 512 and its reader
 shrinks every item to 256 x 256 with ``Image.resize`` (``dataset.py:65-67``: bicubic for the colours and the depth, nearest
 for the dithered label).  ``put(resize=True)`` packs at the rendering size and resizes into the store,
 ``generate_resident(size=256)`` does that for every step of an env that renders at 512, and ``resized`` does it to a whole
-store; the arithmetic is PIL's bit for bit (``tests/resize_model.py``, checked against PIL and against the files).  So from
-the engine's step to the batch everything is on the device, with the bits the reference's files-and-PIL path would give.
-Still not reproduced: the JPEG, the worker RNG stream (above), and the pairing ``from_directory`` inherits from the
+store; the arithmetic is PIL's bit for bit (``tests/resize_model.py``, checked against PIL and against the files).
+
+So is the JPEG (csrc/occ_jpeg.hpp, ``occ_dataset_jpeg``), the one lossy stage of that path: the reference writes every
+colour image as a 4:2:0 baseline JPEG at the rendering size (``datasetGenerator.py:104``) and trains on the decoded result.
+Entropy coding is lossless, so writing and reading the file is integer arithmetic on the pixels and two quantisation tables
+(``tests/jpeg_model.py``, checked against PIL's save and open bit for bit).  ``DeviceDataset.jpeg(quality)`` does it in
+place, ``put(jpeg=quality)`` where the file would be written (after the pack at the rendering size, before the resize) and
+``generate_resident(jpeg=quality)`` in every step.  ``cv2.imwrite``, the reference's writer, defaults to quality 95 and
+PIL's ``save`` to 75; ``dataset_io.RunWriter(jpeg_quality=)`` sets it for the files.  So from the engine's step to the batch
+everything is on the device, with the bits the reference's files-and-PIL path would give, colours included.
+Still not reproduced: the worker RNG stream (above), and the pairing ``from_directory`` inherits from the
 reference's lexicographic file sort (``0, 1, 10, .., 19, 2, ..`` against numerically ordered labels: images of runs with
 more than 10 frames get other frames' ``pos`` / ``grad``); a generated store is run-major, frame ``j`` numeric, every image
 with its own labels.
@@ -106,6 +115,23 @@ def resize_workspace_bytes(src_size: int, dst_size: int, n: int = 1) -> int:
     if nat.load().occ_dataset_resize_query(int(src_size), int(dst_size), int(n), C.byref(need)) != 0:
         raise ValueError("resize %d -> %d of %d frames is not supported: sizes in 1 .. 4096, src / dst <= 2 or src <= 72, "
                          "1 .. 65535 frames" % (src_size, dst_size, n))
+    return int(need.value)
+
+
+def _quality(jpeg, who: str) -> int:
+    if isinstance(jpeg, bool) or not isinstance(jpeg, (int, np.integer)) or not 1 <= int(jpeg) <= 100:
+        raise ValueError("%s: the JPEG quality is an integer in 1 .. 100" % who)
+    return int(jpeg)
+
+
+def jpeg_workspace_bytes(size: int, n: int = 1, quality: int = 75) -> int:
+    """``occ_dataset_jpeg_query``: the workspace of a JPEG round trip of ``n`` frames of ``size`` x ``size`` pixels, or
+    ``ValueError`` for what the library refuses (``size`` outside 1 .. 4096, ``n`` outside 1 .. 65535, ``quality`` outside
+    1 .. 100).  No GPU is touched."""
+    need = C.c_size_t()
+    if nat.load().occ_dataset_jpeg_query(int(size), int(n), int(quality), C.byref(need)) != 0:
+        raise ValueError("JPEG round trip of %d frames of %d x %d at quality %d is not supported: sizes in 1 .. 4096, "
+                         "1 .. 65535 frames, quality 1 .. 100" % (n, size, size, quality))
     return int(need.value)
 
 
@@ -224,12 +250,44 @@ class DeviceDataset:
                              torch.arange(lo, lo + rows, dtype=torch.int64, device=self.device))
         return out
 
+    def _jpeg_slots(self, slots_dev: torch.Tensor, quality: int) -> None:
+        """One ``occ_dataset_jpeg`` on the frames ``slots_dev`` (int64 on this store's device, at most 65535)."""
+        n = int(slots_dev.shape[0])
+        with torch.cuda.device(self.device):
+            ws = torch.empty(jpeg_workspace_bytes(self.size, n, quality) // 2, dtype=torch.int16, device=self.device)
+            nat.check(nat.load().occ_dataset_jpeg(nat.ptr(self.rgbl), len(self), self.size, nat.ptr(slots_dev), n, quality,
+                                                  nat.ptr(ws), nat.stream_ptr(self.device)), "occ_dataset_jpeg")
+
+    def jpeg(self, quality: int, frames=None) -> None:
+        """The colours of all frames, or of the distinct frame numbers ``frames`` (a host tensor or a list), through
+        ``occ_dataset_jpeg`` (csrc/occ_jpeg.hpp) in place: what ``Image.save(format="JPEG", quality=quality)`` and
+        ``Image.open(...).convert("RGB")`` do to them (libjpeg's 4:2:0 baseline round trip; tests/jpeg_model.py).  Depth,
+        label, ``pos`` and ``grad`` stay."""
+        q = _quality(quality, "jpeg")
+        jpeg_workspace_bytes(self.size, 1, q)  # ValueError for a size the kernel does not take
+        idx = None
+        if frames is not None:
+            idx = torch.as_tensor(frames).reshape(-1)
+            if idx.is_floating_point() or idx.dtype == torch.bool:
+                raise ValueError("jpeg: frames are integers")
+            idx = idx.to("cpu", torch.int64)
+            if idx.numel() < 1 or int(idx.min()) < 0 or int(idx.max()) >= len(self) or idx.unique().numel() != idx.numel():
+                raise ValueError("jpeg: frames are distinct frame numbers in [0, %d)" % len(self))
+        if self.device.type != "cuda":
+            raise nat.NativeError("DeviceDataset.jpeg runs on the GPU only (this store is on %s); there is no CPU path" % self.device)
+        if idx is None:
+            idx = torch.arange(len(self), dtype=torch.int64)
+        idx = idx.to(self.device)
+        for lo, rows in nat.row_chunks(int(idx.numel()), 65535):
+            self._jpeg_slots(idx[lo:lo + rows].contiguous(), q)
+
     def put(self, obs: torch.Tensor, full_state: torch.Tensor, slots, pos=None, grad=None, label: str = "dither",
-            resize: bool = False) -> None:
+            resize: bool = False, jpeg=None) -> None:
         """Write the frames of one engine step into the store, on the device, in one ``occ_dataset_pack`` call
         (csrc/occ_datapack.hpp): env ``i`` of ``obs`` (n,4,S,S) and ``full_state`` (n,S,S,4; its alpha channel is the
         occlusion image; an (n,S,S) alpha image is taken too) becomes frame ``slots[i]`` with the bits
-        ``dataset_io.RunWriter`` and ``from_directory`` at the same size would give it, the JPEG apart: ``img_as_ubyte``
+        ``dataset_io.RunWriter`` and ``from_directory`` at the same size would give it, the JPEG apart (see ``jpeg``):
+        ``img_as_ubyte``
         colours with B and R swapped, ``depth * 51`` truncated, and the label by ``label="dither"`` (PIL's
         ``convert("1")`` of the 8-bit alpha, what the reader does to the file) or ``"threshold"`` (``alpha > 0.5``, the
         rule of ``pretrainer.py:134``).  ``slots``: n int64 on the device or the host; an env whose slot is outside
@@ -240,10 +298,16 @@ class DeviceDataset:
         ``resize=False``: there is no resize, ``obs`` has the store's size.  ``resize=True``: an ``obs`` of another size
         R x R is packed at R (either label rule; the dither runs at R) into a staging store of ``n`` frames that the
         dataset keeps per ``(n, R)``, and the staged frames go through ``occ_dataset_resize`` (csrc/occ_resize.hpp) into
-        ``slots``: the bits of the writer at R and ``from_directory`` at the store's size, the JPEG apart.  With R equal
-        to the store's size it is the single pack call."""
+        ``slots``: the bits of the writer at R and ``from_directory`` at the store's size, the JPEG apart (see ``jpeg``).  With R
+        equal to the store's size it is the single pack call.
+
+        ``jpeg``: None, or the quality (1 .. 100) of the JPEG round trip (``occ_dataset_jpeg``, csrc/occ_jpeg.hpp) that
+        then runs on the packed colours where the writer's file would be: after the pack at R, before the resize, so on
+        the staging store with ``resize=True`` and R != S, on the named slots otherwise.  The frames then have the bits of
+        ``RunWriter(jpeg_quality=jpeg)`` and ``from_directory``, colours included."""
         if label not in LABEL_MODES:
             raise ValueError("label: 'dither' or 'threshold'")
+        q = None if jpeg is None else _quality(jpeg, "put")
         S = self.size
         if obs.ndim != 4 or obs.shape[1] != 4 or obs.shape[-1] != obs.shape[-2] or (not resize and obs.shape[-1] != S):
             raise ValueError("put: obs (n,4,%d,%d): the env renders at the dataset's size (resize=True: at any square size)" % (S, S))
@@ -257,6 +321,8 @@ class DeviceDataset:
             raise ValueError("put: slots are n integers")
         if R != S:
             resize_workspace_bytes(R, S, n)  # ValueError for sizes the kernel does not take
+        if q is not None:
+            jpeg_workspace_bytes(R, n, q)
         if self.device.type != "cuda":
             raise nat.NativeError("DeviceDataset.put runs on the GPU only (this store is on %s); there is no CPU path" % self.device)
         s = s.reshape(n).to(self.device, torch.int64).contiguous()
@@ -274,6 +340,8 @@ class DeviceDataset:
             nat.check(nat.load().occ_dataset_pack(nat.ptr(obs), nat.ptr(fs, 12 if stride == 4 else 0), stride, n, R,
                                                   nat.ptr(into_slots), nat.ptr(into.rgbl), nat.ptr(into.depth), len(into),
                                                   LABEL_MODES[label], nat.stream_ptr(self.device)), "occ_dataset_pack")
+            if q is not None:
+                into._jpeg_slots(into_slots, q)
             if R != S:
                 self._resize_into(into.rgbl, into.depth, s)
             if pos is not None or grad is not None:
@@ -376,7 +444,8 @@ class EpochLoader:
 
 
 def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5e-2, generator=None, max_steps: int = 0,
-                      label: str = "dither", grad_mode: str = "sincos", split: str = "train", size=None) -> DeviceDataset:
+                      label: str = "dither", grad_mode: str = "sincos", split: str = "train", size=None,
+                      jpeg=None) -> DeviceDataset:
     """``dataset_io.generate``'s loop (datasetGenerator.py:76-124) into a ``DeviceDataset`` instead of files: ``num_runs``
     runs of ``num_frames`` frames at the env's own size, frame ``j`` of run ``r`` at index ``r * num_frames + j`` with its
     own ``pos`` (elevation, azimuth) and ``grad``.  Nothing of a frame leaves the device: every step is one
@@ -393,7 +462,10 @@ def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5
 
     ``size``: None stores the frames at the env's own size.  Another ``size`` gives a store of that size, every step going
     through ``put(resize=True)``: rendered at the env's size (the reference: 512), packed there, resized on the device as
-    the reference's reader resizes its files (to 256), see ``DeviceDataset.put``."""
+    the reference's reader resizes its files (to 256), see ``DeviceDataset.put``.
+
+    ``jpeg``: None, or the JPEG quality every ``put`` is given: the colours go through the writer's JPEG at the rendering
+    size, as ``dataset_io.generate(jpeg_quality=)`` followed by ``from_directory`` would have them."""
     if grad_mode not in ("sincos", "raw"):
         raise ValueError("grad_mode: 'sincos' or 'raw'")
     if label not in LABEL_MODES:
@@ -403,6 +475,10 @@ def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5
         raise ValueError("generate_resident: at least one run of one frame")
     eng, N = venv.engine, venv.num_envs
     dev, M = eng.device, num_runs * num_frames
+    if jpeg is not None:
+        jpeg_workspace_bytes(eng.S, N, _quality(jpeg, "generate_resident"))  # ValueError for what the kernel does not take
+        if dev.type != "cuda":
+            raise nat.NativeError("generate_resident(jpeg=) runs on the GPU only (the engine is on %s); there is no CPU path" % dev)
     if size is not None:
         if isinstance(size, bool) or not isinstance(size, (int, np.integer)):
             raise ValueError("generate_resident: size is an integer or None")
@@ -436,7 +512,7 @@ def generate_resident(venv, num_runs: int, num_frames: int = 20, lr: float = 2.5
             g = a.grad.detach()
             good = pending & ~torch.isnan(g).any(1)
             slot = torch.where(good, run * num_frames + frame, torch.full_like(frame, -1))
-            ds.put(obs, full_state, slot, label=label, resize=size is not None)
+            ds.put(obs, full_state, slot, label=label, resize=size is not None, jpeg=jpeg)
             row = torch.where(good, slot, torch.full_like(frame, M))
             elaz[row] = torch.stack([eng.elevation.reshape(N), eng.azimuth.reshape(N)], 1).to(torch.float32)
             graw[row] = g.to(torch.float32)
