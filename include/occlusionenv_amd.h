@@ -108,7 +108,9 @@ typedef struct OccScene {
     const int64_t* mesh_atlas_off;  /* (n_meshes) float offset of each mesh's atlas in pool_atlas, -1 = white vertices */
     int32_t atlas_res;              /* R */
     /* optional (n_env) int32: nonzero = do not render this scene row in this launch (its outputs are left
-     * untouched); used for reserve slots that are not under test (occ_auto_reset keeps it up to date) */
+     * untouched, and in an occ_step launch so are its camera row, el / az, cam_pos_out and the OccStepFinish state);
+     * used for reserve slots that are not under test (occ_auto_reset keeps it up to date) and for the envs an
+     * evaluation has frozen (occ_episode_advance) */
     const int32_t* skip;
     /* optional (n_env,S,S) f32 weight of every pixel's term of the loss: loss = sum_p w_p * full_state[p,3]^2 and
      * its gradient likewise (NULL = 1 everywhere = environment.py:381).  Images are not affected.  Used to score a
@@ -1021,6 +1023,39 @@ int occ_object_mass(const float* alphas, int n_rows, int img, const int32_t* gat
  */
 int occ_reserve_refill(const int32_t* packed, int n, int n_env, int n_reserve, int32_t* scene_mesh, float* scene_offset,
                        int32_t* rs_state, int32_t* skip, void* stream);
+
+/*
+ * Episode bookkeeping of the batched controller evaluation (additive in ABI 12; csrc/occ_episode.hpp): what the
+ * reference's evaluation loops do on the host after every env.step (test.py:92-255, iterator.py:104-204), for n_env
+ * envs in one launch after a batched step with index `step` (0-based) of at most max_step.
+ *   done (n) u8, reward (n), full_reward (n)   the step's outputs (the reward arrays are read for the traces only)
+ *   grad (n,2)   the step's d reward / d action          read by OCC_EPISODE_GRADIENT only
+ *   noise (n,2)  standard normal draws                   read by OCC_EPISODE_RANDOM only
+ *   pred (n,2)   the network's predicted gradient, or the agent's sampled action   read by _MODEL and _AGENT only
+ * State, per env: action (n,2) f32, active (n) int32, skip (n) int32 (the OccScene.skip mask of the next step),
+ * iterations (n) int32, finished (n) u8, nan_steps (n) int32; trace_reward / trace_full_reward (max_step, n) f32 or NULL,
+ * pre-filled by the caller (with NaN).  For an env with active != 0:
+ *   GRADIENT  a NaN in grad: nan_steps += 1 and nothing else of this step happens (`continue`, iterator.py:118-120);
+ *             otherwise action = fadd(action, fmul(lr, grad)): two roundings, as torch's `action += lr * action.grad`
+ *   RANDOM    action = fadd(action, fmul(lr, noise))
+ *   MODEL     action = fmul(-lr, pred)                    (lr is the reference's step_lr)
+ *   AGENT     action = pred
+ * then (not on a NaN step) row `step` of the traces is written; done: iterations = step + 1, finished = 1, active = 0,
+ * skip = 1; else step == max_step - 1 (the cap, test.py:122-124): iterations = step + 1, active = 0, skip = 1.  The cap
+ * also ends an env on a NaN step (the reference would leave no entry for such an episode).  An env with active == 0 has
+ * nothing read and nothing written.  report[0] = the number of envs still active after the call.
+ * One launch of one block on `stream`; no atomics, nothing allocated or synchronised.  OCC_ERR_ARG before the launch for
+ * a null pointer among those the rule reads or the state, a trace without its input, n_env < 1, a rule outside 0..3, or
+ * step outside [0, max_step).
+ */
+#define OCC_EPISODE_GRADIENT 0
+#define OCC_EPISODE_RANDOM 1
+#define OCC_EPISODE_MODEL 2
+#define OCC_EPISODE_AGENT 3
+int occ_episode_advance(const uint8_t* done, const float* reward, const float* full_reward, const float* grad,
+                        const float* pred, const float* noise, int rule, float lr, int step, int max_step, int n_env,
+                        float* action, int32_t* active, int32_t* skip, int32_t* iterations, uint8_t* finished,
+                        int32_t* nan_steps, float* trace_reward, float* trace_full_reward, int32_t* report, void* stream);
 
 /*
  * Measurement hooks (bench.py only; not part of the reference surface).  While enabled, occ_render

@@ -27,7 +27,7 @@ import torch
 from . import _native as nat
 from .baseVecEnv import VecEnv
 from .engine import OcclusionEngine
-from .environment import shared_pool
+from .environment import reset_rng, shared_pool
 
 RECYCLE_SETS = 4  # persistent output sets of the recycled-outputs pool (engine.OcclusionEngine.output_recycle)
 
@@ -468,7 +468,7 @@ class SimpleVecEnv(VecEnv):
         return obs_all
 
     def reset(self):
-        az = [np.random.default_rng().uniform(low=-40, high=40) for _ in range(self.num_envs)]
+        az = [reset_rng().uniform(low=-40, high=40) for _ in range(self.num_envs)]
         obs = self._reset_envs(list(range(self.num_envs)), az)
         if self.engine.R:
             self._warm_reserve()

@@ -151,6 +151,7 @@ class OccReserveStore(C.Structure):
 
 
 RS_EMPTY, RS_PENDING, RS_READY = 0, 1, 2
+EPISODE_GRADIENT, EPISODE_RANDOM, EPISODE_MODEL, EPISODE_AGENT = 0, 1, 2, 3  # the rules of occ_episode_advance
 
 
 class OccEncoderConfig(C.Structure):
@@ -268,6 +269,7 @@ SYMBOLS = {
                                     C.c_void_p]),
     "occ_seg_criterion_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "occ_episode_advance": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10),
     "occ_profile_enable": (C.c_int, [C.c_int]),
     "occ_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

@@ -55,6 +55,8 @@
 //                       occlusion label per pixel, then PIL's convert("1") error diffusion in place, one wave per frame
 //   occ_jpeg_*          the JPEG round trip in place in that store (occ_jpeg.hpp): libjpeg's 4:2:0 encode and decode without
 //                       the entropy coding, a pass per 32 x 32 tile through LDS and the chroma upsampling pass
+//   occ_episode_kernel  the episode bookkeeping of the batched controller evaluation (occ_episode.hpp): the controller's
+//                       action update, traces, finished / cap test and the freeze of the envs that are through, one launch
 //
 // No MFMA: the path is rasterisation.  fp32 throughout.
 
@@ -92,6 +94,7 @@ namespace occ {
 #include "occ_datapack.hpp"
 #include "occ_resize.hpp"
 #include "occ_jpeg.hpp"
+#include "occ_episode.hpp"
 
 }  // namespace occ
 
@@ -621,6 +624,24 @@ extern "C" int occ_reserve_refill(const int32_t* packed, int n, int n_env, int n
     if (!packed || n < 0 || n_env <= 0 || n_reserve <= 0 || !scene_mesh || !scene_offset || !rs_state || !skip) return OCC_ERR_ARG;
     hipLaunchKernelGGL(occ_refill_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, packed, n, n_env, n_reserve, scene_mesh,
                        scene_offset, rs_state, skip);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_episode_advance(const uint8_t* done, const float* reward, const float* full_reward, const float* grad,
+                                   const float* pred, const float* noise, int rule, float lr, int step, int max_step, int n_env,
+                                   float* action, int32_t* active, int32_t* skip, int32_t* iterations, uint8_t* finished,
+                                   int32_t* nan_steps, float* trace_reward, float* trace_full_reward, int32_t* report,
+                                   void* stream) {
+    if (!done || !action || !active || !skip || !iterations || !finished || !nan_steps || !report || n_env <= 0 || max_step <= 0 ||
+        step < 0 || step >= max_step || rule < OCC_EPISODE_GRADIENT || rule > OCC_EPISODE_AGENT)
+        return OCC_ERR_ARG;
+    if ((rule == OCC_EPISODE_GRADIENT && !grad) || (rule == OCC_EPISODE_RANDOM && !noise) || (rule >= OCC_EPISODE_MODEL && !pred))
+        return OCC_ERR_ARG;
+    if ((trace_reward && !reward) || (trace_full_reward && !full_reward)) return OCC_ERR_ARG;
+    EpisodeArgs a{done, reward, full_reward, grad, pred, noise, rule, lr, step, max_step, n_env, action, active, skip, iterations,
+                  finished, nan_steps, trace_reward, trace_full_reward, report};
+    const int threads = n_env >= 1024 ? 1024 : ((n_env + 63) & ~63);
+    hipLaunchKernelGGL(occ_episode_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

@@ -266,7 +266,8 @@ __device__ __forceinline__ RecSpan rec_span(const WS& ws, int rec_cap, int eo) {
 // Objects that no longer fit into rec_total get an empty span and raise OCC_STATUS_REC_OVERFLOW.
 // The launch's prologue as well: the eight work-queue heads and the header of the work-item order are zeroed here
 // (two memset launches less in a sequence of ~25 dependent small launches at ~5 us each).
-// A STEP launch (occ_step) folds the camera update in: blocks 1.. take 1024 envs each (OccCameraArgs; cam_args.n = 0: none).
+// A STEP launch (occ_step) folds the camera update in: blocks 1.. take 1024 envs each (OccCameraArgs; cam_args.n = 0: none);
+// rows of the skip mask are left out of it like out of everything else.
 __global__ __launch_bounds__(1024) void occ_recoff_kernel(OccScene sc, long long* __restrict__ rec_off, long long rec_total,
                                                           int* __restrict__ status, uint32_t* __restrict__ queue,
                                                           uint32_t* __restrict__ order_hdr, OccCameraArgs cam_args,
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(1024) void occ_recoff_kernel(OccScene sc, long long
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (blockIdx.x > 0) {
         const int n = (int)(blockIdx.x - 1) * 1024 + tid;
-        if (n < cam_args.n)
+        if (n < cam_args.n && !(sc.skip && sc.skip[n]))  // a skipped row keeps its camera, its angles and its position
             camera_one(cam_args.mode, cam_args.action, cam_args.el, cam_args.az, cam_args.radius, cam, cam_args.cam_pos_out,
                        cam_args.cam_pos_out2, n);
         return;

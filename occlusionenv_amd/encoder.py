@@ -423,7 +423,14 @@ class FrozenEncoder:
         (model.py:81-85)."""
         if self.grad_w is None:
             raise ValueError("this checkpoint has no gradPredictor / output head")
-        g = torch.addmm(self.grad_b, self(obs), self.grad_w.t())
+        return self.grad_head(self(obs))
+
+    @torch.no_grad()
+    def grad_head(self, feats: torch.Tensor) -> torch.Tensor:
+        """The head of ``predict_grad`` alone, on pooled features (N,256) that a caller already holds."""
+        if self.grad_w is None:
+            raise ValueError("this checkpoint has no gradPredictor / output head")
+        g = torch.addmm(self.grad_b, feats, self.grad_w.t())
         return torch.tanh(g) if self.grad_tanh else g
 
     # ---- segmentation decoder --------------------------------------------------------------------------------------

@@ -417,10 +417,17 @@ class OcclusionEngine:
             setattr(ca, name, None if t is None else t.data_ptr())
         return ca
 
-    def _render(self, idx: Optional[torch.Tensor], cam_mode: int, cam_input: Optional[torch.Tensor], flags: int, finish=None):
+    def _render(self, idx: Optional[torch.Tensor], cam_mode: int, cam_input: Optional[torch.Tensor], flags: int, finish=None,
+                skip: Optional[torch.Tensor] = None, idx_host=None):
         """Camera + render for all envs (idx None) or the compact subset idx, one occ_step call.  ``finish``: an
-        OccStepFinish whose reward bookkeeping the launch does as well.  Returns a dict of fresh tensors."""
-        rows = self._mesh_host[: self.N] if idx is None else self._mesh_host[idx.cpu().numpy()]
+        OccStepFinish whose reward bookkeeping the launch does as well.  ``skip``: the OccScene.skip mask of the launch's
+        rows (``step``).  ``idx_host``: ``idx`` on the host, when the caller has it (the record arrays are sized from the
+        host copy of the mesh ids; without it ``idx`` is copied back, which waits for the stream).  Returns a dict of fresh
+        tensors."""
+        if idx is None:
+            rows = self._mesh_host[: self.N]
+        else:
+            rows = self._mesh_host[idx.cpu().numpy() if idx_host is None else idx_host]
         ws = self._ensure_workspace(self._records_needed(rows))
         d, S = self.device, self.S
         f32 = dict(dtype=torch.float32, device=d)
@@ -432,9 +439,12 @@ class OcclusionEngine:
         else:
             n = int(idx.numel())
             el, az, rad = self.elevation[idx], self.azimuth[idx], self.radius[idx]
-            cam = torch.empty(n, nat.CAM_STRIDE, **f32)
-            campos = torch.empty(n, 3, **f32)
-            alphas = torch.empty(n, 3, S, S, **f32)
+            if skip is None:
+                cam = torch.empty(n, nat.CAM_STRIDE, **f32)
+                campos = torch.empty(n, 3, **f32)
+                alphas = torch.empty(n, 3, S, S, **f32)
+            else:  # the launch leaves skipped rows alone: what is scattered back below must be what the rows hold now
+                cam, campos, alphas = self.cam[idx], self.camera_position[idx], self.alphas[idx]
             smesh, soff = self.scene_mesh[idx].contiguous(), self.scene_offset[idx].contiguous()
         st = self._stream()
         cam_in = None if cam_input is None else cam_input.contiguous()
@@ -460,7 +470,7 @@ class OcclusionEngine:
         pw = None
         if self.pixel_weight is not None:
             pw = self.pixel_weight if idx is None else self.pixel_weight[idx].contiguous()
-        sc = self._scene_struct(n, smesh, soff, pix_weight=pw)
+        sc = self._scene_struct(n, smesh, soff, skip=skip, pix_weight=pw)
         nat.check(self.lib.occ_step(C.byref(sc), C.byref(ca), _p(cam), C.byref(ws), C.byref(ro), flags, self.K, st), "occ_step")
         if idx is not None:
             if cam_mode == nat.CAM_STEP:
@@ -473,7 +483,7 @@ class OcclusionEngine:
         elif flags & nat.RENDER_SOFT:
             self._alpha_touch(slice(0, n))  # an untracked launch wrote whole frames
         out["cam"] = cam
-        out["_keep"] = (smesh, soff, el, az, rad, cam_in, pw)  # keep temporaries alive until the stream is done with them
+        out["_keep"] = (smesh, soff, el, az, rad, cam_in, pw, skip)  # keep temporaries alive until the stream is done with them
         return out
 
     def reset_render(self, env_ids=None, radius=4.0, azimuth=0.0, elevation=0.0):
@@ -654,16 +664,36 @@ class OcclusionEngine:
                                           _p(flags), self._stream()), "occ_step_flags")
         return flags
 
-    def step(self, actions: torch.Tensor, env_ids=None, with_reserve: bool = False, pre_launch=None):
+    def step(self, actions: torch.Tensor, env_ids=None, with_reserve: bool = False, pre_launch=None, skip=None,
+             env_ids_host=None):
         """Batched step(): returns (obs (n,4,S,S), reward (n,) [autograd-attached], done (n,) bool, full_state, loss).
+        ``skip`` (not together with ``with_reserve``): an (n,) int32 device mask, row for row with ``actions``.  A row with
+        ``skip != 0`` does not take part in the launch (OccScene.skip): its ``elevation``, ``azimuth``, ``camera_position``,
+        ``full_reward`` and ``object_mass`` (and its camera and alphas rows) keep the bits they had after the row's last
+        rendered step, and its rows of EVERY tensor this call returns are undefined: nothing may read them.  The mask is read
+        when the launch runs, so a kernel earlier on the stream may have written it (``episodes.evaluate_controllers``).
+        ``env_ids_host``: the indices of a device tensor ``env_ids`` as a host array, from a caller that holds both: the step
+        then reads nothing back from the device (``env_ids`` given as a list or an array is its own host copy).
         ``with_reserve`` (whole-batch steps only) also renders the reserve scenes in the same launch sequence and
         returns a sixth item: the dict of whole-batch tensors (``obs_all``, ``loss_all`` ...).  ``pre_launch`` (with
         the reserve only) is called after every output is allocated and every argument struct is built, right
         before the first kernel launch: the place for a host sync that must precede this step."""
         idx = None if env_ids is None else torch.as_tensor(env_ids, dtype=torch.long, device=self.device).reshape(-1)
         n = self.N if idx is None else int(idx.numel())
+        if idx is not None:
+            if env_ids_host is None and not (torch.is_tensor(env_ids) and env_ids.is_cuda):
+                env_ids_host = env_ids.numpy() if torch.is_tensor(env_ids) else env_ids
+            if env_ids_host is not None:
+                env_ids_host = np.asarray(env_ids_host, dtype=np.int64).reshape(-1)
+                if env_ids_host.shape != (n,):
+                    raise ValueError(f"env_ids_host must hold the {n} indices of env_ids")
         if actions.shape != (n, 2):
             raise ValueError(f"actions must have shape ({n}, 2), got {tuple(actions.shape)}")
+        if skip is not None:
+            if with_reserve:
+                raise ValueError("skip= is the mask of a plain step; a step with the reserve keeps its own")
+            if skip.shape != (n,) or skip.dtype != torch.int32 or skip.device != self.device or not skip.is_contiguous():
+                raise ValueError(f"skip must be a contiguous int32 ({n},) tensor on {self.device}")
         need_grad = bool(actions.requires_grad and torch.is_grad_enabled())
         a = actions.detach().to(self.device, torch.float32).contiguous()
         flags = nat.RENDER_SOFT | nat.RENDER_HARD | (nat.RENDER_GRAD if need_grad else 0)
@@ -684,7 +714,7 @@ class OcclusionEngine:
             with_reserve = False
             if pre_launch is not None:
                 pre_launch()
-            out = self._render(idx, nat.CAM_STEP, a, flags, fin)
+            out = self._render(idx, nat.CAM_STEP, a, flags, fin, skip=skip, idx_host=env_ids_host)
         if idx is not None:
             self.full_reward[idx] = fr
         if need_grad:

@@ -67,6 +67,24 @@ def seed_scene_rng(seed=None) -> None:
     global _SCENE_RNG
     _SCENE_RNG = np.random.default_rng(seed)
 
+
+# SimpleVecEnv.reset() draws every env's azimuth from a fresh unseeded generator, as the reference does
+# (SubProcVecEnv.py:230-235); a scene is accepted by its loss at that azimuth, so the scenes a reset keeps depend on it.
+_RESET_RNG = None
+
+
+def seed_reset_rng(seed=None) -> None:
+    """Test hook: ``SimpleVecEnv.reset()`` draws its azimuths from one generator seeded here (None: back to a fresh
+    unseeded generator per draw).  With ``seed_scene_rng`` and ``np.random.seed`` a reset then keeps the same scenes."""
+    global _RESET_RNG
+    _RESET_RNG = None if seed is None else np.random.default_rng(seed)
+
+
+def reset_rng() -> np.random.Generator:
+    """The generator of one azimuth draw of ``SimpleVecEnv.reset()``."""
+    return _RESET_RNG if _RESET_RNG is not None else np.random.default_rng()
+
+
 # one pool per device, shared by every env/VecEnv in the process (a ShapeNet model is uploaded once)
 _POOLS: Dict[str, MeshPool] = {}
 

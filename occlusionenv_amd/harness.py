@@ -22,6 +22,11 @@
     statistics.  ``native_optimizer=True``: ``netoptim.PackedAdamW``, the AdamW step in packed order in one native launch.
   * ``pretrain`` -- pretrainer.py:209-259 (``PreTrainer.run``): per epoch ``pretrain_epoch``, ``validate_pretrained`` on the
     trained network, one step of the cosine schedule; the state dict of the best validation IoU is kept.
+  * ``evaluate_controllers`` -- test.py:92-255 / iterator.py:104-204, the experiment itself: the number of steps until
+    ``finished`` for the raw gradient, a random walk, the pretrained network's predicted gradient and the PPO agent
+    (``GradientAscent``, ``RandomWalk``, ``PredictedGradient``, ``Agent``) on the same scenes, all envs at once with the
+    episode bookkeeping on the device; ``write_iterations`` writes the reference's ``iterations_*.txt``,
+    ``summarise_iterations`` the means, medians and paired differences.  They live in ``episodes.py``.
 """
 from __future__ import annotations
 
@@ -30,6 +35,8 @@ from typing import Callable, Optional
 import torch
 
 from . import rollout
+from .episodes import (Agent, GradientAscent, PredictedGradient, RandomWalk, controller_generators,  # noqa: F401
+                       evaluate_controllers, summarise_iterations, write_iterations)
 
 
 def gradient_ascent(env, steps: int = 20, lr: float = 0.01, reset_kwargs: Optional[dict] = None):

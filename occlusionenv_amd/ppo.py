@@ -154,16 +154,19 @@ class BatchedPPO:
         return agent
 
     # ---- acting (PPO.py:152-164) ------------------------------------------------------------
+    def features(self, obs: torch.Tensor) -> torch.Tensor:
+        """obs (N,4,S,S) -> the (N,256) features the heads act on."""
+        if self.encoder is None:
+            return rollout.pooled_features(obs)
+        with torch.no_grad():  # PPO.py:154: the encoder is frozen
+            feats = self.encoder(obs)
+        if feats.shape != (obs.shape[0], 256):
+            raise ValueError(f"the encoder must map (N,4,S,S) to (N,256) features, got {tuple(feats.shape)}")
+        return feats.detach().to(torch.float32).contiguous()
+
     def select_action(self, obs: torch.Tensor, generator: Optional[torch.Generator] = None):
         """obs (N,4,S,S) -> (features, action, logprob) from the OLD policy."""
-        if self.encoder is None:
-            feats = rollout.pooled_features(obs)
-        else:
-            with torch.no_grad():  # PPO.py:154: the encoder is frozen
-                feats = self.encoder(obs)
-            if feats.shape != (obs.shape[0], 256):
-                raise ValueError(f"the encoder must map (N,4,S,S) to (N,256) features, got {tuple(feats.shape)}")
-            feats = feats.detach().to(torch.float32).contiguous()
+        feats = self.features(obs)
         action, logprob = self.policy_old.act(feats, generator)
         return feats, action, logprob
 
