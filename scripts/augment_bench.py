@@ -95,7 +95,7 @@ def main():
     from occlusionenv_amd.encoder import FrozenEncoder
     from occlusionenv_amd.netoptim import PackedAdamW
     from occlusionenv_amd.sepfullnet import TrainableSeparableFullNetwork
-    from tests import bn_train_model as btm
+    from tests import train_model as tm
 
     B, S = args.batch, args.img
     out = dict(device=torch.cuda.get_device_name(0), batch=B, img=S, frames=args.frames, step_ms=STEP_MS, bar_ms=BAR_MS,
@@ -145,7 +145,7 @@ def main():
         out["b_reader_images_per_s"], out["b_reader_images_per_s_all"] = statistics.median(rates), rates
 
         # (d)
-        enc = FrozenEncoder.from_state_dict(btm.state_dict("golden", "separable"), preset="ppo", dilation=2, residual=True)
+        enc = FrozenEncoder.from_state_dict(tm.joint_state_dict("golden"), preset="ppo", dilation=2, residual=True)
         dev_loader = ds.loader(batch_size=B, generator=torch.Generator().manual_seed(3))
         for name, loader in (("device", dev_loader), ("reader", cpu_loader)):
             net = TrainableSeparableFullNetwork.from_encoder(enc)

@@ -1,7 +1,7 @@
 """The ``--batch-stats`` mode of scripts/fullnet_train_bench.py and scripts/sep_fullnet_train_bench.py: one step of the
 pretrainer below its optimizer with BatchNorm in train mode, native (``from_encoder(enc, batch_stats=True)``: ``net(obs)`` ->
 Dice + MSE -> ``backward``; csrc/occ_bn_train.hpp) against (a) the same network as PyTorch-ROCm ops in f32 with torch autograd
-and ``F.batch_norm(training=True)`` (tests/bn_train_model.forward_gated) and (b) the native running-statistics step of the
+and ``F.batch_norm(training=True)`` (tests/train_model.forward_gated) and (b) the native running-statistics step of the
 same build.  One process, interleaved samples, medians compared with the larger min-max spread as the margin.  The
 running-statistics step the parent commit recorded for the shape (``profile``, the script's committed output) is reported next
 to them when it is there.
@@ -42,7 +42,7 @@ def recorded_native_ms(profile, n, img):
 def run_shape(net_class, form, kind, sd32, enc, obs, occl, grad, warmup, iters, calls, profile=None):
     from occlusionenv_amd import _native as nat
     from occlusionenv_amd import segmentation
-    from tests import bn_train_model as bm
+    from tests import train_model as tm
 
     n, img = int(obs.shape[0]), int(obs.shape[2])
 
@@ -63,12 +63,13 @@ def run_shape(net_class, form, kind, sd32, enc, obs, occl, grad, warmup, iters, 
     params = {k: sd[k].clone().requires_grad_() for k, _p in net.named_parameters()}
     sdp = dict(sd)
     sdp.update(params)
-    buffers = {st + leaf: sd[st + leaf].clone() for st in bm.bn_stems(form) for leaf in ("bn.running_mean", "bn.running_var")}
+    model = tm.Net("ppo", form == "separable", enc.dilation, enc.residual, True, True)
+    buffers = {st + leaf: sd[st + leaf].clone() for st in tm.bn_stems(model) for leaf in tm.STATS}
 
     def ref():
         for v in params.values():
             v.grad = None
-        pooled, logit = bm.forward_gated(sdp, buffers, obs, form, enc.dilation, enc.residual)
+        pooled, logit = tm.forward_gated(sdp, obs, model, running=buffers)
         pred = F.linear(pooled, sdp["gradPredictor.weight"], sdp["gradPredictor.bias"])
         loss = dice(torch.sigmoid(logit), occl) + F.mse_loss(pred, grad)
         loss.backward()

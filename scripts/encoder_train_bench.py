@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 from occlusionenv_amd.encoder import FrozenEncoder  # noqa: E402
 from occlusionenv_amd.enctrain import TrainableEncoder  # noqa: E402
 from tests.encoder_model import make_obs, preset_forward  # noqa: E402
-from tests.encoder_train_model import dense_state_dict  # noqa: E402
+from tests.train_model import dense_state_dict  # noqa: E402
 
 
 def sample(fn, calls):

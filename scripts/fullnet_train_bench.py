@@ -1,5 +1,5 @@
 """One step of the pretrainer below its optimizer, native (occlusionenv_amd/fullnet.py: ``net(obs)`` -> Dice + MSE ->
-``backward``; csrc/occ_fullnet_bwd.hpp) against the same expressions of tests/fullnet_train_model.py as PyTorch-ROCm ops in
+``backward``; csrc/occ_fullnet_bwd.hpp) against the same expressions of tests/train_model.py as PyTorch-ROCm ops in
 f32 with torch autograd, and against what reaches the same parameters without the joint backward: one
 ``seghead.SegmentationHead`` step (Dice) plus one ``enctrain.TrainableEncoder`` step (MSE on the head), which runs the encoder
 twice and still misses the join.  One process, interleaved samples.
@@ -35,8 +35,10 @@ from occlusionenv_amd.encoder import FrozenEncoder  # noqa: E402
 from occlusionenv_amd.enctrain import TrainableEncoder  # noqa: E402
 from occlusionenv_amd.fullnet import TrainableFullNetwork  # noqa: E402
 from occlusionenv_amd.seghead import SegmentationHead  # noqa: E402
-from tests import fullnet_train_model as m  # noqa: E402
+from tests import train_model as m  # noqa: E402
 from tests.encoder_model import make_obs  # noqa: E402
+
+NET = m.Net("ppo", False, 1, True, True)  # the dense joint network
 
 
 def sample(fn, calls):
@@ -61,7 +63,7 @@ def torch_step_fn(sd, params, obs, occl, grad):
     def step():
         for v in params.values():
             v.grad = None
-        pooled, logit = m.forward_gated(sdp, obs, "ppo", True)
+        pooled, logit = m.forward_gated(sdp, obs, NET)
         pred = F.linear(pooled, sdp["gradPredictor.weight"], sdp["gradPredictor.bias"])
         loss = dice(torch.sigmoid(logit), occl) + F.mse_loss(pred, grad)
         loss.backward()
@@ -102,7 +104,7 @@ def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only, batch_stats=
     if batch_stats:
         import bn_step_bench
 
-        return bn_step_bench.run_shape(TrainableFullNetwork, "dense", lambda k: m.kind("ppo", k), sd32, enc, obs, occl, grad, warmup,
+        return bn_step_bench.run_shape(TrainableFullNetwork, "dense", lambda k: m.kind(NET, k), sd32, enc, obs, occl, grad, warmup,
                                        iters, calls, os.path.join(ROOT, "profiles", "fullnet_train_bench.json"))
     net = TrainableFullNetwork.from_encoder(enc)
     joint = native_step_fn(net, obs, occl, grad)
@@ -122,7 +124,7 @@ def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only, batch_stats=
     rel = {}
     for k, p in net.named_parameters():
         err = float((p.grad - params[k].grad).abs().max() / params[k].grad.abs().max())
-        rel[m.kind("ppo", k)] = max(rel.get(m.kind("ppo", k), 0.0), err)
+        rel[m.kind(NET, k)] = max(rel.get(m.kind(NET, k), 0.0), err)
     for _ in range(warmup):
         sample(joint, calls), sample(ref, calls), sample(split, calls)
     nms, tms, sms = [], [], []

@@ -29,7 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 from sep_encoder_train_bench import sample  # noqa: E402
-from tests import bn_train_model as btm  # noqa: E402
+from tests import train_model as tm  # noqa: E402
 from tests.encoder_model import make_obs  # noqa: E402
 
 FORMS = {"dense": 1, "separable": 2}  # form -> dilation
@@ -69,7 +69,7 @@ def run_case(form, n, img, warmup, iters, calls):
     from occlusionenv_amd.netoptim import PackedAdamW
     from occlusionenv_amd.sepfullnet import TrainableSeparableFullNetwork
 
-    sd32 = btm.state_dict("golden", form)
+    sd32 = tm.joint_state_dict("golden", form == "separable")
     enc = FrozenEncoder.from_state_dict(sd32, preset="ppo", dilation=FORMS[form], residual=True)
     cls = TrainableFullNetwork if form == "dense" else TrainableSeparableFullNetwork
     base = make_obs(31, 8, img).float()

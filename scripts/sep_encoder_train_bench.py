@@ -5,7 +5,7 @@ tests/encoder_model.py as PyTorch-ROCm ops in f32 with torch autograd, in one pr
     python scripts/sep_encoder_train_bench.py --out profiles/sep_encoder_train_bench.json
 
 Shapes: 128 x 256^2 and 64 x 512^2.  Weights: "ppo" = the separable FullNetwork fixture tests/golden/encoder_golden.npz
-(dilation 2, residual, gradPredictor head) and "predictor" = sep_encoder_train_model.sep_state_dict("predictor", 32, gain 1.25)
+(dilation 2, residual, gradPredictor head) and "predictor" = tests/train_model.sep_state_dict("predictor", 32, gain 1.25)
 (dilation 1, no residual, tanh head).  Both paths compute the gradients of the 86 encoder parameters and of the head; neither
 runs an optimizer.  The torch path runs BatchNorm with its running statistics, as the native one does.  Each sample is
 ``--calls`` steps between two HIP events; after ``--warmup`` samples of each path, ``--iters`` samples alternate between the
@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tests.encoder_model import golden_state_dict, make_obs, preset_forward  # noqa: E402
-from tests.sep_encoder_train_model import sep_state_dict  # noqa: E402
+from tests.train_model import sep_state_dict  # noqa: E402
 
 
 def sample(fn, calls):

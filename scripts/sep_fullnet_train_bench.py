@@ -38,9 +38,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 from sep_encoder_train_bench import kernel_stats, sample  # noqa: E402
-from tests import sep_fullnet_train_model as m  # noqa: E402
+from tests import train_model as m  # noqa: E402
 from tests.encoder_model import make_obs  # noqa: E402
 from tests.segmenter_model import full_forward  # noqa: E402
+
+NET = m.Net("ppo", True, 2, True, True)  # the separable joint network (the parameter kinds do not depend on the dilation)
 
 
 def dice(p, t):
@@ -104,8 +106,8 @@ def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only, batch_stats=
     if batch_stats:
         import bn_step_bench
 
-        return bn_step_bench.run_shape(TrainableSeparableFullNetwork, "separable", m.kind, sd32, enc, obs, occl, grad, warmup, iters,
-                                       calls, os.path.join(ROOT, "profiles", "sep_fullnet_train_bench.json"))
+        return bn_step_bench.run_shape(TrainableSeparableFullNetwork, "separable", lambda k: m.kind(NET, k), sd32, enc, obs, occl, grad,
+                                       warmup, iters, calls, os.path.join(ROOT, "profiles", "sep_fullnet_train_bench.json"))
     net = TrainableSeparableFullNetwork.from_encoder(enc)
     joint = native_step_fn(net, obs, occl, grad)
     wsb, scb = C.c_size_t(), C.c_size_t()
@@ -127,7 +129,7 @@ def run_shape(sd32, enc, n, img, warmup, iters, calls, native_only, batch_stats=
     rel = {}
     for k, p in net.named_parameters():
         err = float((p.grad - params[k].grad).abs().max() / params[k].grad.abs().max())
-        rel[m.kind(k)] = max(rel.get(m.kind(k), 0.0), err)
+        rel[m.kind(NET, k)] = max(rel.get(m.kind(NET, k), 0.0), err)
     for _ in range(warmup):
         sample(joint, calls), sample(ref, calls), sample(split, calls)
     nms, tms, sms = [], [], []

@@ -18,7 +18,7 @@ import torch
 
 from occlusionenv_amd import _native as nat
 from tests import adamw_model as am
-from tests import bn_train_model as btm
+from tests import train_model as tm
 
 P16 = C.c_void_p(4096)  # never dereferenced: every call below is rejected before a launch
 EPS32 = float(np.finfo(np.float32).eps)
@@ -44,7 +44,7 @@ def _random_grads(model, seed):
 
 
 def _follows_torch(form, mutate=None):
-    sd = btm.state_dict("golden", form)
+    sd = tm.joint_state_dict("golden", form == "separable")
     model = am.PackedModel(form, sd, dtype=np.float32)
     steps = _random_grads(model, 7)
     per_key = [am.grads_per_key(model, packed, head, 0) for packed, head in steps]
@@ -78,7 +78,7 @@ def test_the_check_catches_a_broken_model(mutate):
 
 
 def test_the_f64_model_and_its_f32_form_agree_to_f32_rounding():
-    sd = btm.state_dict("golden", "dense")
+    sd = tm.joint_state_dict("golden", separable=False)
     m64, m32 = am.PackedModel("dense", sd), am.PackedModel("dense", sd, dtype=np.float32)
     for (packed, head), lr in zip(_random_grads(m64, 11), LRS):
         m64.step(packed, head, lr, WEIGHT_DECAY, 1)

@@ -1,6 +1,7 @@
 """Host-side checks of the joint training step with batch-statistics BatchNorm (csrc/occ_bn_train.hpp,
 ``from_encoder(enc, batch_stats=True)``): the A / B / C form of the BatchNorm backward is the gradient, the running-average
-rule of ``nettrain`` is nn.BatchNorm2d's, the workspace query is the documented layout, and every case whose gradients the GPU
+rule of ``nettrain`` is nn.BatchNorm2d's, the workspace query is the documented layout, the statistics the train-mode model
+records are those of its relu outputs, and every case whose gradients the GPU
 test judges is well conditioned: PyTorch's own f32 run of it agrees with the f64 model within 1e-4 for every tensor.  The
 argument contract of the three entry points is checked from the table of tests/train_abi.py by
 tests/test_train_abi_host.py.  No GPU."""
@@ -11,11 +12,15 @@ import torch
 
 from occlusionenv_amd import _native as nat
 from occlusionenv_amd import nettrain
-from tests import bn_train_model as m
-from tests import fullnet_train_model as ftm
+from tests import train_layout as tl
+from tests import train_model as m
 
 SYMBOLS = ("occ_fullnet_bn_train_workspace_query", "occ_fullnet_bn_train_forward", "occ_fullnet_bn_backward")
 FORMS = {"dense": dict(dilation=1, separable=0), "separable": dict(dilation=2, separable=1)}
+
+
+def _net(form, residual=True, batch_stats=True):
+    return m.Net("ppo", form == "separable", FORMS[form]["dilation"], residual, True, batch_stats)
 
 
 def _cfg(img=64, dilation=2, residual=1, separable=1):
@@ -54,8 +59,8 @@ def test_running_average_rule_is_batchnorm2d():
     """nettrain._update_running_stats, two steps, against nn.BatchNorm2d in f64 on the same activations."""
     n, img = 2, 32
     stems = [f"l{i}." for i in range(21)]
-    shapes = m.layer_shapes(img)
-    assert [(c, s * s) for c, s in shapes] == nettrain.bn_layer_shapes(img) and sum(c for c, _s in shapes) == m.CHANNELS
+    shapes = tl.layer_shapes(img)
+    assert [(c, s * s) for c, s in shapes] == nettrain.bn_layer_shapes(img) and sum(c for c, _s in shapes) == tl.CHANNELS
     gen = torch.Generator().manual_seed(9)
     bns = [torch.nn.BatchNorm2d(c).double().train() for c, _s in shapes]
     buffers = {}
@@ -92,14 +97,14 @@ def test_workspace_query_is_the_documented_layout(form):
         rc, ws_b, sc_b = _query(lib, SYMBOLS[0], img, n, **FORMS[form])
         rcj, ws_j, sc_j = _query(lib, joint, img, n, **FORMS[form])
         assert rc == 0 and rcj == 0
-        assert ws_j == ftm.ws_bytes(img, n) and sc_b == sc_j == m.scratch_bytes(form, img, n)
-        assert ws_b == m.ws_bytes(img, n) and ws_b - ws_j == m.extra_ws_bytes(img, n) > 0, (img, n)
+        assert ws_j == tl.ws_bytes(_net(form, batch_stats=False), img, n) and sc_b == sc_j == tl.scratch_bytes(_net(form), img, n)
+        assert ws_b == tl.ws_bytes(_net(form), img, n) and ws_b - ws_j == tl.extra_ws_bytes(img, n) > 0, (img, n)
         assert ws_b % 256 == 0
     # coef 24 bytes per channel, abc 3 x 256 floats, the partials of the largest layer: the last down (256 channels, one
     # chunk) until level 0 (8 channels) has more than 32 chunks
-    assert m.extra_ws_bytes(256, 8) == 29952 + 3072 + 256 * 8 * 1 * 2 * 8
-    assert m.extra_ws_bytes(1024, 2) == 29952 + 3072 + 8 * 2 * 256 * 2 * 8
-    assert m.extra_ws_bytes(32, 2) == 29952 + 3072 + 256 * 2 * 1 * 2 * 8
+    assert tl.extra_ws_bytes(256, 8) == 29952 + 3072 + 256 * 8 * 1 * 2 * 8
+    assert tl.extra_ws_bytes(1024, 2) == 29952 + 3072 + 8 * 2 * 256 * 2 * 8
+    assert tl.extra_ws_bytes(32, 2) == 29952 + 3072 + 256 * 2 * 1 * 2 * 8
 
 
 def test_python_keyword_and_modes_need_no_gpu():
@@ -118,16 +123,40 @@ def test_python_keyword_and_modes_need_no_gpu():
     assert nettrain.TrainableNet.BN_SYMBOLS is None and nettrain.BN_MOMENTUM == m.MOMENTUM
 
 
-@pytest.mark.parametrize("case", m.GRAD_CASES, ids=m.IDS[:len(m.GRAD_CASES)])
+def test_recorded_statistics_are_those_of_the_relu_outputs():
+    """With ``running`` a copy of the checkpoint's statistics, the train-mode forward's ``stats`` are the mean and the biased
+    variance of relu(u) for the u's it hands out, layer by layer, and ``running`` moves by momentum 0.1 towards them (the
+    variance unbiased), for one dense and one separable net at 2 x 32^2: 32 is the smallest S the decoder takes, N = 2 the
+    smallest batch with N (S/32)^2 >= 2 values per channel at the deepest layer."""
+    for form in sorted(FORMS):
+        net = _net(form)
+        host = m.HostModel(m.joint_state_dict("golden", net.separable), net, m.case_obs((32, 2)))
+        before = {k: v.clone() for k, v in host.running.items()}
+        us = []
+        with torch.no_grad():
+            host.forward(None, us)
+        assert len(us) == len(host.stats) == 21 and host.packed_stats().shape == (2 * tl.CHANNELS,)
+        assert [(u.shape[1], u.shape[-1]) for u in us] == tl.layer_shapes(32)
+        for stem, u, (mean, var) in zip(m.bn_stems(net), us, host.stats):
+            r = torch.relu(u)
+            cnt = r.numel() // r.shape[1]
+            assert torch.equal(mean, r.mean(dim=(0, 2, 3))) and torch.equal(var, r.var(dim=(0, 2, 3), unbiased=False)), stem
+            for leaf, want in (("bn.running_mean", mean), ("bn.running_var", var * cnt / (cnt - 1))):
+                moved = (1 - m.MOMENTUM) * before[stem + leaf] + m.MOMENTUM * want
+                assert torch.allclose(host.running[stem + leaf], moved, rtol=1e-12, atol=1e-14), stem + leaf
+        assert all(torch.equal(host.sd[k], v) for k, v in before.items())  # the checkpoint's own statistics stay
+
+
+@pytest.mark.parametrize("case", m.BN_GRAD_CASES, ids=m.BN_IDS[:len(m.BN_GRAD_CASES)])
 def test_conditioning_of_the_judged_cases(case):
     """Every tensor of every judged case: PyTorch's f32 CPU autograd run is within 1e-4 of the plain f64 model, so the
     bar max(1e-4, 4 e32) never exceeds 4e-4.  Measured worst e32: 1.6e-5 (golden separable S=64 N=3), 1.5e-5 (dense
     S=64 N=4), 1.7e-5 (seeded separable S=96 N=2); worst band share 0.11 %, 0.19 %, 0.34 %."""
-    e = m.e32(case)
-    assert len(e) == len(m.enc_keys(case[1])) + 22
+    e, net = m.e32(case), m.bn_net(case)
+    assert len(e) == len(m.enc_keys(net)) + 22
     worst = {}
     for k, v in e.items():
-        worst[m.kind(k)] = max(worst.get(m.kind(k), 0.0), v)
+        worst[m.kind(net, k)] = max(worst.get(m.kind(net, k), 0.0), v)
     print(case, {k: f"{v:.3g}" for k, v in sorted(worst.items())})
     assert all(v <= m.E32_CAP for v in e.values()), {k: v for k, v in e.items() if v > m.E32_CAP}
     assert all(m.TOL <= m.bar(case, k) <= m.MARGIN * m.E32_CAP for k in e)

@@ -10,7 +10,10 @@ import torch.nn.functional as F
 
 from occlusionenv_amd import _native as nat
 from tests import encoder_model
-from tests import encoder_train_model as m
+from tests import train_layout as tl
+from tests import train_model as m
+
+DENSE = m.Net("ppo", False, 1, True)  # the scratch does not depend on the preset or the residual
 
 
 def _cfg(img=64, dilation=1, residual=0, separable=0):
@@ -37,7 +40,7 @@ def test_workspace_query_grows_with_n_and_covers_the_kept_tensors():
             rc, ws_b, _sc = _query(lib, img, n)
             assert rc == 0 and ws_b % 256 == 0
             # the kept tensors and three gradient buffers of (n, 8, S, S)
-            assert ws_b >= m.kept_bytes(img, n) + 3 * 4 * n * 8 * img * img
+            assert ws_b >= tl.kept_bytes(img, n) + 3 * 4 * n * 8 * img * img
     # the size the header states: 30.31 MiB per env at 256^2
     assert abs(_query(lib, 256, 128)[1] / 128 / 2 ** 20 - 30.31) < 0.01
 
@@ -49,18 +52,18 @@ def test_pack_round_trip_against_pack_state_dict():
 
     buf = torch.randn(packed_floats(False), generator=torch.Generator().manual_seed(1))
     layers = unpack_encoder_buffer(buf)
-    assert [tuple(l[0].shape) for l in layers] == [(co, ci, 3, 3) for _s, ci, co, _st in m.layers()]
+    assert [tuple(l[0].shape) for l in layers] == [(co, ci, 3, 3) for _s, ci, co, *_ in m.layers(False)]
     assert torch.equal(pack_encoder_buffer(layers), buf)
     w1 = layers[1][0]  # the layout: w[ci][ky * 3 + kx][co]
     off = 9 * 4 * 8 + 3 * 8
     assert float(w1[5, 3, 2, 1]) == float(buf[off + (3 * 9 + 2 * 3 + 1) * 8 + 5])
     for preset in ("predictor", "ppo"):
         sd = {k: v.float() for k, v in m.dense_state_dict(preset, 11).items()}
-        prefix = m.PRESETS[preset][0]
+        prefix = m.preset_keys(preset)["prefix"]
         separable, want, _offsets = pack_state_dict(sd, prefix)
         assert not separable
         folded = []
-        for stem, _ci, _co, _st in m.layers():
+        for stem, *_ in m.layers(False):
             st = prefix + stem
             scale, shift, _ = fold_bn_vectors(sd[st + "bn.weight"], sd[st + "bn.bias"], sd[st + "bn.running_mean"], sd[st + "bn.running_var"])
             folded.append((sd[st + "conv.weight"], sd[st + "conv.bias"], scale, shift))
@@ -96,8 +99,9 @@ def test_gated_model_with_its_own_gates_is_plain_autograd():
         sd = m.dense_state_dict(preset, 21)
         obs = encoder_model.make_obs(22, 2, 40)
         up = torch.randn(2, 256, generator=torch.Generator().manual_seed(23), dtype=torch.float64)
-        prefix, _hd, _tanh, residual, _gain = m.PRESETS[preset]
-        host = m.HostModel(sd, preset, obs)
+        prefix, residual = m.preset_keys(preset)["prefix"], m.preset_keys(preset)["residual"]
+        net = m.Net(preset, False, 1, residual)
+        host = m.HostModel(sd, net, obs)
         us = []
         f_plain = host.feats(None, us)
         assert len(us) == 16 and [u.shape[-1] for u in us] == [40, 40, 40, 20, 20, 20, 10, 10, 10, 5, 5, 5, 3, 3, 3, 2]
@@ -106,7 +110,7 @@ def test_gated_model_with_its_own_gates_is_plain_autograd():
         f_ref = encoder_model.encode(ref, obs, prefix, False, 1, residual)
         assert torch.equal(f_plain.detach(), f_ref.detach())
         (f_ref * up).sum().backward()
-        want = {k: ref[k].grad for k in m.param_keys(preset)}
+        want = {k: ref[k].grad for k in m.param_keys(net)}
         plain = host.grads((f_plain * up).sum())
         gated = host.grads((host.feats([(u > 0).double() for u in us]) * up).sum())
         assert len(want) == 64
@@ -121,11 +125,11 @@ def test_split_plan_is_what_the_query_sizes_scratch_for():
         for n in (1, 2, 3, 64, 65, 128, 129):
             rc, ws_b, sc_b = _query(lib, img, n, residual=1)
             assert rc == 0
-            assert sc_b == m.scratch_bytes(img, n), (img, n)
-            for p in m.dw_plans(img, n):
-                assert p["slices"] * p["grid_y"] <= m.DW_BLOCKS
+            assert sc_b == tl.scratch_bytes(DENSE, img, n), (img, n)
+            for p in tl.dw_plans(img, n):
+                assert p["slices"] * p["grid_y"] <= tl.DW_BLOCKS
                 assert (p["slices"] - 1) * p["tps"] < p["total_tiles"] <= p["slices"] * p["tps"]
-    col = lambda img, n, key: [p[key] for p in m.dw_plans(img, n)]  # noqa: E731
+    col = lambda img, n, key: [p[key] for p in tl.dw_plans(img, n)]  # noqa: E731
     assert col(40, 3, "ho") == [40, 40, 40, 20, 20, 20, 10, 10, 10, 5, 5, 5, 3, 3, 3, 2]
     assert col(40, 3, "T") == [8] * 10 + [4] * 6
     assert set(col(32, 2, "tps")) == set(col(40, 3, "tps")) == set(col(96, 2, "tps")) == {1}  # one tile per block there
@@ -135,9 +139,9 @@ def test_split_plan_is_what_the_query_sizes_scratch_for():
 
 def test_split_case_reaches_the_tile_loop():
     """What the split case of tests/test_gpu_encoder_train.py has to reach, on the model alone."""
-    preset, img, n = m.SPLIT_CASE
+    preset, img, n = m.ENCODER_SPLIT_CASE
     assert (preset, img, n) == ("ppo", 32, 129)
-    plans = m.dw_plans(img, n)
+    plans = tl.dw_plans(img, n)
     assert [p["tps"] for p in plans] == [5, 5, 5, 2, 2, 2, 1, 1, 1, 1, 1, 1, 2, 3, 3, 5]
     # the three deepest layers (one 4-pixel tile per env): every slice of several tiles crosses env boundaries
     assert all(p["T"] == 4 and p["tiles_env"] == 1 and p["straddles"] for p in plans[12:])

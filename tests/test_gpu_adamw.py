@@ -4,7 +4,7 @@ native_optimizer=True)``, ``harness.pretrain``) against tests/adamw_model.py.
 The network's parameter count is fixed, so the smallest observations do: N = 2, S = 32 under running statistics, N = 1,
 S = 64 under batch statistics (N (S / 32)^2 = 4 values per channel in the deepest layer).  Every case runs the dense network
 at dilation 1 and the separable one at dilation 2, both with the residual, on the "golden" checkpoints of
-tests/bn_train_model.py.
+tests/train_model.py (joint_state_dict).
 
 Bars.
   * The packed output against torch's own fold and ``Part.pack`` of the synced parameters: bitwise.  It is a permutation
@@ -31,7 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import adamw_model as am
-from tests import bn_train_model as btm
+from tests import train_model as tm
 from tests.encoder_model import make_obs
 
 pytestmark = pytest.mark.gpu
@@ -77,7 +77,7 @@ def encs():
 
     out = {}
     for form, d, res in FORMS:
-        sd32 = btm.state_dict("golden", form)
+        sd32 = tm.joint_state_dict("golden", form == "separable")
         out[form] = (sd32, FrozenEncoder.from_state_dict(sd32, preset="ppo", dilation=d, residual=bool(res)))
     return out
 

@@ -290,12 +290,12 @@ def test_pretrain_epoch_runs_from_a_loader_batch(dataset):
     from occlusionenv_amd import harness
     from occlusionenv_amd.devdata import DeviceDataset
     from occlusionenv_amd.encoder import FrozenEncoder
-    from tests import bn_train_model as btm
+    from tests import train_model as tm
 
     store, _ = dataset
     ds = DeviceDataset.from_arrays(*(a[:2] for a in store), "cuda", split="train")
     assert torch.allclose((ds.grad ** 2).sum(1), torch.ones(2, device="cuda"))  # (sin, cos)
-    enc = FrozenEncoder.from_state_dict(btm.state_dict("golden", "separable"), preset="ppo", dilation=2, residual=True)
+    enc = FrozenEncoder.from_state_dict(tm.joint_state_dict("golden"), preset="ppo", dilation=2, residual=True)
     res = harness.pretrain_epoch(enc, ds.loader(batch_size=2, generator=torch.Generator().manual_seed(41)), native_optimizer=True)
     assert res["batches"] == 1 and res["pixels"] == 2 * 32 * 32 and np.isfinite(res["loss"])
 
@@ -306,12 +306,12 @@ def test_pretrain_runs_an_epoch_from_two_loaders(dataset):
     from occlusionenv_amd import harness
     from occlusionenv_amd.devdata import DeviceDataset
     from occlusionenv_amd.encoder import FrozenEncoder
-    from tests import bn_train_model as btm
+    from tests import train_model as tm
 
     store, _ = dataset
     train = DeviceDataset.from_arrays(*(a[:4] for a in store), "cuda", split="train")
     val = DeviceDataset.from_arrays(*(a[4:7] for a in store), "cuda", split="val")
-    enc = FrozenEncoder.from_state_dict(btm.state_dict("golden", "separable"), preset="ppo", dilation=2, residual=True)
+    enc = FrozenEncoder.from_state_dict(tm.joint_state_dict("golden"), preset="ppo", dilation=2, residual=True)
     tl, vl = train.loader(batch_size=2, generator=torch.Generator().manual_seed(42)), val.loader(batch_size=3)
     assert tl.train and not vl.train
     out = harness.pretrain(enc, tl, vl, epochs=1)

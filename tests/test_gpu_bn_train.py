@@ -1,13 +1,13 @@
 """GPU tests of the joint training step with batch-statistics BatchNorm (csrc/occ_bn_train.hpp,
-``from_encoder(enc, batch_stats=True)``, ``harness.pretrain_epoch(.., batch_stats=True)``) against tests/bn_train_model.py: the
-network in train mode in f64 on the CPU with torch autograd.
+``from_encoder(enc, batch_stats=True)``, ``harness.pretrain_epoch(.., batch_stats=True)``) against tests/train_model.py (a joint
+``Net`` with ``batch_stats``): the network in train mode in f64 on the CPU with torch autograd.
 
 Cases (weights, form, dilation, residual, S, N), weights rounded to f32 and used as exactly those values by the model:
 golden separable d2 res S=64 N=3; golden dense d1 res S=64 N=4; seeded separable d2 no residual S=96 N=2 (M = 18 at the
 deepest layer, whose plane is 3 x 3; level 0 has 2.25 chunks; no plane below level 0 is a multiple of 4 pixels, so the
 one-pixel-per-lane kernels run next to the 16-byte ones).  Golden separable S=32 N=2 (M = 2 at the deepest layer) gets the
 forward and determinism checks only: PyTorch's own f32 run misses the f64 model by 6e-4 there.  Two cases take their
-observation from another seed than the other training tests' (bn_train_model.OBS_SEEDS says which and why: conditioning and
+observation from another seed than the other training tests' (train_model.OBS_SEEDS says which and why: conditioning and
 the gate band, both settled on the CPU).
 
 Bars.  Forward: bn_stats, feats and prob within 1e-4 max(1, max |want|) per tensor; kept relu outputs within
@@ -35,7 +35,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests import bn_train_model as m
+from tests import train_layout as tl
+from tests import train_model as m
 from tests.train_utils import GUARD
 from tests.train_utils import dice64 as _dice64
 from tests.train_utils import grads as _grads
@@ -44,8 +45,8 @@ from tests.train_utils import guarded as _guarded
 pytestmark = pytest.mark.gpu
 
 TOL = m.TOL
-CASES, IDS = m.CASES, m.IDS
-GRAD_CASES, GRAD_IDS = m.GRAD_CASES, m.IDS[:len(m.GRAD_CASES)]
+CASES, IDS = m.BN_CASES, m.BN_IDS
+GRAD_CASES, GRAD_IDS = m.BN_GRAD_CASES, m.BN_IDS[:len(m.BN_GRAD_CASES)]
 WORST = {}  # measured worst relative error per parameter kind (printed with -s)
 
 
@@ -63,7 +64,7 @@ def nets():
 
     out = {}
     for weights, form, d, res in sorted({c[:4] for c in CASES}):
-        sd32 = m.state_dict(weights, form)
+        sd32 = m.joint_state_dict(weights, form == "separable")
         enc = FrozenEncoder.from_state_dict(sd32, preset="ppo", dilation=d, residual=bool(res))
         assert enc.separable == (form == "separable") and enc.dilation == d and enc.has_decoder
         out[weights, form, d, res] = (sd32, enc)
@@ -88,12 +89,12 @@ def runs(nets):
             gf, gp = m.upstream(img, n)
             net.zero_grad()
             torch.autograd.backward([feats, prob], [gf.cuda(), gp.cuda()])
-            kept = [m.kept_relu(net, i).cpu().clone() for i in range(21)]
+            kept = [tl.kept_relu(net, i).cpu().clone() for i in range(21)]
             cache[case] = dict(enc=enc, net=net, obs=obs, feats=feats.detach().cpu(), prob=prob.detach().cpu(), gf=gf, gp=gp,
                                kept=kept, gates=[(k > 0).double() for k in kept], stats=net.bn_stats.cpu().clone(),
                                grads={k: v.cpu() for k, v in _grads(net).items()},
                                buffers={k: v.cpu().clone() for k, v in net.named_buffers() if "running_" in k},
-                               host=m.HostModel(sd32, form, d, res, obs.cpu()))
+                               host=m.HostModel(sd32, m.bn_net(case), obs.cpu()))
         return cache[case]
 
     return get
@@ -106,12 +107,12 @@ def _close(got, want, what):
 
 
 def _check_grads(what, case, got, want):
-    e32 = m.e32(case)
+    e32, net = m.e32(case), m.bn_net(case)
     for k, w in want.items():
         scale = float(w.abs().max())
         assert scale > 0.0, (what, k, "the oracle's gradient is all zero")
         err = float((got[k].double().cpu() - w).abs().max()) / scale
-        WORST[m.kind(k)] = max(WORST.get(m.kind(k), 0.0), err)
+        WORST[m.kind(net, k)] = max(WORST.get(m.kind(net, k), 0.0), err)
         print(f"{what} {k}: max|want| {scale:.3g}, relative error {err:.3g}, e32 {e32.get(k, 0.0):.3g}")
     for k, w in want.items():
         assert got[k].shape == w.shape and got[k].dtype == torch.float32
@@ -126,7 +127,7 @@ def test_forward_against_the_f64_model(runs, case):
     _w, _form, _d, _res, img, n = case
     host = m.plain_f64(case)[0]
     pooled, prob = host.first
-    assert r["stats"].shape == (2 * m.CHANNELS,) and r["feats"].shape == (n, 256) and r["prob"].shape == (n, 1, img, img)
+    assert r["stats"].shape == (2 * tl.CHANNELS,) and r["feats"].shape == (n, 256) and r["prob"].shape == (n, 1, img, img)
     _close(r["stats"], host.packed_stats(), "bn_stats")
     _close(r["feats"], pooled, "feats")
     _close(r["prob"], prob, "prob")
@@ -160,7 +161,7 @@ def test_gradients_against_f64_autograd(runs, case):
     host = r["host"]
     pooled, prob, _pred = host.forward(r["gates"])
     want = host.grads((pooled * r["gf"].double()).sum() + (prob * r["gp"].double()).sum())
-    assert len(want) == len(m.enc_keys(case[1])) + 22 and set(want) <= set(r["grads"])
+    assert len(want) == len(m.enc_keys(m.bn_net(case))) + 22 and set(want) <= set(r["grads"])
     _check_grads(str(case), case, r["grads"], want)
 
 
@@ -180,11 +181,11 @@ def test_gradients_through_the_real_losses(runs):
     loss = segmentation.binary_dice_loss(segm, occl.cuda()) + F.mse_loss(pred, grad.cuda())
     loss.backward()
     got = _grads(net)
-    gates = [(m.kept_relu(net, i).cpu() > 0).double() for i in range(21)]
+    gates = [(tl.kept_relu(net, i).cpu() > 0).double() for i in range(21)]
     _p64, prob64, pred64 = host.forward(gates)
     loss64 = _dice64(prob64, occl) + F.mse_loss(pred64, grad.double())
     want = host.grads(loss64, head=True)
-    assert len(want) == len(m.enc_keys(case[1])) + 22 + 2
+    assert len(want) == len(m.enc_keys(m.bn_net(case))) + 22 + 2
     assert abs(float(loss.detach()) - float(loss64.detach())) <= TOL * max(1.0, abs(float(loss64.detach())))
     _check_grads(f"dice+mse {case}", case, got, want)
 
@@ -196,7 +197,7 @@ def test_running_buffers_and_eval_mode(nets, runs, case):
     weights, form, d, res, img, n = case
     r = runs(case)
     sd32, enc = nets[case[:4]]
-    host = m.HostModel(sd32, form, d, res, r["obs"].cpu())
+    host = m.HostModel(sd32, m.bn_net(case), r["obs"].cpu())
     with torch.no_grad():
         host.forward()
     for k, want in host.running.items():
@@ -257,8 +258,8 @@ def test_nothing_outside_the_reported_sizes(runs, case):
     wsb, scb = C.c_size_t(), C.c_size_t()
     nat.check(lib.occ_fullnet_bn_train_workspace_query(C.byref(cfg), n, C.byref(wsb), C.byref(scb)), "query")
     sizes = dict(ws=int(wsb.value), scratch=int(scb.value), grad_enc=4 * packed_floats(form == "separable"),
-                 grad_dec=4 * decoder_packed_floats(), prob=4 * n * img * img, feats=4 * n * FEATURES, stats=8 * m.CHANNELS)
-    assert sizes["ws"] == m.ws_bytes(img, n) and sizes["scratch"] == m.scratch_bytes(form, img, n)
+                 grad_dec=4 * decoder_packed_floats(), prob=4 * n * img * img, feats=4 * n * FEATURES, stats=8 * tl.CHANNELS)
+    assert sizes["ws"] == tl.ws_bytes(m.bn_net(case), img, n) and sizes["scratch"] == tl.scratch_bytes(m.bn_net(case), img, n)
     bufs = {k: _guarded(b) for k, b in sizes.items()}
     mid = {k: whole[lo:lo + sizes[k]] for k, (whole, lo) in bufs.items()}
     # the packed buffers of the train-mode step: gamma / beta unfolded in the scale / shift slots
@@ -287,7 +288,7 @@ def test_nothing_outside_the_reported_sizes(runs, case):
         for k, t in zip(part.tail, tail):
             assert torch.equal(t, r["grads"][k]), k
             at += 1
-    assert at == len(m.enc_keys(form)) + 22
+    assert at == len(m.enc_keys(m.bn_net(case))) + 22
     for k, (whole, lo) in bufs.items():
         assert lo >= GUARD and whole.numel() - (lo + sizes[k]) >= GUARD
         assert bool((whole[:lo] == 0xA5).all()), f"bytes in front of {k} were written"
@@ -334,7 +335,7 @@ def test_pretrain_epoch_with_batch_stats(nets):
     res_ = harness.pretrain_epoch(enc, batches, batch_stats=True)
     net = res_["net"]
     assert isinstance(net, _net_class(form)) and net.batch_stats and res_["batches"] == 2
-    host = m.HostModel(sd32, form, d, res, batches[0][0])
+    host = m.HostModel(sd32, m.Net("ppo", True, d, bool(res), True, True), batches[0][0])
     opt = torch.optim.AdamW(list(host.params.values()), lr=1e-3, weight_decay=1e-5)
     rows = []
     for obs, occl, grad, _ in batches:

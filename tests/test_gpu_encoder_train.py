@@ -1,8 +1,9 @@
 """GPU tests of the native encoder backward (csrc/occ_encoder_bwd.hpp, occlusionenv_amd/enctrain.py, harness.train_predictor)
-against tests/encoder_train_model.py in f64 on the CPU, torch autograd supplying the gradients.  The bodies this module
-shares with tests/test_gpu_sep_encoder_train.py are in tests/train_gpu_suite.py; FORM below is what they are given.
+against tests/train_model.py (the dense encoder-only ``Net``) in f64 on the CPU, torch autograd supplying the gradients.  The
+bodies this module shares with tests/test_gpu_sep_encoder_train.py are in tests/train_gpu_suite.py; FORM below is what they
+are given.
 
-Weights: encoder_train_model.dense_state_dict rounded to f32 (what a checkpoint on disk holds), used as exactly those
+Weights: train_model.dense_state_dict rounded to f32 (what a checkpoint on disk holds), used as exactly those
 values in f64 by the host model; presets "predictor" (no residual, tanh head) and a dense "ppo"-keyed encoder (dilation 1,
 residual).  Inputs: encoder_model.make_obs; the upstream grad_feats is randn.
 
@@ -34,21 +35,20 @@ import pytest
 import torch
 
 from occlusionenv_amd.enctrain import TrainableEncoder
-from tests import encoder_train_model as m
 from tests import train_gpu_suite as suite
+from tests import train_model as m
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
-SPLIT = m.SPLIT_CASE
+SPLIT = m.ENCODER_SPLIT_CASE
 CASES = [(p, s, n) for s, n in ((32, 2), (40, 3), (96, 2)) for p in ("predictor", "ppo")] + [SPLIT]
 IDS = [f"{p}-S{s}-N{n}" for p, s, n in CASES]
 WORST = {}  # measured worst relative error per tensor kind (printed with -s)
 FORM = suite.Form(
-    model=m, net=TrainableEncoder, joint=False, separable=False,
+    net=TrainableEncoder, model=lambda case: m.Net(case[0], False, 1, case[0] == "ppo"),
     symbols=("occ_encoder_train_workspace_query", "occ_encoder_train_forward", "occ_encoder_backward"),
-    host=lambda entry, case, obs64: m.HostModel(entry[1], case[0], obs64),
-    label=lambda case: "{} S={} N={}".format(*case), kind=lambda case, k: ".".join(k.rsplit(".", 2)[-2:]),
+    label=lambda case: "{} S={} N={}".format(*case),
     n_params=64, seed=7000, steps=40, tol=TOL, finite_losses=True)
 
 
@@ -59,9 +59,8 @@ def nets():
     out = {}
     for preset in ("predictor", "ppo"):
         sd32 = {k: v.float() for k, v in m.dense_state_dict(preset, 31 if preset == "ppo" else 32).items()}
-        sd64 = {k: v.double() for k, v in sd32.items()}
         kw = dict(dilation=1, residual=True) if preset == "ppo" else {}
-        out[preset] = (sd32, sd64, FrozenEncoder.from_state_dict(sd32, preset=preset, **kw))
+        out[preset] = (sd32, FrozenEncoder.from_state_dict(sd32, preset=preset, **kw))
     return out
 
 
@@ -162,11 +161,11 @@ def test_train_predictor_harness(nets):
     np.random.seed(78)
     torch.manual_seed(78)
     venv = SimpleVecEnv([lambda: OcclusionEnv(ds, img_size=64) for _ in range(4)])
-    net = TrainableEncoder.from_encoder(nets["predictor"][2])
+    net = TrainableEncoder.from_encoder(nets["predictor"][1])
     before = {k: v.detach().clone() for k, v in net.named_parameters()}
     res = harness.train_predictor(venv, net, 4)
     assert res["net"] is net and res["steps"] + res["skipped"] == 4 and res["steps"] >= 1
     assert len(res["losses"]) == res["steps"] and all(np.isfinite(v) for v in res["losses"])
     assert all(not torch.equal(v, before[k]) for k, v in net.named_parameters())
-    res = harness.train_predictor(venv, nets["predictor"][2], 1)  # from an encoder: a net is made
+    res = harness.train_predictor(venv, nets["predictor"][1], 1)  # from an encoder: a net is made
     assert isinstance(res["net"], TrainableEncoder)

@@ -1,8 +1,8 @@
 """GPU tests of the native joint backward (csrc/occ_fullnet_bwd.hpp, occlusionenv_amd/fullnet.py, harness.pretrain_epoch)
-against tests/fullnet_train_model.py in f64 on the CPU with torch autograd.  The bodies this module shares with
-tests/test_gpu_sep_fullnet_train.py are in tests/train_gpu_suite.py; FORM below is what they are given.
+against tests/train_model.py (the dense joint ``Net``) in f64 on the CPU with torch autograd.  The bodies this module shares
+with tests/test_gpu_sep_fullnet_train.py are in tests/train_gpu_suite.py; FORM below is what they are given.
 
-Weights: fullnet_train_model.state_dict rounded to f32 (what a checkpoint on disk holds), used as exactly those values in
+Weights: train_model.state_dict rounded to f32 (what a checkpoint on disk holds), used as exactly those values in
 f64 by the host model.  Inputs: encoder_model.make_obs.  Upstream: a randn grad_feats and a randn grad_prob together.
 
 Shapes: S=32 N=2 (the deepest decoder plane is 1 x 1: the new input gradient of the deepest level), S=64 N=3, S=96 N=2 (sides
@@ -21,23 +21,20 @@ import torch
 from occlusionenv_amd.enctrain import TrainableEncoder
 from occlusionenv_amd.fullnet import TrainableFullNetwork
 from tests import decoder_split_model as dsm
-from tests import encoder_train_model as etm
-from tests import fullnet_train_model as m
 from tests import train_gpu_suite as suite
+from tests import train_layout as tl
+from tests import train_model as m
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
-CASES = m.GRAD_CASES + m.SPLIT_CASES
+CASES = m.JOINT_GRAD_CASES + m.JOINT_SPLIT_CASES
 IDS = [f"{p}-res{r}-S{s}-N{n}" for p, r, s, n in CASES]
 WORST = {}  # measured worst relative error per parameter kind (printed with -s)
 FORM = suite.Form(
-    model=m, net=TrainableFullNetwork, encoder_net=TrainableEncoder, joint=True, separable=False,
+    net=TrainableFullNetwork, model=lambda case: m.Net(case[0], False, 1, bool(case[1]), True), encoder_net=TrainableEncoder,
     symbols=("occ_fullnet_train_workspace_query", "occ_fullnet_train_forward", "occ_fullnet_backward"),
-    host=lambda entry, case, obs64: m.HostModel(entry[1], case[0], case[1], obs64),
-    label=lambda case: "{} res{} S={} N={}".format(*case), kind=lambda case, k: m.kind(case[0], k),
-    enc_keys=lambda case: m.enc_keys(case[0]), dec_keys=lambda case: m.dec_keys(case[0]),
-    n_params=64 + 22, seed=9000, steps=40, tol=TOL)
+    label=lambda case: "{} res{} S={} N={}".format(*case), n_params=64 + 22, seed=9000, steps=40, tol=TOL)
 
 
 @pytest.fixture(scope="module")
@@ -45,11 +42,10 @@ def nets():
     from occlusionenv_amd.encoder import FrozenEncoder
 
     out = {}
-    for preset in m.PRESETS:
+    for preset in m.JOINT_PRESETS:
         sd32 = {k: v.float() for k, v in m.state_dict(preset).items()}
-        sd64 = {k: v.double() for k, v in sd32.items()}
         for residual in (1, 0):
-            out[preset, residual] = (sd32, sd64, FrozenEncoder.from_state_dict(sd32, preset=preset, dilation=1, residual=bool(residual)))
+            out[preset, residual] = (sd32, FrozenEncoder.from_state_dict(sd32, preset=preset, dilation=1, residual=bool(residual)))
     return out
 
 
@@ -63,15 +59,15 @@ def runs(nets):
 def test_split_cases_reach_the_tile_loops_on_both_sides():
     """What the split cases have to reach, from the two split models alone: at least two tiles per slice in some encoder
     layer and in some decoder level of each, slices that cross env boundaries on both sides, and a short last slice."""
-    for _p, _r, img, n in m.SPLIT_CASES:
-        enc, dec = etm.dw_plans(img, n), dsm.dw_plans(img, n)
+    for _p, _r, img, n in m.JOINT_SPLIT_CASES:
+        enc, dec = tl.dw_plans(img, n), dsm.dw_plans(img, n)
         assert max(p["tps"] for p in enc) >= 2 and max(p["tps"] for p in dec) >= 2, (img, n)
         assert any(p["tps"] >= 2 and p["straddles"] for p in enc) and any(p["short_last"] for p in enc)
         # a decoder slice of more tiles than an env has crosses env boundaries whatever its start
         assert any(p["tps"] >= 2 and (p["straddles"] or p["tps"] > p["tiles_env"]) for p in dec)
-    assert [p["tps"] for p in etm.dw_plans(32, 129)] == [5, 5, 5, 2, 2, 2, 1, 1, 1, 1, 1, 1, 2, 3, 3, 5]
+    assert [p["tps"] for p in tl.dw_plans(32, 129)] == [5, 5, 5, 2, 2, 2, 1, 1, 1, 1, 1, 1, 2, 3, 3, 5]
     assert [p["tps"] for p in dsm.dw_plans(32, 129)] == [3, 1, 1, 1, 2]
-    assert [p["tps"] for p in etm.dw_plans(96, 65)] == [19, 19, 19, 5, 5, 5, 2, 2, 2, 2, 3, 3, 3, 5, 5, 3]
+    assert [p["tps"] for p in tl.dw_plans(96, 65)] == [19, 19, 19, 5, 5, 5, 2, 2, 2, 2, 3, 3, 3, 5, 5, 3]
     assert [p["tps"] for p in dsm.dw_plans(96, 65)] == [2, 2, 2, 2, 5]
     assert any(p["short_last"] for p in dsm.dw_plans(96, 65)) and sum(p["straddles"] for p in dsm.dw_plans(96, 65)) == 3
 
@@ -94,7 +90,7 @@ def test_gradients_through_the_real_losses(runs, losses):
 
 
 @pytest.mark.parametrize("which", ["last", "one"])
-@pytest.mark.parametrize("preset,residual,img,n", m.SPLIT_CASES, ids=IDS[-2:])
+@pytest.mark.parametrize("preset,residual,img,n", m.JOINT_SPLIT_CASES, ids=IDS[-2:])
 def test_gradients_of_one_env(runs, preset, residual, img, n, which):
     """Both upstream gradients are randn in one env and zero in the others: a tile given to the wrong env or dropped from a
     short last slice is the whole signal."""
@@ -128,7 +124,7 @@ def test_errors(nets, runs):
 
     import numpy as np
 
-    sd32, _sd64, _enc = nets["ppo", 1]
+    sd32, _enc = nets["ppo", 1]
     r = runs("ppo", 1, 64, 3)
     with pytest.raises(ValueError, match="dilation 1 only"):
         TrainableFullNetwork.from_encoder(FrozenEncoder.from_state_dict(sd32, preset="ppo"))  # the preset's dilation 2
@@ -140,7 +136,7 @@ def test_errors(nets, runs):
         TrainableFullNetwork.from_encoder(bare)
     suite.errors_tail(FORM, r)
     # "segmenter": Segmenter.forward's pair without the decoder feature
-    seg = TrainableFullNetwork.from_encoder(nets["segmenter", 1][2])
+    seg = TrainableFullNetwork.from_encoder(nets["segmenter", 1][1])
     none, prob = seg(r["obs"])
     assert none is None and prob.shape == (3, 1, 64, 64) and prob.requires_grad and not seg.has_grad_head
 
@@ -148,7 +144,7 @@ def test_errors(nets, runs):
 @pytest.fixture(scope="module")
 def trained(nets):
     """Forty AdamW steps at lr 1e-3 on a fixed batch (N=4, S=64), Dice + MSE as in pretrainer.py."""
-    return suite.trained_joint(FORM, nets["ppo", 1][2])
+    return suite.trained_joint(FORM, nets["ppo", 1][1])
 
 
 def test_learning(trained):
@@ -172,4 +168,4 @@ def test_round_trip_into_a_frozen_encoder(trained):
 
 
 def test_pretrain_epoch(nets):
-    suite.pretrain_epoch(FORM, nets["ppo", 1][2])
+    suite.pretrain_epoch(FORM, nets["ppo", 1][1])

@@ -134,9 +134,9 @@ def test_without_jpeg_nothing_changes(venv, monkeypatch):
 def test_one_pretrain_epoch_from_the_jpeg_store(venv):
     from occlusionenv_amd import devdata, harness
     from occlusionenv_amd.encoder import FrozenEncoder
-    from tests import bn_train_model as btm
+    from tests import train_model as tm
 
     ds = devdata.generate_resident(venv, N, num_frames=1, generator=torch.Generator(device="cuda").manual_seed(7), jpeg=75)
-    enc = FrozenEncoder.from_state_dict(btm.state_dict("golden", "separable"), preset="ppo", dilation=2, residual=True)
+    enc = FrozenEncoder.from_state_dict(tm.joint_state_dict("golden"), preset="ppo", dilation=2, residual=True)
     res = harness.pretrain_epoch(enc, ds.loader(batch_size=N, generator=torch.Generator().manual_seed(41)), native_optimizer=True)
     assert res["batches"] == 1 and res["pixels"] == N * S * S and np.isfinite(res["loss"])

@@ -1,12 +1,12 @@
 """GPU tests of the native separable-encoder backward (csrc/occ_sepenc_bwd.hpp, occlusionenv_amd/septrain.py,
-harness.train_predictor) against tests/sep_encoder_train_model.py in f64 on the CPU, torch autograd supplying the gradients.
-The bodies this module shares with tests/test_gpu_encoder_train.py are in tests/train_gpu_suite.py; FORM below is what they
-are given.
+harness.train_predictor) against tests/train_model.py (the separable encoder-only ``Net``) in f64 on the CPU, torch autograd
+supplying the gradients.  The bodies this module shares with tests/test_gpu_encoder_train.py are in
+tests/train_gpu_suite.py; FORM below is what they are given.
 
 Weights, rounded to f32 (what a checkpoint on disk holds) and used as exactly those values in f64 by the host model:
 "golden" = the separable FullNetwork fixture tests/golden/encoder_golden.npz ("ppo" keys) whose inference is pinned to the
 reference, run at dilation 2 with the residual and once at dilation 1 with the residual; "predictor" =
-sep_encoder_train_model.sep_state_dict("predictor", 32, gain 1.25) at dilation 1 without the residual, tanh head.  Inputs:
+train_model.sep_state_dict("predictor", 32, gain 1.25) at dilation 1 without the residual, tanh head.  Inputs:
 encoder_model.make_obs; the upstream grad_feats is randn.
 
 Shapes: S=32 N=2 (the deepest planes are 2x2 and 1x1: a dilation-2 halo is all padding), S=40 N=3 (sides 40 / 20 / 10 / 5 / 3 /
@@ -42,50 +42,40 @@ import pytest
 import torch
 
 from occlusionenv_amd.septrain import TrainableSeparableEncoder
-from tests import sep_encoder_train_model as m
 from tests import train_gpu_suite as suite
+from tests import train_model as m
 from tests.encoder_model import golden_state_dict
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
 BAND_CAP = 0.01
-SPLIT = ("golden", 2) + m.SPLIT_CASE
+SPLIT = ("golden", 2) + m.SEP_ENCODER_SPLIT_CASE
 SMALL = [(w, d, s, n) for s, n in ((32, 2), (40, 3), (96, 2)) for w, d in (("golden", 2), ("predictor", 1))] + [("golden", 1, 40, 3)]
 CASES = SMALL + [SPLIT]
 IDS = [f"{w}-d{d}-S{s}-N{n}" for w, d, s, n in CASES]
 WORST = {}  # measured worst relative error per tensor kind (printed with -s)
-
-
-def _kind(_case, k):
-    for marker in (".conv.", ".bn."):
-        if marker in k:
-            return k[k.index(marker) + 1:]
-    return "head." + k.rsplit(".", 1)[-1]
-
-
+PRESET = {"golden": "ppo", "predictor": "predictor"}  # weights -> preset; "ppo" has the residual
 FORM = suite.Form(
-    model=m, net=TrainableSeparableEncoder, joint=False, separable=True,
+    net=TrainableSeparableEncoder, model=lambda case: m.Net(PRESET[case[0]], True, case[1], case[0] == "golden"),
     symbols=("occ_sep_encoder_train_workspace_query", "occ_sep_encoder_train_forward", "occ_sep_encoder_backward"),
-    host=lambda entry, case, obs64: m.HostModel(entry[1], entry[2], obs64, dilation=case[1]),
-    label=lambda case: "{} d={} S={} N={}".format(*case), kind=_kind,
+    label=lambda case: "{} d={} S={} N={}".format(*case),
     n_params=11 * 6 + 5 * 4, seed=9000, steps=20, tol=TOL, nonzero_scale=True, band_cap=BAND_CAP, finite_losses=True)
 
 
 @pytest.fixture(scope="module")
 def nets():
-    """(weights, dilation) -> (sd32, sd64, preset, FrozenEncoder)."""
+    """(weights, dilation) -> (sd32, FrozenEncoder)."""
     from occlusionenv_amd.encoder import FrozenEncoder
 
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "encoder_golden.npz"))
     golden = {k: v.float() for k, v in golden_state_dict(g, "ppo").items()}
     pred = {k: v.float() for k, v in m.sep_state_dict("predictor", 32, gain=1.25).items()}
     out = {}
-    for wname, d, sd32, preset in (("golden", 2, golden, "ppo"), ("golden", 1, golden, "ppo"), ("predictor", 1, pred, "predictor")):
-        sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd32.items()}
-        enc = FrozenEncoder.from_state_dict(sd32, preset=preset, dilation=d)
-        assert enc.separable and enc.dilation == d and enc.residual == (preset == "ppo")
-        out[(wname, d)] = (sd32, sd64, preset, enc)
+    for wname, d, sd32 in (("golden", 2, golden), ("golden", 1, golden), ("predictor", 1, pred)):
+        enc = FrozenEncoder.from_state_dict(sd32, preset=PRESET[wname], dilation=d)
+        assert enc.separable and enc.dilation == d and enc.residual == (wname == "golden")
+        out[(wname, d)] = (sd32, enc)
     return out
 
 
@@ -164,9 +154,8 @@ def test_round_trip_into_a_frozen_encoder(trained):
 
 def test_errors(runs):
     from occlusionenv_amd.encoder import FrozenEncoder
-    from tests.encoder_train_model import dense_state_dict
 
-    dense = FrozenEncoder.from_state_dict({k: v.float() for k, v in dense_state_dict("predictor", 32).items()}, preset="predictor")
+    dense = FrozenEncoder.from_state_dict({k: v.float() for k, v in m.dense_state_dict("predictor", 32).items()}, preset="predictor")
     assert not dense.separable
     with pytest.raises(ValueError, match="dense"):
         TrainableSeparableEncoder.from_encoder(dense)
@@ -186,7 +175,7 @@ def test_train_predictor_harness(nets):
     np.random.seed(78)
     torch.manual_seed(78)
     venv = SimpleVecEnv([lambda: OcclusionEnv(ds, img_size=64) for _ in range(4)])
-    enc = nets[("predictor", 1)][3]
+    enc = nets[("predictor", 1)][1]
     net = TrainableSeparableEncoder.from_encoder(enc)
     before = {k: v.detach().clone() for k, v in net.named_parameters()}
     res = harness.train_predictor(venv, net, 4)
@@ -195,5 +184,5 @@ def test_train_predictor_harness(nets):
     assert all(not torch.equal(v, before[k]) for k, v in net.named_parameters())
     res = harness.train_predictor(venv, enc, 1)  # from a separable encoder: the separable net is made
     assert isinstance(res["net"], TrainableSeparableEncoder)
-    res = harness.train_predictor(venv, nets[("golden", 2)][3], 1)  # the "ppo" preset, dilation 2, gradPredictor head
+    res = harness.train_predictor(venv, nets[("golden", 2)][1], 1)  # the "ppo" preset, dilation 2, gradPredictor head
     assert isinstance(res["net"], TrainableSeparableEncoder) and res["net"].enc.dilation == 2

@@ -1,12 +1,12 @@
 """GPU tests of the native joint backward of the separable network (csrc/occ_fullnet_bwd.hpp,
-occlusionenv_amd/sepfullnet.py, harness.pretrain_epoch) against tests/sep_fullnet_train_model.py in f64 on the CPU with torch
-autograd.  The bodies this module shares with tests/test_gpu_fullnet_train.py are in tests/train_gpu_suite.py; FORM below is
-what they are given.
+occlusionenv_amd/sepfullnet.py, harness.pretrain_epoch) against tests/train_model.py (the separable joint ``Net``) in f64 on
+the CPU with torch autograd.  The bodies this module shares with tests/test_gpu_fullnet_train.py are in
+tests/train_gpu_suite.py; FORM below is what they are given.
 
 Weights, rounded to f32 (what a checkpoint on disk holds) and used as exactly those values in f64 by the host model:
 "golden" = the fixture tests/golden/segmenter_golden.npz ("ppo" keys), the reference's own FullNetwork(8, dilation=2,
 separable=True) with its decoder, run at dilation 2 with the residual and once at dilation 1; "seeded" =
-sep_fullnet_train_model.seeded_state_dict, at dilation 2 without the residual.  Inputs: encoder_model.make_obs.  Upstream: a
+train_model.seeded_state_dict, at dilation 2 without the residual.  Inputs: encoder_model.make_obs.  Upstream: a
 randn grad_feats and a randn grad_prob together.
 
 Shapes: S=32 N=2 (the deepest plane is 1 x 1, a dilation-2 halo there is all padding, and Ho = 16 is the smallest side the
@@ -42,24 +42,24 @@ import torch
 
 from occlusionenv_amd.sepfullnet import TrainableSeparableFullNetwork
 from occlusionenv_amd.septrain import TrainableSeparableEncoder
-from tests import sep_fullnet_train_model as m
 from tests import train_gpu_suite as suite
+from tests import train_model as m
 
 pytestmark = pytest.mark.gpu
 
 TOL = m.TOL
 BAND_CAP = 0.01
-CASES = m.CASES
+CASES = m.SEP_JOINT_CASES
 IDS = [f"{w}-d{d}-res{r}-S{s}-N{n}" for w, d, r, s, n in CASES]
-SPLIT_IDS = IDS[len(m.GRAD_CASES):]
+SPLIT_IDS = IDS[len(m.SEP_JOINT_GRAD_CASES):]
 WORST = {}  # measured worst relative error per parameter kind (printed with -s)
 N_ENC, N_DEC = 11 * 6 + 5 * 4, 22
+ENC_KEYS = m.enc_keys(m.Net("ppo", True, 2, True, True))
 FORM = suite.Form(
-    model=m, net=TrainableSeparableFullNetwork, encoder_net=TrainableSeparableEncoder, joint=True, separable=True,
+    net=TrainableSeparableFullNetwork, model=lambda case: m.Net("ppo", True, case[1], bool(case[2]), True),
+    encoder_net=TrainableSeparableEncoder,
     symbols=("occ_sep_fullnet_train_workspace_query", "occ_sep_fullnet_train_forward", "occ_sep_fullnet_backward"),
-    host=lambda entry, case, obs64: m.HostModel(entry[0], case[1], case[2], obs64),
     label=lambda case: "{} d={} res{} S={} N={}".format(*case), gate_label=lambda case: IDS[CASES.index(case)],
-    kind=lambda case, k: m.kind(k), enc_keys=lambda case: m.enc_keys(), dec_keys=lambda case: m.dec_keys(),
     n_params=N_ENC + N_DEC, seed=9000, steps=20, tol=TOL,
     nonzero_scale=True, band_cap=BAND_CAP, head_is_the_decoder=True)
 assert all(suite.case_seed(FORM, c) == m.obs_seed(*c[-2:]) for c in CASES)  # the observations of the host test's gate bands
@@ -72,7 +72,7 @@ def nets():
 
     out = {}
     for weights, d, res in sorted({c[:3] for c in CASES}):
-        sd32 = m.state_dict(weights)
+        sd32 = m.joint_state_dict(weights)
         enc = FrozenEncoder.from_state_dict(sd32, preset="ppo", dilation=d, residual=bool(res))
         assert enc.separable and enc.dilation == d and enc.residual == bool(res) and enc.has_decoder
         out[weights, d, res] = (sd32, enc)
@@ -112,13 +112,13 @@ def test_gradients_through_the_real_losses(runs, losses):
 def test_the_join_itself(runs, weights, d, res, img, n):
     """grad_feats absent: whatever reaches the encoder came through the decoder's skip and input gradients, down to both
     depthwise weights of the initial layer."""
-    assert len(m.enc_keys()) == N_ENC
-    assert {"encoder.initial.conv.0.weight", "encoder.initial.conv.1.weight"} <= set(m.enc_keys())
+    assert len(ENC_KEYS) == N_ENC
+    assert {"encoder.initial.conv.0.weight", "encoder.initial.conv.1.weight"} <= set(ENC_KEYS)
     suite.the_join_itself(FORM, WORST, runs(weights, d, res, img, n), (weights, d, res, img, n))
 
 
 @pytest.mark.parametrize("which", ["last", "one"])
-@pytest.mark.parametrize("weights,d,res,img,n", m.SPLIT_CASES, ids=SPLIT_IDS)
+@pytest.mark.parametrize("weights,d,res,img,n", m.SEP_JOINT_SPLIT_CASES, ids=SPLIT_IDS)
 def test_gradients_of_one_env(runs, weights, d, res, img, n, which):
     """Both upstream gradients are randn in one env and zero in the others: a tile given to the wrong env or dropped from a
     short last slice is the whole signal."""
@@ -142,12 +142,11 @@ def test_no_stale_reads_and_nothing_outside_the_reported_sizes(runs, weights, d,
 def test_errors(nets, runs):
     from occlusionenv_amd.encoder import FrozenEncoder
     from occlusionenv_amd.fullnet import TrainableFullNetwork
-    from tests import fullnet_train_model as ftm
 
     sd32, enc = nets["golden", 2, 1]
     with pytest.raises(ValueError, match="FrozenEncoder"):
         TrainableSeparableFullNetwork.from_encoder(object())
-    dense = FrozenEncoder.from_state_dict({k: v.float() for k, v in ftm.state_dict("ppo").items()}, preset="ppo", dilation=1)
+    dense = FrozenEncoder.from_state_dict({k: v.float() for k, v in m.state_dict("ppo").items()}, preset="ppo", dilation=1)
     assert not dense.separable
     with pytest.raises(ValueError, match=r"dense \(use fullnet.TrainableFullNetwork\)"):
         TrainableSeparableFullNetwork.from_encoder(dense)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import encoder_train_model as etm
+from tests import train_model as tm
 from tests.segmenter_model import golden_seg_state_dict
 
 
@@ -65,8 +65,8 @@ def test_generic_pack_equals_pack_state_dict():
     from occlusionenv_amd.nettrain import ENCODER_PERM, encoder_part, pack_layers
 
     for preset in ("predictor", "ppo"):
-        sd = {k: v.float() for k, v in etm.dense_state_dict(preset, 11).items()}
-        separable, want, _offsets = pack_state_dict(sd, etm.PRESETS[preset][0])
+        sd = {k: v.float() for k, v in tm.dense_state_dict(preset, 11).items()}
+        separable, want, _offsets = pack_state_dict(sd, tm.preset_keys(preset)["prefix"])
         assert not separable
         layers = _folded(sd, encoder_part(preset).stems)
         got = pack_layers(layers, ENCODER_PERM)

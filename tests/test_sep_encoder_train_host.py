@@ -13,10 +13,11 @@ import torch.nn.functional as F
 
 from occlusionenv_amd import _native as nat
 from tests import encoder_model
-from tests import encoder_train_model as etm
-from tests import sep_encoder_train_model as m
+from tests import train_layout as tl
+from tests import train_model as m
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "encoder_golden.npz")
+SEP = m.Net("ppo", True, 2, True)  # the scratch does not depend on the preset, the dilation or the residual
 
 
 def _cfg(img=64, dilation=2, residual=1, separable=1):
@@ -38,24 +39,24 @@ def test_queries_equal_the_model():
             for d in (1, 2):
                 rc, ws_b, sc_b = _query(lib, img, n, dilation=d, residual=d - 1)
                 assert rc == 0
-                assert sc_b == m.scratch_bytes(img, n), (img, n)
+                assert sc_b == tl.scratch_bytes(SEP, img, n), (img, n)
                 # the workspace is the dense training workspace: the same tensors are kept
                 dws, dsc = C.c_size_t(), C.c_size_t()
                 dense = _cfg(img, dilation=1, residual=0, separable=0)
                 assert lib.occ_encoder_train_workspace_query(C.byref(dense), n, C.byref(dws), C.byref(dsc)) == 0
                 assert ws_b == int(dws.value) and ws_b % 256 == 0
-                assert ws_b >= etm.kept_bytes(img, n) + 3 * 4 * n * 8 * img * img
-            for p in m.dpw_plans(img, n):
+                assert ws_b >= tl.kept_bytes(img, n) + 3 * 4 * n * 8 * img * img
+            for p in tl.dpw_plans(img, n):
                 if p["sep"]:
-                    assert p["slices"] * p["grid_y"] <= m.DPW_BLOCKS
+                    assert p["slices"] * p["grid_y"] <= tl.DPW_BLOCKS
                     assert (p["slices"] - 1) * p["tps"] < p["total_tiles"] <= p["slices"] * p["tps"]
-    col = lambda img, n, key: [p[key] for p in m.dpw_plans(img, n)]  # noqa: E731
+    col = lambda img, n, key: [p[key] for p in tl.dpw_plans(img, n)]  # noqa: E731
     assert col(40, 3, "ho") == [40, 40, 40, 20, 20, 20, 10, 10, 10, 5, 5, 5, 3, 3, 3, 2]
     assert col(40, 3, "T") == [16, 16, 16, 8, 8, 8, 8, 8, 8, 8, 4, 4, 4, 4, 4, 4]
-    sep = [i for i, p in enumerate(m.dpw_plans(40, 3)) if p["sep"]]
+    sep = [i for i, p in enumerate(tl.dpw_plans(40, 3)) if p["sep"]]
     assert sep == [0, 1, 2, 4, 5, 7, 8, 10, 11, 13, 14]
     for img, n in ((32, 2), (40, 3), (96, 2)):  # one tile per block in the small cases of the GPU test
-        assert {p["tps"] for p in m.dpw_plans(img, n)} == {1}
+        assert {p["tps"] for p in tl.dpw_plans(img, n)} == {1}
     # the timing shape 128 x 256^2: 256 16-pixel tiles per env at level 0, 32 per slice
     assert col(256, 128, "tps")[:3] == [32, 32, 32] and col(256, 128, "slices")[:3] == [1024] * 3
 
@@ -69,7 +70,7 @@ def test_separable_pack_is_pack_state_dict_and_round_trips():
     separable, want, _offsets = pack_state_dict(sd, "encoder.")
     assert separable and want.size == packed_floats(True)
     part = sep_encoder_part("ppo")
-    assert part.stems == tuple("encoder." + stem for stem, *_ in m.layers())
+    assert part.stems == tuple("encoder." + stem for stem, *_ in m.layers(True))
     assert [len(leaves) for leaves in part.layer_leaves()] == [6] + [6, 6, 4] * 5
     folded = []
     for stem, leaves in zip(part.stems, part.layer_leaves()):
@@ -105,9 +106,9 @@ def test_dense_parts_are_unchanged():
 
 def test_split_case_reaches_the_tile_loop():
     """What the split case of tests/test_gpu_sep_encoder_train.py has to reach, on the model alone."""
-    img, n = m.SPLIT_CASE
+    img, n = m.SEP_ENCODER_SPLIT_CASE
     assert (img, n) == (33, 115)
-    plans = m.dpw_plans(img, n)
+    plans = tl.dpw_plans(img, n)
     assert [p["ho"] for p in plans] == [33, 33, 33, 17, 17, 17, 9, 9, 9, 5, 5, 5, 3, 3, 3, 2]
     assert [p["tps"] for p in plans if p["sep"]] == [2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1]
     # the initial layer and both layers of levels 0 (16-pixel tiles) and 1 (8-pixel tiles): 9 tiles per env (the last row and
@@ -151,7 +152,8 @@ def test_gated_model_with_its_own_gates_is_plain_autograd():
     obs = encoder_model.make_obs(22, 2, 40)
     up = torch.randn(2, 256, generator=torch.Generator().manual_seed(23), dtype=torch.float64)
     for d in (1, 2):
-        host = m.HostModel(sd, "ppo", obs, dilation=d)
+        net = m.Net("ppo", True, d, True)
+        host = m.HostModel(sd, net, obs)
         us = []
         f_plain = host.feats(None, us)
         assert len(us) == 16 and [u.shape[-1] for u in us] == [40, 40, 40, 20, 20, 20, 10, 10, 10, 5, 5, 5, 3, 3, 3, 2]
@@ -159,7 +161,7 @@ def test_gated_model_with_its_own_gates_is_plain_autograd():
         f_ref = encoder_model.encode(ref, obs, "encoder.", True, d, True)
         assert torch.allclose(f_plain.detach(), f_ref.detach(), rtol=1e-13, atol=1e-13)  # the sliced depthwise pair
         (f_ref * up).sum().backward()
-        want = {k: ref[k].grad for k in m.param_keys("ppo")}
+        want = {k: ref[k].grad for k in m.param_keys(net)}
         plain = host.grads((f_plain * up).sum())
         assert len(want) == 11 * 6 + 5 * 4
         gated = host.grads((host.feats([(u > 0).double() for u in us]) * up).sum())

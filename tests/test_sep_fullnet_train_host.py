@@ -1,9 +1,9 @@
 """Host-side checks of the joint training path of the separable network (csrc/occ_fullnet_bwd.hpp,
 occlusionenv_amd/sepfullnet.py): the workspace query is the restated layout, the two parts' packed layouts round-trip from
-the whole checkpoint, the f64 model of tests/sep_fullnet_train_model.py is the composition of the separable encoder's and the
-decoder's models, the split cases of the GPU test reach what they claim, and every GPU case keeps its gate band small.  The
-argument contract of the three entry points is checked from the table of tests/train_abi.py by
-tests/test_train_abi_host.py.  No GPU."""
+the whole checkpoint, the separable joint f64 model of tests/train_model.py is the inference model of
+tests/segmenter_model.py and its joint gradient the sum of its two losses' gradients, the split cases of the GPU test reach
+what they claim, and every GPU case keeps its gate band small.  The argument contract of the three entry points is checked
+from the table of tests/train_abi.py by tests/test_train_abi_host.py.  No GPU."""
 import ctypes as C
 
 import numpy as np
@@ -12,12 +12,13 @@ import torch
 
 from occlusionenv_amd import _native as nat
 from tests import decoder_split_model as dsm
-from tests import fullnet_train_model as ftm
 from tests import segmenter_model
-from tests import sep_encoder_train_model as stm
-from tests import sep_fullnet_train_model as m
+from tests import train_layout as tl
+from tests import train_model as m
 
 BAND_CAP = 0.005
+JOINT = m.Net("ppo", True, 2, True, True)  # the sizes and the keys do not depend on the dilation or the residual
+DENSE_JOINT = m.Net("ppo", False, 1, True, True)
 
 
 def _cfg(img=64, dilation=2, residual=1, separable=1):
@@ -34,14 +35,14 @@ def _query(lib, img, n, **kw):
 
 def test_workspace_query_is_the_restated_layout():
     lib = nat.load()
-    pairs = {(s, n) for _w, _d, _r, s, n in m.CASES} | {(64, 4), (64, 1), (256, 128), (512, 64), (1024, 1)}
+    pairs = {(s, n) for _w, _d, _r, s, n in m.SEP_JOINT_CASES} | {(64, 4), (64, 1), (256, 128), (512, 64), (1024, 1)}
     assert {(32, 2), (64, 3), (96, 2), (64, 130), (96, 65)} <= pairs
     for img, n in sorted(pairs):
         for d, residual in ((2, 1), (1, 1), (2, 0)):
             rc, ws_b, sc_b = _query(lib, img, n, dilation=d, residual=residual)
             assert rc == 0
-            assert ws_b == m.ws_bytes(img, n) == ftm.ws_bytes(img, n), (img, n)
-            assert sc_b == m.scratch_bytes(img, n), (img, n)
+            assert ws_b == tl.ws_bytes(JOINT, img, n) == tl.ws_bytes(DENSE_JOINT, img, n), (img, n)
+            assert sc_b == tl.scratch_bytes(JOINT, img, n), (img, n)
             assert ws_b % 256 == 0 and sc_b % 256 == 0
         # the workspace is the dense joint one; the scratch the larger of the two single passes'
         f_ws, f_sc = C.c_size_t(), C.c_size_t()
@@ -51,7 +52,7 @@ def test_workspace_query_is_the_restated_layout():
         e_ws, e_sc, d_ws, d_sc = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         assert lib.occ_sep_encoder_train_workspace_query(C.byref(_cfg(img)), n, C.byref(e_ws), C.byref(e_sc)) == 0
         assert lib.occ_segment_train_workspace_query(C.byref(_cfg(img)), n, C.byref(d_ws), C.byref(d_sc)) == 0
-        assert int(e_ws.value) == m.encoder_ws_bytes(img, n)
+        assert int(e_ws.value) == tl.encoder_ws_bytes(img, n)
         assert sc_b == max(int(e_sc.value), int(d_sc.value))
         assert ws_b < int(e_ws.value) + int(d_ws.value)  # one encoder pass, 0.94 kept d skip buffers
 
@@ -63,14 +64,14 @@ def test_pack_round_trips_from_a_whole_checkpoint(weights):
     from occlusionenv_amd.encoder import DECODER_KEYS, pack_decoder, pack_state_dict
     from occlusionenv_amd.nettrain import decoder_part, fold_bn_vectors, sep_encoder_part
 
-    sd = m.state_dict(weights)
-    assert set(m.enc_keys() + m.dec_keys() + m.head_keys()) <= set(sd)
-    assert len(m.enc_keys()) == 11 * 6 + 5 * 4 and len(m.dec_keys()) == 22
+    sd = m.joint_state_dict(weights)
+    assert set(m.param_keys(JOINT, head=True)) <= set(sd)
+    assert len(m.enc_keys(JOINT)) == 11 * 6 + 5 * 4 and len(m.dec_keys(JOINT)) == 22
     separable, want_enc, _off = pack_state_dict(sd, "encoder.")
     assert separable
-    want = [want_enc, pack_decoder(sd, *DECODER_KEYS[m.PRESET])]
-    parts = [sep_encoder_part(m.PRESET), decoder_part(m.PRESET)]
-    assert list(parts[0].stems) == ["encoder." + stem for stem, *_ in stm.layers()]
+    want = [want_enc, pack_decoder(sd, *DECODER_KEYS["ppo"])]
+    parts = [sep_encoder_part("ppo"), decoder_part("ppo")]
+    assert list(parts[0].stems) == ["encoder." + stem for stem, *_ in m.layers(True)]
     for part, buf in zip(parts, want):
         folded = []
         for stem, leaves in zip(part.stems, part.layer_leaves()):
@@ -88,22 +89,22 @@ def test_pack_round_trips_from_a_whole_checkpoint(weights):
 
 
 @pytest.mark.parametrize("weights,dilation,residual", [("golden", 2, 1), ("golden", 1, 1), ("seeded", 2, 0)])
-def test_model_is_the_composition_of_the_two_models(weights, dilation, residual):
-    """Without gates: pooled is sep_encoder_train_model.encode_gated, the map segmenter_model.decode on segmenter_model.
-    encode_full, bitwise; with its own gates it is the same function up to rounding; each upstream gradient alone gives its
-    constituent's gradients, bitwise where the other one is zero."""
-    obs = m.case_obs(32, 2)
-    sd = {k: v.double() for k, v in m.state_dict(weights).items()}
-    p = segmenter_model.PRESETS[m.PRESET]
+def test_forward_is_the_inference_model(weights, dilation, residual):
+    """Without gates: segmenter_model.full_forward (decode on encode_full, the classifier, the pool), up to the rounding of
+    the depthwise pair; with its own gates it is the same function up to rounding; grad_feats alone gives the encoder-only
+    net's gradients bitwise and leaves the decoder's exactly zero; both upstream gradients together give the sum of the
+    two."""
+    obs = m.case_obs((32, 2))
+    sd = {k: v.double() for k, v in m.joint_state_dict(weights).items()}
+    net = m.Net("ppo", True, dilation, bool(residual), True)
     us = []
-    pooled, logit = m.forward_gated(sd, obs, dilation, residual, None, us)
+    pooled, logit = m.forward_gated(sd, obs, net, None, us)
     assert len(us) == 21 and [u.shape[-1] for u in us[16:]] == [2, 4, 8, 16, 32] and us[15].shape[1:] == (256, 1, 1)
-    assert torch.equal(pooled, stm.encode_gated(sd, obs, p["prefix"], dilation, bool(residual)))
-    ref = segmenter_model.full_forward(sd, obs, m.PRESET, dilation, bool(residual))
+    ref = segmenter_model.full_forward(sd, obs, "ppo", dilation, bool(residual))
     # encode_full's depthwise pair is F.conv2d, the model's the sliced sums: the same function, not the same rounding
     assert torch.allclose(logit, ref["logit"], rtol=1e-12, atol=1e-13) and torch.allclose(pooled, ref["pooled"], rtol=1e-12, atol=1e-13)
     gates = [(u > 0).double() for u in us]
-    pooled_g, logit_g = m.forward_gated(sd, obs, dilation, residual, gates)
+    pooled_g, logit_g = m.forward_gated(sd, obs, net, gates)
     assert torch.allclose(pooled_g, pooled, rtol=1e-12, atol=1e-14) and torch.allclose(logit_g, logit, rtol=1e-12, atol=1e-14)
     # alive: every layer has open and closed gates, the map both classes
     assert all(0.02 < float(g.mean()) < 0.98 for g in gates), [float(g.mean()) for g in gates]
@@ -112,57 +113,26 @@ def test_model_is_the_composition_of_the_two_models(weights, dilation, residual)
     gen = torch.Generator().manual_seed(44)
     gf = torch.randn(2, 256, generator=gen, dtype=torch.float64)
     gp = torch.randn(2, 1, 32, 32, generator=gen, dtype=torch.float64)
-    host = m.HostModel(sd, dilation, residual, obs)
-    # grad_prob = 0: the encoder's gradients are the separable encoder model's, the decoder's exactly zero
+    host = m.HostModel(sd, net, obs)
+    # grad_prob = 0: the encoder's gradients are the encoder-only net's, the decoder's exactly zero
     a = host.grads((host.forward(gates)[0] * gf).sum())
-    enc_host = stm.HostModel(sd, m.PRESET, obs, dilation=dilation, residual=bool(residual))
+    enc_host = m.HostModel(sd, net._replace(joint=False), obs)
     want = enc_host.grads((enc_host.feats(gates[:16]) * gf).sum())
-    assert set(want) == set(m.enc_keys()) and all(torch.equal(a[k], w) for k, w in want.items())
-    assert all(float(a[k].abs().max()) == 0.0 for k in m.dec_keys())
-    # grad_feats = 0: the decoder's gradients are those of the dense joint model's decoder on the same last / skips
+    assert set(want) == set(m.enc_keys(net)) and all(torch.equal(a[k], w) for k, w in want.items())
+    assert all(float(a[k].abs().max()) == 0.0 for k in m.dec_keys(net))
+    # grad_feats = 0: the map's loss reaches every encoder layer (the join) and every decoder level
     b = host.grads((host.forward(gates)[1] * gp).sum())
-    assert all(float(b[k].abs().max()) > 0.0 for k in m.enc_keys() + m.dec_keys())
-    dec = {k: sd[k].clone().requires_grad_() for k in m.dec_keys()}
-    with torch.no_grad():
-        x, skips = _last_and_skips(sd, obs, dilation, residual, gates)
-    prob = torch.sigmoid(_decode_gated({**sd, **dec}, x, skips, gates[16:]))
-    (prob * gp).sum().backward()
-    assert all(torch.equal(b[k], dec[k].grad) for k in m.dec_keys())
+    assert all(float(b[k].abs().max()) > 0.0 for k in m.param_keys(net))
     # together: the sum of the two
     joint = host.grads((host.forward(gates)[0] * gf).sum() + (host.forward(gates)[1] * gp).sum())
     for k, w in joint.items():
         assert torch.allclose(a[k] + b[k], w, rtol=1e-11, atol=1e-13 * float(w.abs().max())), k
 
 
-def _last_and_skips(sd, obs, dilation, residual, gates):
-    """The gated separable encoder's last down output and level outputs, read off forward_gated by its own hooks."""
-    us = []
-    m.forward_gated(sd, obs, dilation, residual, gates, us)
-    p = segmenter_model.PRESETS[m.PRESET]["prefix"]
-    skips, x = [], None
-    for i, (stem, *_rest) in enumerate(stm.layers()):
-        y = ftm._bn(us[i] * gates[i], sd, p + stem)
-        if stem.endswith("Layer 2."):
-            skips.append(y + x if residual else y)
-        if stem == "initial." or stem.endswith("down."):
-            x = y  # the block input of the next level; after the last down, the decoder's input
-    return x, skips
-
-
-def _decode_gated(sd, x, skips, gates):
-    """fullnet_train_model.forward_gated's decoder on given inputs."""
-    p = segmenter_model.PRESETS[m.PRESET]
-    for j, y in enumerate(skips[::-1]):
-        st = f"{p['decoder']}{j}.up."
-        u = torch.nn.functional.conv_transpose2d(x, sd[st + "conv.weight"], sd[st + "conv.bias"], stride=2, padding=1, output_padding=1)
-        x = ftm._bn(u * gates[j], sd, st) + y
-    return torch.nn.functional.conv2d(x, sd[p["classifier"] + "weight"], sd[p["classifier"] + "bias"])
-
-
 def test_split_cases_reach_what_they_claim():
-    """From sep_encoder_train_model.dpw_plans and decoder_split_model.dw_plans alone."""
-    assert [(s, n) for _w, _d, _r, s, n in m.SPLIT_CASES] == [(64, 130), (96, 65)]
-    enc = stm.dpw_plans(64, 130)
+    """From train_layout.dpw_plans and decoder_split_model.dw_plans alone."""
+    assert [(s, n) for _w, _d, _r, s, n in m.SEP_JOINT_SPLIT_CASES] == [(64, 130), (96, 65)]
+    enc = tl.dpw_plans(64, 130)
     # the initial layer and both layers of levels 0 (16-pixel tiles, 16 per env) and 1 (8-pixel tiles, 16 per env): 3 tiles
     # per slice, 2080 = 693 x 3 + 1: a last slice of one tile, slices crossing env boundaries
     for p in enc[:3] + enc[4:6]:
@@ -177,20 +147,21 @@ def test_split_cases_reach_what_they_claim():
     dec = dsm.dw_plans(96, 65)
     assert [p["tps"] for p in dec] == [2, 2, 2, 2, 5]
     assert any(p["short_last"] for p in dec) and sum(p["straddles"] for p in dec) == 3
-    enc = stm.dpw_plans(96, 65)
+    enc = tl.dpw_plans(96, 65)
     for i in (10, 11, 13, 14):
         assert enc[i]["sep"] and enc[i]["tps"] >= 2 and enc[i]["straddles"] and enc[i]["short_last"], (i, enc[i])
-    assert ("golden", 2, 1, 96, 65) in m.SPLIT_CASES and ("ppo", 96, 65) in dsm.SPLIT_CASES
+    assert ("golden", 2, 1, 96, 65) in m.SEP_JOINT_SPLIT_CASES and ("ppo", 96, 65) in dsm.SPLIT_CASES
 
 
-@pytest.mark.parametrize("weights,dilation,residual,img,n", m.CASES, ids=[f"{w}-d{d}-res{r}-S{s}-N{n}" for w, d, r, s, n in m.CASES])
+@pytest.mark.parametrize("weights,dilation,residual,img,n", m.SEP_JOINT_CASES,
+                         ids=[f"{w}-d{d}-res{r}-S{s}-N{n}" for w, d, r, s, n in m.SEP_JOINT_CASES])
 def test_gate_band_is_small_in_every_gpu_case(weights, dilation, residual, img, n):
     """From the f64 model alone: at most 0.5 % of any layer's pixels have |u| <= 1e-4 max(1, max |u|), so that the 1 % cap
     of the GPU test is met or missed by the kernels and not by the inputs."""
-    sd = {k: v.double() for k, v in m.state_dict(weights).items()}
+    sd = {k: v.double() for k, v in m.joint_state_dict(weights).items()}
     us = []
     with torch.no_grad():
-        m.forward_gated(sd, m.case_obs(img, n), dilation, residual, None, us)
+        m.forward_gated(sd, m.case_obs((img, n)), m.Net("ppo", True, dilation, bool(residual), True), None, us)
     shares = m.band_shares(us)
     assert len(shares) == 21
     assert max(shares) <= BAND_CAP, [f"{s:.4f}" for s in shares]

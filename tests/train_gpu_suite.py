@@ -5,10 +5,11 @@ tests/test_gpu_fullnet_train.py and tests/test_gpu_sep_fullnet_train.py (the joi
 call in here.  Nothing is cached in this module: what lives on the device is what the calling module's fixtures hold.
 
 A case is a tuple that ends in (img, n); what is in front of it selects the weights (the key of the module's ``nets``, whose
-entries end in the FrozenEncoder).  A joint form's step has two outputs, (feats, prob), and two upstream gradients; an
-encoder form's has feats alone."""
+entries are (the f32 state dict, the FrozenEncoder)).  A joint form's step has two outputs, (feats, prob), and two upstream
+gradients; an encoder form's has feats alone.  The oracle is tests/train_model.HostModel on the case's f32 weights, the
+workspace layout tests/train_layout.py."""
 import ctypes as C
-from typing import Any, Callable, NamedTuple, Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 import pytest
@@ -16,6 +17,8 @@ import torch
 import torch.nn.functional as F
 
 from tests import decoder_split_model as dsm
+from tests import train_layout as tl
+from tests import train_model as tm
 from tests.encoder_model import make_obs
 from tests.train_utils import GUARD, bce64, dice64, grads, guarded
 
@@ -24,27 +27,26 @@ NAN = 0x7FC00000
 
 
 class Form(NamedTuple):
-    model: Any                    # the f64 host model's module
     net: type                     # the trainable net
-    joint: bool                   # the step returns (feats, prob), else feats
+    model: Callable               # case -> the train_model.Net it runs
     symbols: Tuple[str, str, str]  # workspace query, train forward, backward
-    separable: bool               # of encoder.packed_floats
-    host: Callable                # (entry of nets, case, f64 obs) -> the module's HostModel
     label: Callable               # case -> what a printed line starts with
-    kind: Callable                # (case, key) -> the parameter kind WORST is kept by
     n_params: int                 # tensors that receive a gradient, without the head's two
     seed: int                     # 7000 or 9000: a case's seed is seed + img + n
     steps: int                    # AdamW steps of ``trained``
     tol: float
     encoder_net: Optional[type] = None   # joint: the single encoder pass the joint step is compared with
-    enc_keys: Optional[Callable] = None  # joint: case -> the encoder's keys
-    dec_keys: Optional[Callable] = None  # joint: case -> the decoder's and the classifier's keys
     gate_label: Optional[Callable] = None  # case -> the start of a gate line, where it is not ``label``
     # what one form asserts and the other does not
     nonzero_scale: bool = False       # no wanted gradient is all zero
     band_cap: Optional[float] = None  # the largest share of a layer's pixels inside the gate band
     head_is_the_decoder: bool = False  # SegmentationHead's gradients are exactly the decoder keys
     finite_losses: bool = False       # the losses of ``trained`` are finite, not only not NaN
+
+    @property
+    def joint(self):
+        """The step returns (feats, prob), else feats alone."""
+        return "prob" in self.net.RETURNS
 
 
 def case_seed(f, case):
@@ -62,20 +64,16 @@ def _total(outs):
     return total
 
 
-def _kept(f, net, i):
-    return f.model.kept_relu(net, i) if f.joint else net._kept_relu(i)
-
-
 def _n_relu(f):
     return 21 if f.joint else 16
 
 
 def gates_of(f, net):
-    return [(_kept(f, net, i).cpu() > 0).double() for i in range(_n_relu(f))]
+    return [(tl.kept_relu(net, i).cpu() > 0).double() for i in range(_n_relu(f))]
 
 
 def _host_outs(f, host, gates, us=None):
-    return host.forward(gates, us)[:2] if f.joint else (host.feats(gates, us),)
+    return host.forward(gates, us)[:2 if f.joint else 1]
 
 
 def _dot(outs64, ups):
@@ -98,8 +96,7 @@ def make_runs(f, nets):
         if case not in cache:
             img, n = case[-2:]
             key = case[:-2]
-            entry = nets[key if len(key) > 1 else key[0]]
-            enc = entry[-1]
+            sd32, enc = nets[key if len(key) > 1 else key[0]]
             obs = make_obs(case_seed(f, case), n, img).float().cuda()
             net = f.net.from_encoder(enc)
             outs = _step(f, net, obs)
@@ -107,10 +104,11 @@ def make_runs(f, nets):
             ups = [torch.randn(*s, generator=gen) for s in _shapes(f, img, n)]
             net.zero_grad()
             torch.autograd.backward(list(outs), [u.cuda() for u in ups])
-            kept = [_kept(f, net, i).cpu().clone() for i in range(_n_relu(f))]
+            kept = [tl.kept_relu(net, i).cpu().clone() for i in range(_n_relu(f))]
             cache[case] = dict(enc=enc, net=net, obs=obs, outs=[o.detach() for o in outs], feats=outs[0].detach(), ups=ups,
                                kept=kept, gates=[(k > 0).double() for k in kept],
-                               grads={k: v.cpu() for k, v in grads(net).items()}, host=f.host(entry, case, obs.double().cpu()))
+                               grads={k: v.cpu() for k, v in grads(net).items()},
+                               host=tm.HostModel(sd32, f.model(case), obs.double().cpu()))
         return cache[case]
 
     return get
@@ -122,7 +120,7 @@ def check_grads(f, worst, what, case, got, want):
         if f.nonzero_scale:
             assert scale > 0.0, (what, k, "the oracle's gradient is all zero")
         err = float((got[k].double().cpu() - w).abs().max()) / scale
-        kind = f.kind(case, k)
+        kind = tm.kind(f.model(case), k)
         worst[kind] = max(worst.get(kind, 0.0), err)
         print(f"{what} {k}: max|want| {scale:.3g}, relative error {err:.3g}")
     for k, w in want.items():
@@ -144,7 +142,10 @@ def kept_relu_and_gates(f, r, case):
     with torch.no_grad():
         _host_outs(f, r["host"], None, us)
     assert len(us) == len(r["kept"]) == _n_relu(f)
-    start = (f.gate_label or f.label)(case)
+    if not f.joint:  # the package's own view of the encoder-only workspace (PooledFeatureNet._kept_relu) is the same view
+        mine, theirs = [tl.kept_relu(r["net"], i) for i in range(16)], [r["net"]._kept_relu(i) for i in range(16)]
+        assert all(a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.dtype == b.dtype for a, b in zip(mine, theirs))
+    start =(f.gate_label or f.label)(case)
     total, worst_band, worst_err = 0, 0.0, 0.0
     for i, (u64, got) in enumerate(zip(us, r["kept"])):
         assert got.shape == u64.shape
@@ -250,7 +251,7 @@ def the_join_itself(f, worst, r, case):
     _feats, prob = net.features_and_map(r["obs"])
     prob.backward(r["ups"][1].cuda())  # the absent gradient of feats arrives as zeros
     got = grads(net)
-    assert all(float(got[k].abs().max()) > 0.0 for k in f.enc_keys(case))
+    assert all(float(got[k].abs().max()) > 0.0 for k in tm.enc_keys(f.model(case)))
     _pooled64, prob64, _pred = host.forward(gates_of(f, net))
     want = host.grads((prob64 * r["ups"][1].double()).sum())
     check_grads(f, worst, f"join {f.label(case)}", case, got, want)
@@ -261,24 +262,25 @@ def bitwise_against_the_single_passes(f, r, case):
 
     net, enc, obs = r["net"], r["enc"], r["obs"]
     gf, gp = (u.cuda() for u in r["ups"])
-    n_dec = len(f.dec_keys(case))
+    enc_keys, dec_keys = tm.enc_keys(f.model(case)), tm.dec_keys(f.model(case))
+    n_dec = len(dec_keys)
     # the decoder and classifier gradients are SegmentationHead's for the same grad_prob, whatever grad_feats is
     head = SegmentationHead.from_encoder(enc)
     head(obs).backward(gp)
     hg = grads(head)
     assert len(hg) == n_dec == 22 and all(torch.equal(v.cpu(), r["grads"][k]) for k, v in hg.items())
     if f.head_is_the_decoder:
-        assert set(hg) == set(f.dec_keys(case))
+        assert set(hg) == set(dec_keys)
     # with grad_prob absent the encoder gradients are the single encoder pass's and the decoder's exactly zero
     tenc = f.encoder_net.from_encoder(enc)
     tenc(obs).backward(gf)
-    eg = {k: v for k, v in grads(tenc).items() if k in f.enc_keys(case)}
+    eg = {k: v for k, v in grads(tenc).items() if k in enc_keys}
     net.zero_grad()
     feats, _prob = net.features_and_map(obs)
     feats.backward(gf)
     got = grads(net)
     assert len(eg) == f.n_params - n_dec and all(torch.equal(v, got[k]) for k, v in eg.items())
-    assert all(float(got[k].abs().max()) == 0.0 for k in f.dec_keys(case))
+    assert all(float(got[k].abs().max()) == 0.0 for k in dec_keys)
     # two joint backward calls give the same bits
     net.zero_grad()
     feats, prob = net.features_and_map(obs)
@@ -296,7 +298,7 @@ def no_stale_reads_and_nothing_outside_the_reported_sizes(f, r, case):
     from occlusionenv_amd.encoder import decoder_packed_floats, packed_floats
 
     img, n = case[-2:]
-    m, enc, net, obs = f.model, r["enc"], r["net"], r["obs"]
+    m, enc, net, obs = f.model(case), r["enc"], r["net"], r["obs"]
     ups = [u.cuda() for u in r["ups"]]
     packed = [enc.packed, enc.dec_packed] if f.joint else [enc.packed]
     out_names = ["feats", "prob"] if f.joint else ["feats"]
@@ -306,11 +308,9 @@ def no_stale_reads_and_nothing_outside_the_reported_sizes(f, r, case):
     wsb, scb = C.c_size_t(), C.c_size_t()
     nat.check(getattr(lib, query)(C.byref(cfg), n, C.byref(wsb), C.byref(scb)), query)
     sizes = dict(ws=int(wsb.value), scratch=int(scb.value))
-    sizes.update(zip(grad_names, (4 * packed_floats(f.separable), 4 * decoder_packed_floats())))
+    sizes.update(zip(grad_names, (4 * packed_floats(m.separable), 4 * decoder_packed_floats())))
     sizes.update(zip(out_names, (4 * n * FEATURES, 4 * n * img * img)))
-    assert sizes["scratch"] == m.scratch_bytes(img, n)
-    if f.joint:
-        assert sizes["ws"] == m.ws_bytes(img, n)
+    assert sizes["scratch"] == tl.scratch_bytes(m, img, n) and sizes["ws"] == tl.ws_bytes(m, img, n)
     bufs = {k: guarded(b) for k, b in sizes.items()}
     mid = {k: whole[lo:lo + sizes[k]] for k, (whole, lo) in bufs.items()}
     assert all(v.data_ptr() % 256 == 0 for v in mid.values())
@@ -331,7 +331,7 @@ def no_stale_reads_and_nothing_outside_the_reported_sizes(f, r, case):
     # what the backward only writes: g0 | g1 | g2 at the end of the encoder's workspace (include/occlusionenv_amd.h) and, in a
     # joint form, dlast | dskip at the end of the whole
     buf = dsm.align(4 * n * 8 * img * img)
-    e_end = m.encoder_ws_bytes(img, n) if f.joint else sizes["ws"]
+    e_end = tl.encoder_ws_bytes(img, n)
     mid["ws"][e_end - 3 * buf:e_end].view(torch.int32).fill_(NAN)
     if f.joint:
         tail = dsm.align(4 * n * 256 * (img // 32) ** 2) + sum(dsm.level_bytes(img, n)[:4])
