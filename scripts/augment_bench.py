@@ -18,7 +18,6 @@ The frames are seeded noise written through ``dataset_io.RunWriter`` into a temp
 readers, so both decode the same files.
 """
 import argparse
-import json
 import os
 import shutil
 import statistics
@@ -31,7 +30,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+import benchlib as bl  # noqa: E402
 
 STEP_MS = 21.14  # separable d2 at 128 x 256^2, profiles/pretrain_step_bench.json
 BAR_MS = 0.05 * STEP_MS
@@ -88,9 +88,6 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "augment_bench needs a GPU"
-    from pretrain_step_bench import count_launches
-    from sep_encoder_train_bench import sample
-
     from occlusionenv_amd import dataset_io, devdata, harness
     from occlusionenv_amd.encoder import FrozenEncoder
     from occlusionenv_amd.netoptim import PackedAdamW
@@ -115,19 +112,8 @@ def main():
         idx_dev, params_dev = idx.cuda(), devdata._params_tensor(params).cuda()
         paths = dict(batch=lambda: ds.batch(idx, params), resident=lambda: ds._run(idx_dev, params_dev, True),
                      resident_no_jitter=lambda: ds._run(idx_dev, None, True))
-        for _ in range(args.warmup):
-            for fn in paths.values():
-                sample(fn, args.calls)
-        ms = {k: [] for k in paths}
-        for _ in range(args.iters):
-            for k, fn in paths.items():
-                ms[k].append(sample(fn, args.calls))
-        for k, v in ms.items():
-            out[f"a_{k}_ms"], out[f"a_{k}_ms_all"] = statistics.median(v), v
-            try:
-                out[f"a_{k}_kernel_launches"], out[f"a_{k}_copies_and_memsets"] = count_launches(paths[k])
-            except Exception as e:  # the trace is evidence, not the product
-                out[f"a_{k}_kernel_launches"], out[f"a_{k}_launch_count_error"] = None, repr(e)
+        out.update(bl.medians(bl.interleaved(paths, args.warmup, args.iters, args.calls), "a_"))
+        out.update(bl.launch_counts(paths, "a_"))
         out["a_bytes_moved"] = B * S * S * (2 * 6 + 20)
         out["a_under_bar"] = bool(out["a_batch_ms"] < BAR_MS)
 
@@ -162,10 +148,8 @@ def main():
         del cpu_loader
     finally:
         shutil.rmtree(root, ignore_errors=True)
-    print(json.dumps({k: v for k, v in out.items() if not k.endswith("_all")}), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+    bl.emit(out)
+    bl.write(out, args.out)
 
 
 if __name__ == "__main__":

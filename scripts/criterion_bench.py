@@ -12,9 +12,7 @@ least HBM traffic of a step (pred and target read once for the sums, once for th
 counted from the shape; the share of peak uses 8.0 TB/s.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
@@ -22,10 +20,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import benchlib as bl  # noqa: E402
 from occlusionenv_amd import ops  # noqa: E402
 from tests import criterion_model as cm  # noqa: E402
-
-PEAK_HBM = 8.0e12
 
 
 def native_step(pred, target):
@@ -51,16 +48,6 @@ def torch_step(pred, target):
     return loss, correct, inter, union
 
 
-def sample(fn, calls):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / calls
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=128)
@@ -83,27 +70,17 @@ def main():
     got = nat()
     diff = dict(loss=abs(float(want[0].detach()) - float(got[0].detach())), grad_rel_to_max=float((pred.grad - want_grad).abs().max() / want_grad.abs().max()),
                 counts_equal=all(int(a) == int(b) for a, b in zip(want[1:], got[1:])))
-    for _ in range(args.warmup):
-        sample(nat, args.calls), sample(ref, args.calls)
-    nms, tms = [], []
-    for _ in range(args.iters):
-        nms.append(sample(nat, args.calls))
-        tms.append(sample(ref, args.calls))
-    med, tmed = statistics.median(nms), statistics.median(tms)
-    margin = max(max(nms) - min(nms), max(tms) - min(tms))
+    ms = bl.interleaved(dict(native=nat, torch=ref), args.warmup, args.iters, args.calls)
     pixels = args.n * args.img * args.img
     # native: the metrics pass and the loss's forward each read both maps, the backward reads both and writes one
     native_bytes = 4 * pixels * (2 + 2 + 3)
     least_bytes = 4 * pixels * (2 + 3)
     r = dict(device=torch.cuda.get_device_name(0), n_env=args.n, img=args.img, warmup=args.warmup, iters=args.iters,
-             calls_per_sample=args.calls, native_ms=med, native_ms_all=nms, torch_ms=tmed, torch_ms_all=tms,
-             native_spread_ms=max(nms) - min(nms), torch_spread_ms=max(tms) - min(tms), margin_ms=margin, speedup=tmed / med,
-             not_slower=bool(med <= tmed + margin), native_bytes_per_step=native_bytes, least_bytes_per_step=least_bytes,
-             native_frac_hbm_peak=native_bytes / PEAK_HBM / (med * 1e-3), diff_vs_torch_f32=diff)
-    print(json.dumps({k: v for k, v in r.items() if not k.endswith("_all")}), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(r, f, indent=1)
+             calls_per_sample=args.calls, **bl.named(bl.compare(ms["native"], ms["torch"]), bl.ONE_RIVAL_NOT_SLOWER))
+    r.update(native_bytes_per_step=native_bytes, least_bytes_per_step=least_bytes,
+             native_frac_hbm_peak=native_bytes / bl.PEAK_HBM / (r["native_ms"] * 1e-3), diff_vs_torch_f32=diff)
+    bl.emit(r)
+    bl.write(r, args.out)
 
 
 if __name__ == "__main__":

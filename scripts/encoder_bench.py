@@ -9,9 +9,7 @@ timings per call.  MACs, FLOPs and the least HBM traffic (every layer reads its 
 are counted from the shapes; shares of peak use 157.3 TF f32 and 8.0 TB/s.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -20,38 +18,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import benchlib as bl  # noqa: E402
 from occlusionenv_amd import encoder as E  # noqa: E402
 from tests.encoder_model import encode, golden_state_dict, make_obs  # noqa: E402
-
-PEAK_F32, PEAK_HBM = 157.3e12, 8.0e12
-
-
-def work(img: int, separable: bool, residual: bool):
-    """(MACs, least bytes) per env."""
-    macs, nbytes, h = 0, 4 * 4 * img * img, img
-    for _stem, cin, cout, sep, stride in E.layer_plan(separable):
-        ho = h if stride == 1 else (h + 1) // 2
-        macs += ho * ho * ((6 * cin + cin * cout) if sep else 9 * cin * cout)
-        nbytes += 4 * cout * ho * ho + (4 * cin * h * h if _stem != "initial." else 0)
-        if residual and "Layer 2" in _stem:
-            nbytes += 4 * cout * ho * ho
-        h = ho
-    return macs, nbytes
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), ms
 
 
 def main():
@@ -68,31 +37,27 @@ def main():
     enc = E.FrozenEncoder.from_state_dict(sd64, preset="ppo")
     sd32 = {k: v.to("cuda", torch.float32) if v.is_floating_point() else v for k, v in sd64.items()}
     results = []
-    for shape in args.shapes.split(","):
-        n, img = (int(x) for x in shape.split("x"))
+    for n, img in bl.parse_shapes(args.shapes):
         base = make_obs(5, 8, img, dtype=torch.float32).cuda()
         obs = base[torch.arange(n) % 8].contiguous()
-        macs, nbytes = work(img, True, True)
+        macs, nbytes = bl.encoder_work(img, True, True)
         r = dict(n_env=n, img=img, launches_per_call=17, mac_per_env=macs, gflop_per_call=2 * macs * n / 1e9,
                  least_bytes_per_env=nbytes)
-        med, ms = timed(lambda: enc(obs), args.warmup, args.iters)
+        med, ms = bl.timed(lambda: enc(obs), args.warmup, args.iters)
         r["native_ms"], r["native_ms_all"] = med, ms
-        t_flop, t_byte = 2 * macs * n / PEAK_F32, nbytes * n / PEAK_HBM
+        t_flop, t_byte = 2 * macs * n / bl.PEAK_F32, nbytes * n / bl.PEAK_HBM
         r["native_frac_f32_peak"] = t_flop / (med * 1e-3)
         r["native_frac_hbm_peak"] = t_byte / (med * 1e-3)
         if not args.native_only:
             with torch.no_grad():
                 ref = lambda: encode(sd32, obs, "encoder.", True, 2, True)  # noqa: E731
-                tmed, tms = timed(ref, args.warmup, args.iters)
+                tmed, tms = bl.timed(ref, args.warmup, args.iters)
                 diff = float((ref() - enc(obs)).abs().max())
             r["torch_ms"], r["torch_ms_all"], r["speedup"] = tmed, tms, tmed / med
             r["max_abs_diff_vs_torch_f32"] = diff
-        print(json.dumps({k: v for k, v in r.items() if not k.endswith("_all")}), flush=True)
+        bl.emit(r)
         results.append(r)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), warmup=args.warmup, iters=args.iters, results=results), f,
-                      indent=1)
+    bl.write(dict(device=torch.cuda.get_device_name(0), warmup=args.warmup, iters=args.iters, results=results), args.out)
 
 
 if __name__ == "__main__":

@@ -37,6 +37,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import benchlib as bl  # noqa: E402
 from occlusionenv_amd import _native as nat  # noqa: E402
 from occlusionenv_amd import environment, episodes, harness, ppo  # noqa: E402
 from occlusionenv_amd.encoder import FrozenEncoder  # noqa: E402
@@ -128,7 +129,7 @@ def added_cost(lib, N, dev, poll_every):
         ep.advance(lib, nat.EPISODE_RANDOM, 1.0, 0, done, z, z, None, None, noise)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
-    for i in range(200):
+    for i in range(200):  # the step index changes with every launch, so this is not benchlib.sample's loop
         ep.advance(lib, nat.EPISODE_RANDOM, 1.0, i, done, z, z, None, None, noise)
     b.record()
     b.synchronize()
@@ -226,8 +227,7 @@ def main():
                added_cost=cost)
     print(json.dumps(out["b_single_env"]), json.dumps(cost), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
+    bl.write(out, args.out)
     print("wrote", args.out)
 
 

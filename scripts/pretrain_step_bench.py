@@ -16,9 +16,7 @@ medians are compared, the larger min-max spread of the two paths is the margin. 
 events (and, apart, the copies and memsets) of one step under ``torch.profiler``, after the timing.
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
@@ -26,11 +24,9 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-from sep_encoder_train_bench import sample  # noqa: E402
+import benchlib as bl  # noqa: E402
 from tests import train_model as tm  # noqa: E402
-from tests.encoder_model import make_obs  # noqa: E402
 
 FORMS = {"dense": 1, "separable": 2}  # form -> dilation
 
@@ -49,20 +45,6 @@ def step_fn(net, opt, obs, occl, grad):
     return step
 
 
-def count_launches(step):
-    """(kernels, copies and memsets) of one step, from torch.profiler's device events."""
-    from torch.autograd import DeviceType
-    from torch.profiler import ProfilerActivity, profile
-
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        step()
-        torch.cuda.synchronize()
-    device = [e for e in prof.events() if e.device_type == DeviceType.CUDA]
-    other = [e for e in device if e.name.lower().startswith(("memcpy", "memset", "copybuffer", "fillbuffer"))]
-    return len(device) - len(other), len(other)
-
-
 def run_case(form, n, img, warmup, iters, calls):
     from occlusionenv_amd.encoder import FrozenEncoder
     from occlusionenv_amd.fullnet import TrainableFullNetwork
@@ -72,33 +54,15 @@ def run_case(form, n, img, warmup, iters, calls):
     sd32 = tm.joint_state_dict("golden", form == "separable")
     enc = FrozenEncoder.from_state_dict(sd32, preset="ppo", dilation=FORMS[form], residual=True)
     cls = TrainableFullNetwork if form == "dense" else TrainableSeparableFullNetwork
-    base = make_obs(31, 8, img).float()
-    obs = base[torch.arange(n) % 8].cuda()
-    gen = torch.Generator().manual_seed(7)
-    occl = (torch.rand(n, 1, img // 8, img // 8, generator=gen) > 0.5).float().repeat_interleave(8, 2).repeat_interleave(8, 3).cuda()
-    grad = F.normalize(torch.randn(n, 2, generator=gen), dim=1).cuda()
+    obs, occl, grad, _target = (t.cuda() for t in bl.train_inputs(n, img))
     per_key_net, packed_net = cls.from_encoder(enc), cls.from_encoder(enc)
     steps = dict(per_key=step_fn(per_key_net, torch.optim.AdamW(per_key_net.parameters(), lr=1e-3, weight_decay=1e-5), obs, occl, grad),
                  packed=step_fn(packed_net, PackedAdamW(packed_net, lr=1e-3, weight_decay=1e-5), obs, occl, grad))
     first = {k: float(fn().detach()) for k, fn in steps.items()}
-    for _ in range(warmup):
-        for fn in steps.values():
-            sample(fn, calls)
-    ms = {k: [] for k in steps}
-    for _ in range(iters):
-        for k, fn in steps.items():
-            ms[k].append(sample(fn, calls))
+    ms = bl.interleaved(steps, warmup, iters, calls)
     out = dict(form=form, dilation=FORMS[form], n_env=n, img=img, first_loss=first)
-    for k, v in ms.items():
-        out[k + "_ms"], out[k + "_ms_all"], out[k + "_spread_ms"] = statistics.median(v), v, max(v) - min(v)
-        try:
-            out[k + "_kernel_launches"], out[k + "_copies_and_memsets"] = count_launches(steps[k])
-        except Exception as e:  # the trace is evidence, not the product: say what went wrong and keep the timings
-            out[k + "_kernel_launches"], out[k + "_launch_count_error"] = None, repr(e)
-    margin = max(out["per_key_spread_ms"], out["packed_spread_ms"])
-    out.update(margin_ms=margin, speedup=out["per_key_ms"] / out["packed_ms"],
-               packed_faster_by_more_than_margin=bool(out["packed_ms"] + margin < out["per_key_ms"]),
-               packed_slower_by_more_than_margin=bool(out["per_key_ms"] + margin < out["packed_ms"]))
+    out.update(bl.named(bl.compare(ms["packed"], ms["per_key"]), bl.OPTIMIZERS, n="packed", r="per_key"))
+    out.update(bl.launch_counts(steps))
     return out
 
 
@@ -114,19 +78,16 @@ def main():
     assert torch.cuda.is_available(), "pretrain_step_bench needs a GPU"
     cases = []
     for form in args.forms.split(","):
-        for s in args.shapes.split(","):
-            n, img = (int(v) for v in s.split("x"))
+        for n, img in bl.parse_shapes(args.shapes):
             r = run_case(form, n, img, args.warmup, args.iters, args.calls)
-            print(json.dumps({k: v for k, v in r.items() if not k.endswith("_all")}), flush=True)
+            bl.emit(r)
             cases.append(r)
             torch.cuda.empty_cache()
     out = dict(device=torch.cuda.get_device_name(0), warmup=args.warmup, iters=args.iters, calls_per_sample=args.calls,
                what="whole step: zero_grad, forward, Dice + MSE, backward, optimizer step; per_key = torch.optim.AdamW on the "
                     "parameters under the checkpoint's keys, packed = netoptim.PackedAdamW; same build, interleaved samples",
                cases=cases)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+    bl.write(out, args.out)
 
 
 if __name__ == "__main__":

@@ -16,10 +16,8 @@ through the files (``dataset_io.generate`` + ``DeviceDataset.from_directory``), 
 The bar: (e) with the dither is at most 25 % of one iteration of (a), so that generation stays bound by rendering.
 """
 import argparse
-import json
 import os
 import shutil
-import statistics
 import sys
 import tempfile
 import time
@@ -28,7 +26,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+import benchlib as bl  # noqa: E402
 
 BAR = 0.25
 
@@ -47,7 +46,6 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "resident_gen_bench needs a GPU"
     from bench import build_env
-    from sep_encoder_train_bench import sample
 
     from occlusionenv_amd import _native as nat
     from occlusionenv_amd import dataset_io, devdata
@@ -63,21 +61,8 @@ def main():
     venv.reset()
     venv._drain()
     gen = torch.Generator(device=dev).manual_seed(1)
-    state = dict(action=lr * torch.randn(N, 2, device=dev, generator=gen))
-
-    def bare():
-        a = state["action"].clone().requires_grad_(True)
-        obs, rewards, dones, full_state, loss = eng.step(a)
-        rewards.sum().backward()
-        good = ~torch.isnan(a.grad).any(1)
-        fresh = lr * torch.randn(N, 2, device=dev, generator=gen)
-        state["action"] = torch.where(good[:, None], fresh, state["action"])
-        state["obs"], state["fs"] = obs.detach(), full_state.detach()
-
-    for _ in range(args.warmup):
-        sample(bare, args.calls)
-    v = [sample(bare, args.calls) for _ in range(args.iters)]
-    out["a_bare_iteration_ms"], out["a_bare_iteration_ms_all"] = statistics.median(v), v
+    bare, state = bl.generation_loop(eng, lr, gen)
+    out.update(bl.medians(bl.interleaved(dict(a_bare_iteration=bare), args.warmup, args.iters, args.calls)))
     print("(a)", out["a_bare_iteration_ms"], flush=True)
 
     # (e), on the outputs of the last step
@@ -92,15 +77,7 @@ def main():
 
     paths = dict(pack_dither=lambda: pack(0), pack_threshold=lambda: pack(1), put_dither=lambda: ds.put(obs, fs, slots),
                  put_threshold=lambda: ds.put(obs, fs, slots, label="threshold"))
-    for _ in range(args.warmup):
-        for fn in paths.values():
-            sample(fn, args.calls)
-    ms = {k: [] for k in paths}
-    for _ in range(args.iters):
-        for k, fn in paths.items():
-            ms[k].append(sample(fn, args.calls))
-    for k, v in ms.items():
-        out[f"e_{k}_ms"], out[f"e_{k}_ms_all"] = statistics.median(v), v
+    out.update(bl.medians(bl.interleaved(paths, args.warmup, args.iters, args.calls), "e_"))
     out["e_dither_pass_ms"] = out["e_pack_dither_ms"] - out["e_pack_threshold_ms"]
     out["e_point_pass_bytes"] = N * S * S * (5 * 4 + 6)  # the 16-byte full_state pixel counts as its 4 bytes of alpha
     out["e_share_of_a"] = out["e_pack_dither_ms"] / out["a_bare_iteration_ms"]
@@ -110,32 +87,10 @@ def main():
 
     # (b), (c)
     for key, label in (("b_resident_dither", "dither"), ("c_resident_threshold", "threshold")):
-        secs, steps = [], []
-        for it in range(1 + args.iters // 2):
-            count = dict(n=0)
-            real = eng.step
+        def generate(label=label):
+            return devdata.generate_resident(venv, N, num_frames=F, lr=lr, generator=gen, label=label)
 
-            def counted(*a, **kw):
-                count["n"] += 1
-                return real(*a, **kw)
-
-            eng.step = counted
-            try:
-                torch.cuda.synchronize()
-                t = time.perf_counter()
-                ds = devdata.generate_resident(venv, N, num_frames=F, lr=lr, generator=gen, label=label)
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t
-            finally:
-                eng.step = real
-            del ds
-            if it:  # the first call warms up
-                secs.append(dt)
-                steps.append(count["n"])
-        k = secs.index(statistics.median_low(secs))
-        out[f"{key}_s"], out[f"{key}_s_all"], out[f"{key}_engine_steps"] = secs[k], secs, steps[k]
-        out[f"{key}_ms_per_step"] = secs[k] / steps[k] * 1e3
-        out[f"{key}_frames_per_s"] = N * F / secs[k]
+        out.update(bl.timed_generation(eng, key, generate, args.iters, N * F))
         print(f"({key[0]})", out[f"{key}_ms_per_step"], out[f"{key}_frames_per_s"], flush=True)
 
     # (d)
@@ -157,10 +112,8 @@ def main():
         out["d_files_frames_per_s"] = N * F / (out["d_files_generate_s"] + out["d_files_load_s"])
         out["b_over_d"] = out["b_resident_dither_frames_per_s"] / out["d_files_frames_per_s"]
         print("(d)", out["d_files_load_s"], out["d_files_frames_per_s"], flush=True)
-    print(json.dumps({k: v for k, v in out.items() if not k.endswith("_all")}), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+    bl.emit(out)
+    bl.write(out, args.out)
 
 
 if __name__ == "__main__":

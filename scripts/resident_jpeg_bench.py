@@ -25,7 +25,6 @@ The bar: everything between the engine's step and the store is at most 25 % of o
 """
 import argparse
 import io
-import json
 import os
 import statistics
 import sys
@@ -36,7 +35,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+import benchlib as bl  # noqa: E402
 
 BAR = 0.25
 QUALITY = 95
@@ -45,7 +45,6 @@ QUALITY = 95
 def measure(args, N, R, S):
     from bench import build_env
     from PIL import Image
-    from sep_encoder_train_bench import sample
 
     from occlusionenv_amd import _native as nat
     from occlusionenv_amd import devdata
@@ -60,21 +59,8 @@ def measure(args, N, R, S):
     venv.reset()
     venv._drain()
     gen = torch.Generator(device=dev).manual_seed(1)
-    state = dict(action=lr * torch.randn(N, 2, device=dev, generator=gen))
-
-    def bare():
-        a = state["action"].clone().requires_grad_(True)
-        obs, rewards, dones, full_state, loss = eng.step(a)
-        rewards.sum().backward()
-        good = ~torch.isnan(a.grad).any(1)
-        fresh = lr * torch.randn(N, 2, device=dev, generator=gen)
-        state["action"] = torch.where(good[:, None], fresh, state["action"])
-        state["obs"], state["fs"] = obs.detach(), full_state.detach()
-
-    for _ in range(args.warmup):
-        sample(bare, args.calls)
-    v = [sample(bare, args.calls) for _ in range(args.iters)]
-    out["a_bare_iteration_ms"], out["a_bare_iteration_ms_all"] = statistics.median(v), v
+    bare, state = bl.generation_loop(eng, lr, gen)
+    out.update(bl.medians(bl.interleaved(dict(a_bare_iteration=bare), args.warmup, args.iters, args.calls)))
     print("(a)", N, R, out["a_bare_iteration_ms"], flush=True)
 
     # (d), on the outputs of the last step
@@ -108,15 +94,7 @@ def measure(args, N, R, S):
 
         paths["pack_jpeg_resize"] = all_three
     pack()
-    for _ in range(args.warmup):
-        for fn in paths.values():
-            sample(fn, args.calls)
-    ms = {k: [] for k in paths}
-    for _ in range(args.iters):
-        for k, fn in paths.items():
-            ms[k].append(sample(fn, args.calls))
-    for k, v in ms.items():
-        out[f"{k}_ms"], out[f"{k}_ms_all"] = statistics.median(v), v
+    out.update(bl.medians(bl.interleaved(paths, args.warmup, args.iters, args.calls)))
     a = out["a_bare_iteration_ms"]
     out["pack_share_of_a"], out["d_jpeg_share_of_a"] = out["pack_ms"] / a, out["d_jpeg_ms"] / a
     out["pack_jpeg_share_of_a"] = out["pack_jpeg_ms"] / a
@@ -152,36 +130,15 @@ def measure(args, N, R, S):
 
     # (b), (c)
     for key, q in (("b_resident", None), ("c_resident_jpeg", QUALITY)):
-        secs, steps = [], []
-        for it in range(1 + args.iters // 2):
-            count = dict(n=0)
-            real = eng.step
+        def generate(q=q):
+            ds = devdata.generate_resident(venv, N, num_frames=F, lr=lr, generator=gen, size=None if R == S else S, jpeg=q)
+            assert ds.size == S
+            return ds
 
-            def counted(*a, **kw):
-                count["n"] += 1
-                return real(*a, **kw)
-
-            eng.step = counted
-            try:
-                torch.cuda.synchronize()
-                t = time.perf_counter()
-                ds = devdata.generate_resident(venv, N, num_frames=F, lr=lr, generator=gen, size=None if R == S else S, jpeg=q)
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t
-            finally:
-                eng.step = real
-            assert ds.size == S and len(ds) == N * F
-            del ds
-            if it:  # the first call warms up
-                secs.append(dt)
-                steps.append(count["n"])
-        k = secs.index(statistics.median_low(secs))
-        out[f"{key}_s"], out[f"{key}_s_all"], out[f"{key}_engine_steps"] = secs[k], secs, steps[k]
-        out[f"{key}_ms_per_step"] = secs[k] / steps[k] * 1e3
-        out[f"{key}_frames_per_s"] = N * F / secs[k]
+        out.update(bl.timed_generation(eng, key, generate, args.iters, N * F))
         print(key, out[f"{key}_ms_per_step"], out[f"{key}_frames_per_s"], flush=True)
     out["c_minus_b_ms_per_step"] = out["c_resident_jpeg_ms_per_step"] - out["b_resident_ms_per_step"]
-    del venv, eng
+    del venv, eng, bare, state
     torch.cuda.empty_cache()
     return out
 
@@ -206,10 +163,8 @@ def main():
         N, R, S = (int(x) for x in shape.split(":"))
         out["shapes"].append(measure(args, N, R, S))
     for sh in out["shapes"]:
-        print(json.dumps({k: v for k, v in sh.items() if not k.endswith("_all")}), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+        bl.emit(sh)
+    bl.write(out, args.out)
 
 
 if __name__ == "__main__":

@@ -20,10 +20,8 @@ through the files (``dataset_io.generate`` at 512 + ``DeviceDataset.from_directo
 The bar: (c) is at most 25 % of one iteration of (a), so that generation stays bound by rendering.
 """
 import argparse
-import json
 import os
 import shutil
-import statistics
 import sys
 import tempfile
 import time
@@ -32,7 +30,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+import benchlib as bl  # noqa: E402
 
 BAR = 0.25
 
@@ -52,7 +51,6 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "resident_resize_bench needs a GPU"
     from bench import build_env
-    from sep_encoder_train_bench import sample
 
     from occlusionenv_amd import _native as nat
     from occlusionenv_amd import dataset_io, devdata
@@ -68,21 +66,8 @@ def main():
     venv.reset()
     venv._drain()
     gen = torch.Generator(device=dev).manual_seed(1)
-    state = dict(action=lr * torch.randn(N, 2, device=dev, generator=gen))
-
-    def bare():
-        a = state["action"].clone().requires_grad_(True)
-        obs, rewards, dones, full_state, loss = eng.step(a)
-        rewards.sum().backward()
-        good = ~torch.isnan(a.grad).any(1)
-        fresh = lr * torch.randn(N, 2, device=dev, generator=gen)
-        state["action"] = torch.where(good[:, None], fresh, state["action"])
-        state["obs"], state["fs"] = obs.detach(), full_state.detach()
-
-    for _ in range(args.warmup):
-        sample(bare, args.calls)
-    v = [sample(bare, args.calls) for _ in range(args.iters)]
-    out["a_bare_iteration_ms"], out["a_bare_iteration_ms_all"] = statistics.median(v), v
+    bare, state = bl.generation_loop(eng, lr, gen)
+    out.update(bl.medians(bl.interleaved(dict(a_bare_iteration=bare), args.warmup, args.iters, args.calls)))
     print("(a)", out["a_bare_iteration_ms"], flush=True)
 
     # (c), (d), on the outputs of the last step
@@ -105,15 +90,7 @@ def main():
         resize()
 
     paths = dict(c_pack_resize=both, d_resize=resize, pack=pack, put_resize=lambda: ds.put(obs, fs, slots, resize=True))
-    for _ in range(args.warmup):
-        for fn in paths.values():
-            sample(fn, args.calls)
-    ms = {k: [] for k in paths}
-    for _ in range(args.iters):
-        for k, fn in paths.items():
-            ms[k].append(sample(fn, args.calls))
-    for k, v in ms.items():
-        out[f"{k}_ms"], out[f"{k}_ms_all"] = statistics.median(v), v
+    out.update(bl.medians(bl.interleaved(paths, args.warmup, args.iters, args.calls)))
     out["c_share_of_a"] = out["c_pack_resize_ms"] / out["a_bare_iteration_ms"]
     out["c_under_bar"] = bool(out["c_share_of_a"] <= BAR)
     out["d_traffic_estimate_bytes"] = N * 6 * (R * R + S * S)
@@ -123,33 +100,12 @@ def main():
     del ds, staged
 
     # (b)
-    secs, steps = [], []
-    for it in range(1 + args.iters // 2):
-        count = dict(n=0)
-        real = eng.step
+    def generate():
+        ds = devdata.generate_resident(venv, N, num_frames=F, lr=lr, generator=gen, size=S)
+        assert ds.size == S
+        return ds
 
-        def counted(*a, **kw):
-            count["n"] += 1
-            return real(*a, **kw)
-
-        eng.step = counted
-        try:
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            ds = devdata.generate_resident(venv, N, num_frames=F, lr=lr, generator=gen, size=S)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t
-        finally:
-            eng.step = real
-        assert ds.size == S and len(ds) == N * F
-        del ds
-        if it:  # the first call warms up
-            secs.append(dt)
-            steps.append(count["n"])
-    k = secs.index(statistics.median_low(secs))
-    out["b_resident_s"], out["b_resident_s_all"], out["b_resident_engine_steps"] = secs[k], secs, steps[k]
-    out["b_resident_ms_per_step"] = secs[k] / steps[k] * 1e3
-    out["b_resident_frames_per_s"] = N * F / secs[k]
+    out.update(bl.timed_generation(eng, "b_resident", generate, args.iters, N * F))
     print("(b)", out["b_resident_ms_per_step"], out["b_resident_frames_per_s"], flush=True)
 
     # (e)
@@ -171,10 +127,8 @@ def main():
         out["e_files_frames_per_s"] = N * F / (out["e_files_generate_s"] + out["e_files_load_s"])
         out["b_over_e"] = out["b_resident_frames_per_s"] / out["e_files_frames_per_s"]
         print("(e)", out["e_files_load_s"], out["e_files_frames_per_s"], flush=True)
-    print(json.dumps({k: v for k, v in out.items() if not k.endswith("_all")}), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+    bl.emit(out)
+    bl.write(out, args.out)
 
 
 if __name__ == "__main__":

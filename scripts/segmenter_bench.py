@@ -22,12 +22,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import benchlib as bl  # noqa: E402
 from occlusionenv_amd import encoder as E  # noqa: E402
 from tests.encoder_model import make_obs  # noqa: E402
 from tests.segmenter_model import full_forward, golden_seg_state_dict  # noqa: E402
-from encoder_bench import PEAK_F32, PEAK_HBM, timed, work as encoder_work  # noqa: E402
 
 LEVEL0_BW = 2.0e12  # what the level-0 encoder kernels reach: the yardstick of the decoder's added time
 
@@ -95,39 +94,35 @@ def main():
     enc = E.FrozenEncoder.from_state_dict(sd64, preset="ppo")
     sd32 = {k: v.to("cuda", torch.float32) if v.is_floating_point() else v for k, v in sd64.items()}
     results = []
-    for shape in args.shapes.split(","):
-        n, img = (int(x) for x in shape.split("x"))
+    for n, img in bl.parse_shapes(args.shapes):
         base = make_obs(5, 8, img, dtype=torch.float32).cuda()
         obs = base[torch.arange(n) % 8].contiguous()
-        emacs, ebytes = encoder_work(img, True, True)
+        emacs, ebytes = bl.encoder_work(img, True, True)
         ebytes += 4 * 256 * (img // 32) ** 2  # the last down output is stored as well
         dmacs, dbytes, levels = decoder_work(img)
         r = dict(n_env=n, img=img, launches_per_call=22, decoder_launches=5, decoder_mac_per_env=dmacs,
                  decoder_least_bytes_per_env=dbytes, decoder_levels=[dict(mac_per_env=m, least_bytes_per_env=b) for m, b in levels],
                  mac_per_env=emacs + dmacs, least_bytes_per_env=ebytes + dbytes, gflop_per_call=2 * (emacs + dmacs) * n / 1e9)
-        med, ms = timed(lambda: enc.forward_full(obs), args.warmup, args.iters)
-        emed, ems = timed(lambda: enc(obs), args.warmup, args.iters)
+        med, ms = bl.timed(lambda: enc.forward_full(obs), args.warmup, args.iters)
+        emed, ems = bl.timed(lambda: enc(obs), args.warmup, args.iters)
         r["native_ms"], r["native_ms_all"] = med, ms
         r["encoder_only_ms"], r["encoder_only_ms_all"] = emed, ems
         r["decoder_added_ms"] = med - emed
         r["decoder_least_traffic_ms_at_2TBs"] = dbytes * n / LEVEL0_BW * 1e3
-        r["native_frac_f32_peak"] = 2 * (emacs + dmacs) * n / PEAK_F32 / (med * 1e-3)
-        r["native_frac_hbm_peak"] = (ebytes + dbytes) * n / PEAK_HBM / (med * 1e-3)
+        r["native_frac_f32_peak"] = 2 * (emacs + dmacs) * n / bl.PEAK_F32 / (med * 1e-3)
+        r["native_frac_hbm_peak"] = (ebytes + dbytes) * n / bl.PEAK_HBM / (med * 1e-3)
         if not args.native_only:
             with torch.no_grad():
                 ref = lambda: full_forward(sd32, obs, "ppo")  # noqa: E731
-                tmed, tms = timed(ref, args.warmup, args.iters)
+                tmed, tms = bl.timed(ref, args.warmup, args.iters)
                 want, got = ref(), enc.forward_full(obs)
                 diff = max(float((want["prob"] - got[1]).abs().max()), float((want["pooled"] - got[0]).abs().max()))
             margin = max(max(ms) - min(ms), max(tms) - min(tms))
             r.update(torch_ms=tmed, torch_ms_all=tms, speedup=tmed / med, margin_ms=margin, not_slower=bool(med <= tmed + margin),
                      max_abs_diff_vs_torch_f32=diff)
-        print(json.dumps({k: v for k, v in r.items() if not k.endswith("_all")}), flush=True)
+        bl.emit(r)
         results.append(r)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), warmup=args.warmup, iters=args.iters, results=results), f,
-                      indent=1)
+    bl.write(dict(device=torch.cuda.get_device_name(0), warmup=args.warmup, iters=args.iters, results=results), args.out)
 
 
 if __name__ == "__main__":
