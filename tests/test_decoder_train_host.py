@@ -1,5 +1,7 @@
 """Host-side checks of the decoder training path (csrc/occ_decoder_bwd.hpp, occlusionenv_amd/seghead.py): the workspace
-query covers what the backward needs, and the mapping between the packed gradient and the parameters is right.  The
+query covers what the backward needs, the mapping between the packed gradient and the parameters is right, and the f64
+model and the workspace layout that the GPU tests judge by (tests/train_model.py with the encoder frozen,
+tests/train_layout.py) are the inference model's and the library's.  The
 argument contract of the three entry points is checked from the table of tests/train_abi.py by
 tests/test_train_abi_host.py.  No GPU."""
 import ctypes as C
@@ -143,6 +145,80 @@ def test_split_model_on_the_table_of_known_shapes():
     for img, n in ((32, 1), (96, 65), (256, 128), (512, 64)):
         for p in m.dw_plans(img, n):
             assert p["slices"] * p["grid_y"] <= m.DW_BLOCKS and (p["slices"] - 1) * p["tps"] < p["total_tiles"] <= p["slices"] * p["tps"]
+
+
+def _frozen_hosts():
+    """(preset, S, N, the state dict, obs, tests/train_model.HostModel of the decoder over the frozen encoder) per case."""
+    import numpy as np
+
+    from tests import train_model as tm
+    from tests.encoder_model import make_obs
+    from tests.segmenter_model import golden_seg_state_dict
+
+    g = np.load(tm.GOLDEN)
+    for preset in ("ppo", "segmenter"):
+        sd = {k: (v.float().double() if v.is_floating_point() else v) for k, v in golden_seg_state_dict(g, preset).items()}
+        for img, n in ((32, 1), (64, 2)):
+            obs = make_obs(4000 + img + n, n, img).float().double()
+            yield preset, img, n, sd, obs, tm.HostModel(sd, tm.frozen_net(preset), obs)
+
+
+def test_frozen_encoder_model_is_the_segmenter_model():
+    """Without gates the host model of the decoder path (tests/train_model.py, ``frozen_encoder``) is tests/segmenter_model.py:
+    decode on encode_full, the classifier, the sigmoid, and the mean of the last down output.  The separable encoder's
+    depthwise pair is the same function in another rounding (the tolerances of tests/test_sep_fullnet_train_host.py)."""
+    from tests import train_model as tm
+    from tests.segmenter_model import full_forward
+
+    for preset, img, n, sd, obs, host in _frozen_hosts():
+        assert tm.frozen_net(preset).separable == ("encoder.initial.conv.0.weight" in sd)
+        assert len(host.params) == 22 and list(host.params) == tm.dec_keys(host.net)
+        with torch.no_grad():
+            want = full_forward(sd, obs, preset)
+            us = []
+            pooled, prob, _pred = host.forward(None, us)
+        assert len(us) == 5 and prob.shape == (n, 1, img, img) and pooled.shape == (n, 256)
+        assert torch.allclose(prob, want["prob"], rtol=1e-12, atol=1e-13), (preset, img, n)
+        assert torch.allclose(pooled, want["pooled"], rtol=1e-12, atol=1e-13), (preset, img, n)
+        assert torch.allclose(host.logit()[1].detach(), want["logit"], rtol=1e-12, atol=1e-13), (preset, img, n)
+
+
+def test_frozen_encoder_model_with_its_own_gates():
+    """``u * (u > 0)`` in place of ``relu(u)`` on the decoder's five levels: the same 22 gradients."""
+    for preset, img, n, _sd, _obs, host in _frozen_hosts():
+        up = torch.randn(n, 1, img, img, generator=torch.Generator().manual_seed(img + n), dtype=torch.float64)
+        us = []
+        want = host.grads((host.forward(None, us)[1] * up).sum())
+        got = host.grads((host.forward([(u > 0).double() for u in us])[1] * up).sum())
+        assert len(want) == 22
+        for k, w in want.items():
+            assert float(w.abs().max()) > 0.0
+            assert torch.allclose(got[k], w, rtol=1e-11, atol=1e-13 * float(w.abs().max())), (preset, img, n, k)
+
+
+def test_layout_of_the_decoder_only_workspace():
+    """tests/train_layout.py against the library's queries: the inference decoder's workspace, behind it y_j | r_j per level
+    (include/occlusionenv_amd.h), and the whole."""
+    from tests import decoder_split_model as m
+    from tests import train_layout as tl
+    from tests import train_model as tm
+
+    lib = nat.load()
+    net = tm.frozen_net("ppo")
+    for img, n in ((32, 1), (64, 3), (96, 2), (96, 65), (64, 130), (256, 7)):
+        seg = C.c_size_t()
+        assert lib.occ_segment_workspace_query(C.byref(_cfg(img)), n, C.byref(seg)) == 0
+        assert tl.segment_ws_bytes(img, n) == int(seg.value)
+        assert (tl.ws_bytes(net, img, n), tl.scratch_bytes(net, img, n)) == _query(lib, img, n)
+        views, off = tl.relu_views(img, n, frozen_encoder=True), int(seg.value)
+        assert len(views) == 5
+        for j, view in enumerate(views):  # y_j | r_j, each (n, 128 >> j, S/16 << j, S/16 << j) f32 rounded up to 256 bytes
+            c, side = 128 >> j, (img // 16) << j
+            size = (4 * n * c * side * side + 255) // 256 * 256
+            assert view == (off + size, c, side)
+            off += 2 * size
+        (lo, hi), = tl.only_written(net, img, n)
+        assert lo == off + m.align(4 * n * img * img) and hi == tl.ws_bytes(net, img, n)  # prob, then g0 | g1 to the end
 
 
 def test_split_cases_reach_the_tile_loop():

@@ -35,12 +35,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import train_gpu_suite as suite
 from tests import train_layout as tl
 from tests import train_model as m
-from tests.train_utils import GUARD
 from tests.train_utils import dice64 as _dice64
 from tests.train_utils import grads as _grads
 from tests.train_utils import guarded as _guarded
+from tests.train_utils import guards_intact
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +49,8 @@ TOL = m.TOL
 CASES, IDS = m.BN_CASES, m.BN_IDS
 GRAD_CASES, GRAD_IDS = m.BN_GRAD_CASES, m.BN_IDS[:len(m.BN_GRAD_CASES)]
 WORST = {}  # measured worst relative error per parameter kind (printed with -s)
+# what the shared bodies of tests/train_gpu_suite.py are given; this module keeps its own ``runs`` (batch_stats, OBS_SEEDS, bn_stats)
+FORM = suite.Form(model=m.bn_net, label=str, gate_label=lambda case: "", tol=TOL, nonzero_scale=True, band_cap=m.BAND_CAP, e32=m.e32)
 
 
 def _net_class(form):
@@ -106,21 +109,6 @@ def _close(got, want, what):
     assert got.shape == want.shape and err <= TOL, (what, err)
 
 
-def _check_grads(what, case, got, want):
-    e32, net = m.e32(case), m.bn_net(case)
-    for k, w in want.items():
-        scale = float(w.abs().max())
-        assert scale > 0.0, (what, k, "the oracle's gradient is all zero")
-        err = float((got[k].double().cpu() - w).abs().max()) / scale
-        WORST[m.kind(net, k)] = max(WORST.get(m.kind(net, k), 0.0), err)
-        print(f"{what} {k}: max|want| {scale:.3g}, relative error {err:.3g}, e32 {e32.get(k, 0.0):.3g}")
-    for k, w in want.items():
-        assert got[k].shape == w.shape and got[k].dtype == torch.float32
-        bar = m.bar(case, k) if k in e32 else TOL  # the head's two tensors sit above the pooled feature: the plain bar
-        assert float((got[k].double().cpu() - w).abs().max()) <= bar * float(w.abs().max()), (what, k, bar)
-    print("worst so far:", {k: f"{v:.3g}" for k, v in sorted(WORST.items())})
-
-
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_forward_against_the_f64_model(runs, case):
     r = runs(case)
@@ -135,24 +123,9 @@ def test_forward_against_the_f64_model(runs, case):
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_kept_relu_and_gates(runs, case):
-    r = runs(case)
     us = m.plain_f64(case)[2]
     assert len(us) == 21
-    total, worst_band, worst_err = 0, 0.0, 0.0
-    for i, (u64, got) in enumerate(zip(us, r["kept"])):
-        assert got.shape == u64.shape
-        r64 = torch.relu(u64)
-        err = float((got.double() - r64).abs().max()) / max(1.0, float(r64.abs().max()))
-        band = u64.abs() <= TOL * max(1.0, float(u64.abs().max()))
-        share = float(band.double().mean())
-        differ = (got > 0) != (u64 > 0)
-        total += int(differ.sum())
-        worst_band, worst_err = max(worst_band, share), max(worst_err, err)
-        print(f"layer {i}: relu error {err:.3g}, band share {share:.3g}, gates differing {int(differ.sum())}")
-        assert err <= TOL, (i, err)
-        assert share <= m.BAND_CAP, (i, share)
-        assert not bool((differ & ~band).any()), (i, int((differ & ~band).sum()))
-    print(f"{case}: relu error {worst_err:.3g}, {total} gates differ from the f64 model's, worst band share {worst_band:.3g}")
+    suite.kept_relu_and_gates(FORM, runs(case), case, us)
 
 
 @pytest.mark.parametrize("case", GRAD_CASES, ids=GRAD_IDS)
@@ -162,7 +135,7 @@ def test_gradients_against_f64_autograd(runs, case):
     pooled, prob, _pred = host.forward(r["gates"])
     want = host.grads((pooled * r["gf"].double()).sum() + (prob * r["gp"].double()).sum())
     assert len(want) == len(m.enc_keys(m.bn_net(case))) + 22 and set(want) <= set(r["grads"])
-    _check_grads(str(case), case, r["grads"], want)
+    suite.check_grads(FORM, WORST, str(case), case, r["grads"], want)
 
 
 def test_gradients_through_the_real_losses(runs):
@@ -187,7 +160,7 @@ def test_gradients_through_the_real_losses(runs):
     want = host.grads(loss64, head=True)
     assert len(want) == len(m.enc_keys(m.bn_net(case))) + 22 + 2
     assert abs(float(loss.detach()) - float(loss64.detach())) <= TOL * max(1.0, abs(float(loss64.detach())))
-    _check_grads(f"dice+mse {case}", case, got, want)
+    suite.check_grads(FORM, WORST, f"dice+mse {case}", case, got, want)
 
 
 @pytest.mark.parametrize("case", [GRAD_CASES[0], GRAD_CASES[1]], ids=GRAD_IDS[:2])
@@ -278,21 +251,10 @@ def test_nothing_outside_the_reported_sizes(runs, case):
     assert torch.equal(mid["stats"].view(torch.float32).cpu(), r["stats"])
     assert torch.equal(mid["feats"].view(torch.float32).view(n, FEATURES).cpu(), r["feats"])
     assert torch.equal(mid["prob"].view(torch.float32).view(n, 1, img, img).cpu(), r["prob"])
-    at = 0
-    for part, key in zip(net.parts, ("grad_enc", "grad_dec")):
-        layers, tail = part.unpack(mid[key].view(torch.float32).cpu())
-        for stem, leaves, layer in zip(part.stems, part.layer_leaves(), layers):
-            for leaf, t in zip(leaves, layer):  # d gamma / d beta sit in the scale / shift slots as they are
-                assert torch.equal(t, r["grads"][stem + leaf]), stem + leaf
-                at += 1
-        for k, t in zip(part.tail, tail):
-            assert torch.equal(t, r["grads"][k]), k
-            at += 1
-    assert at == len(m.enc_keys(m.bn_net(case))) + 22
-    for k, (whole, lo) in bufs.items():
-        assert lo >= GUARD and whole.numel() - (lo + sizes[k]) >= GUARD
-        assert bool((whole[:lo] == 0xA5).all()), f"bytes in front of {k} were written"
-        assert bool((whole[lo + sizes[k]:] == 0xA5).all()), f"bytes behind {k} were written"
+    packed_grads = [mid[key].view(torch.float32) for key in ("grad_enc", "grad_dec")]
+    # d gamma / d beta sit in the scale / shift slots as they are
+    assert suite.packed_gradients_are_the_modules(net, packed_grads, r["grads"], folded=False) == len(m.enc_keys(m.bn_net(case))) + 22
+    guards_intact(bufs, sizes)
 
 
 def test_batch_coupling_and_the_one_value_limit(nets, runs):

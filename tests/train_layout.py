@@ -101,6 +101,8 @@ def scratch_bytes(net, img, n):
     """max over the encoder's layers of (activation partials, weight-gradient partials, a separable layer's G partials: nine
     f64 sums per (input channel, env, chunk), not split further: one block per chunk), rounded up to 256; a joint net: the
     larger of that and the decoder's.  Batch statistics need no more."""
+    if net.frozen_encoder:  # the decoder's alone
+        return dsm.scratch_bytes(img, n)
     need = 0
     for p in (dpw_plans if net.separable else dw_plans)(img, n):
         ch = chunks(p["ho"] * p["ho"])
@@ -147,31 +149,60 @@ def extra_ws_bytes(img, n):
     return a(24 * CHANNELS) + a(3 * 256 * 4) + a(part)
 
 
+def segment_ws_bytes(img, n):
+    """The workspace of the inference decoder, what occ_segment_workspace_query reports: two level-0 activation buffers |
+    pool partials | the five skips | last."""
+    a = dsm.align
+    skips = sum(a(4 * n * (8 << lv) * (img >> lv) ** 2) for lv in range(LEVELS))
+    return 2 * a(4 * n * 8 * img * img) + a(4 * n * _tiles(img >> LEVELS) * 256) + skips + a(4 * n * 256 * (img >> LEVELS) ** 2)
+
+
 def ws_bytes(net, img, n):
     """The encoder's; a joint net: + last | y_j, r_j per decoder level | prob | dlast | dskip of levels 1..4 (the sizes of
-    y_3 .. y_0); with batch statistics: + extra_ws_bytes."""
+    y_3 .. y_0); with batch statistics: + extra_ws_bytes.  The decoder over a frozen encoder: the inference decoder's, then
+    y_j, r_j per level | prob | g0 | g1 (the sizes of y_4 and y_3)."""
+    a = dsm.align
+    lvl = dsm.level_bytes(img, n)
+    if net.frozen_encoder:
+        return segment_ws_bytes(img, n) + 2 * sum(lvl) + a(4 * n * img * img) + lvl[4] + lvl[3]
     total = encoder_ws_bytes(img, n)
     if net.joint:
-        a = dsm.align
-        lvl = dsm.level_bytes(img, n)
         last = a(4 * n * 256 * (img // 32) ** 2)
         total += last + 2 * sum(lvl) + a(4 * n * img * img) + last + sum(lvl[:4])
     return total + (extra_ws_bytes(img, n) if net.batch_stats else 0)
 
 
-def relu_views(img, n):
+def only_written(net, img, n):
+    """[(from, to)]: the bytes of the workspace that the backward writes before it reads them, so that whatever they held
+    must not matter: g0 | g1 | g2 at the end of the encoder's workspace and, behind a joint net's, dlast | dskip at the end
+    of the whole; over a frozen encoder g0 | g1 at the end."""
+    lvl, end = dsm.level_bytes(img, n), ws_bytes(net, img, n)
+    if net.frozen_encoder:
+        return [(end - lvl[4] - lvl[3], end)]
+    e_end = encoder_ws_bytes(img, n)
+    out = [(e_end - 3 * dsm.align(4 * n * 8 * img * img), e_end)]
+    if net.joint:
+        out.append((end - dsm.align(4 * n * 256 * (img // 32) ** 2) - sum(lvl[:4]), end))
+    return out
+
+
+def relu_views(img, n, frozen_encoder=False):
     """[(byte offset, channels, side)] x 21: where the workspace keeps r = relu(u) of the 16 encoder layers in packed order
-    and, in a joint workspace, of the decoder's five levels (the layout of include/occlusionenv_amd.h)."""
+    and, in a joint workspace, of the decoder's five levels (the layout of include/occlusionenv_amd.h).  ``frozen_encoder``:
+    the five levels of the decoder-only workspace, which keeps them behind the inference decoder's part."""
     a = dsm.align
-    hs = sides(img)
-    off = a(4 * n * 4 * img * img)  # obs
-    out = [(off, 8, img)]
-    off += a(4 * n * 8 * img * img)
-    for lv in range(LEVELS):
-        c, act = 8 << lv, a(4 * n * (8 << lv) * hs[lv] ** 2)
-        out += [(off + act, c, hs[lv]), (off + 3 * act, c, hs[lv]), (off + 5 * act, 2 * c, hs[lv + 1])]  # a r1 b r2 cc rd
-        off += 5 * act + a(4 * n * 2 * c * hs[lv + 1] ** 2)
-    off = encoder_ws_bytes(img, n) + a(4 * n * 256 * (img // 32) ** 2)  # past the encoder's part and last
+    if frozen_encoder:
+        out, off = [], segment_ws_bytes(img, n)
+    else:
+        hs = sides(img)
+        off = a(4 * n * 4 * img * img)  # obs
+        out = [(off, 8, img)]
+        off += a(4 * n * 8 * img * img)
+        for lv in range(LEVELS):
+            c, act = 8 << lv, a(4 * n * (8 << lv) * hs[lv] ** 2)
+            out += [(off + act, c, hs[lv]), (off + 3 * act, c, hs[lv]), (off + 5 * act, 2 * c, hs[lv + 1])]  # a r1 b r2 cc rd
+            off += 5 * act + a(4 * n * 2 * c * hs[lv + 1] ** 2)
+        off = encoder_ws_bytes(img, n) + a(4 * n * 256 * (img // 32) ** 2)  # past the encoder's part and last
     for j, size in enumerate(dsm.level_bytes(img, n)):
         out.append((off + size, 128 >> j, (img // 16) << j))  # y_j | r_j
         off += 2 * size
@@ -184,5 +215,6 @@ def kept_relu(net, i):
     has a workspace of its own, and which one is viewed goes by the mode the net is in now."""
     n, img = net._latest
     ws, _scratch = net._train_buffers(n, img, net._bn_mode())
-    off, c, side = relu_views(img, n)[i]
+    frozen_encoder = "feats" in net.RETURNS and "feats" not in net.DIFFERENTIABLE  # it returns the feature and trains nothing behind it
+    off, c, side = relu_views(img, n, frozen_encoder)[i]
     return ws[off:off + 4 * n * c * side * side].view(torch.float32).view(n, c, side, side)

@@ -1,7 +1,6 @@
-"""Helpers shared by the GPU tests of the native training paths: tests/test_gpu_decoder_train.py, tests/test_gpu_bn_train.py
-and, through the shared bodies of tests/train_gpu_suite.py, the dense and separable pairs
-tests/test_gpu_encoder_train.py / test_gpu_sep_encoder_train.py and tests/test_gpu_fullnet_train.py /
-test_gpu_sep_fullnet_train.py."""
+"""Helpers shared by the GPU tests of the native training paths, tests/test_gpu_bn_train.py and the shared bodies of
+tests/train_gpu_suite.py: guarded device buffers and the check of their guards, the f64 Dice and BCE losses, and a
+module's gradients by key."""
 import torch
 
 GUARD = 4096
@@ -13,6 +12,14 @@ def guarded(nbytes):
     whole = torch.full((nbytes + 2 * GUARD + 256,), 0xA5, dtype=torch.uint8, device="cuda")
     lo = GUARD + (-(whole.data_ptr() + GUARD)) % 256
     return whole, lo
+
+
+def guards_intact(bufs, sizes):
+    """``bufs`` = {name: guarded(sizes[name])} after the native calls: no byte in front of a window or behind it was written."""
+    for k, (whole, lo) in bufs.items():
+        assert lo >= GUARD and whole.numel() - (lo + sizes[k]) >= GUARD
+        assert bool((whole[:lo] == 0xA5).all()), f"bytes in front of {k} were written"
+        assert bool((whole[lo + sizes[k]:] == 0xA5).all()), f"bytes behind {k} were written"
 
 
 def dice64(p, t):
