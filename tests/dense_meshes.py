@@ -8,6 +8,8 @@ stored, every mesh is built in code from fixed parameters and seeds.
   counts straddle the front-to-back sort's thresholds (occ_setup.hpp: kSortMin = 4 096 <= nrec <= kSortCap = 8 192).
 * ``vertex_sheet(nV)``: a sheet with exactly nV vertices (4 096 / 4 097: either side of the setup kernel's LDS vertex cap).
 * ``reorder``: the same mesh with its faces reversed (roughly back to front) or in a seeded random order.
+* ``needles(kind)``: visible needle triangles with one edge far below kEpsilon in NDC (the -1 sentinel of a record's
+  1 / |edge|^2 slots), the degenerate edge in each of the three slots in turn.
 """
 from __future__ import annotations
 
@@ -119,6 +121,46 @@ def dense_torus():
     return _CACHE["torus"]
 
 
+NEEDLE_KINDS = ("needles01", "needles02", "needles12")
+NEEDLE_COUNT = 320
+NEEDLE_SHORT = 2e-5          # world distance of the two close corners: ~1e-5 NDC at radius 4, |edge|^2 ~ 1e-10 << kEpsilon
+NEEDLE_LENGTH = (0.3, 0.6)   # world distance of the third corner: area (edge function) ~ 3e-6 NDC >> kEpsilon, visible
+
+
+def needles(kind: str):
+    """NEEDLE_COUNT front-facing needle triangles, each with its own three vertices: corners a, b NEEDLE_SHORT apart, the
+    tip c 0.3 ... 0.6 away at right angles to (a, b); centres in a patch half a unit wide, directions all round the
+    clock (pixel centres then fall beyond both ends and beside the flanks of some needle), every needle in a plane
+    z = const of its own (all face +z, no two share a depth).  The kinds are the three rotations of the vertex order -
+    (a, b, c), (b, c, a), (c, a, b) - so that the degenerate edge is (v0, v1), (v0, v2) or (v1, v2): the closest-edge tie
+    order e01, e02, e12 decides which edge the gradient flows through at the tip."""
+    key = ("needles", kind)
+    if key not in _CACHE:
+        rot = {"needles01": (0, 1, 2), "needles02": (1, 2, 0), "needles12": (2, 0, 1)}[kind]
+        rng = np.random.default_rng(1201)  # the same needles for the three kinds
+        n = NEEDLE_COUNT
+        p = rng.uniform(-0.25, 0.25, size=(n, 2))
+        th = (np.arange(n) + rng.uniform(0.0, 1.0, size=n)) * (2.0 * np.pi / n)
+        rng.shuffle(th)
+        L = rng.uniform(*NEEDLE_LENGTH, size=n)
+        z = rng.permutation(n) * (0.1 / n) - 0.05
+        u = np.stack([np.cos(th), np.sin(th)], 1)
+        nrm = np.stack([-u[:, 1], u[:, 0]], 1)  # u turned by +90 degrees
+        m, c = p - 0.5 * L[:, None] * u, p + 0.5 * L[:, None] * u
+        # (a, b, c) counter-clockwise seen from +z (front-facing like the sheets): (b - a) x (c - a) = -nrm x u > 0 for a = m + h nrm
+        a, b = m + 0.5 * NEEDLE_SHORT * nrm, m - 0.5 * NEEDLE_SHORT * nrm
+        tri = np.stack([a, b, c], 1)  # (n, 3, 2)
+        verts = np.concatenate([tri, np.repeat(z[:, None, None], 3, 1)], -1)[:, rot, :].reshape(-1, 3)
+        faces = np.arange(3 * n, dtype=np.int64).reshape(n, 3)
+        _CACHE[key] = (torch.tensor(verts, dtype=torch.float32), torch.tensor(faces, dtype=torch.int64))
+    return _CACHE[key]
+
+
+def needle_short_slot(kind: str) -> int:
+    """Which of a record's three 1 / |edge|^2 slots (R_IL01, R_IL02, R_IL12) holds the degenerate edge of the kind."""
+    return NEEDLE_KINDS.index(kind)
+
+
 def face_order(n_faces: int, order: str) -> np.ndarray:
     """Permutation p of the faces: face k of the reordered mesh is face p[k] of the native one."""
     if order == "native":
@@ -145,6 +187,7 @@ def _kinds():
               "torus_teapots": None,
               # the setup kernel's vertex staging: meshes of 4 096, 4 097 and 122 880 vertices in one pool
               "vstage": lambda: [vertex_sheet(4096), vertex_sheet(4097), dense_torus()]})
+    k.update({kind: (lambda kind=kind: [needles(kind)]) for kind in NEEDLE_KINDS})
     return k
 
 
@@ -162,7 +205,7 @@ def dense_pool_meshes(kind: str):
 
 def dense_layout(kind, n_env, x2):
     """Mesh slot of every object (indices into ``dense_pool_meshes(kind)``) and the object offsets of a dense case.
-    Sheets sit at depths 0 / 1 / 2 in front of the origin, shifted sideways by a tenth of the case's x2 draw (the
+    Sheets and needle patches sit at depths 0 / 1 / 2 in front of the origin, shifted sideways by a tenth of the case's x2 draw (the
     random offsets of the other kinds would push them off screen); the other kinds use make_case's usual offsets."""
     slots = torch.zeros(n_env, 3, dtype=torch.int64)
     if kind == "torus_teapots":  # the torus in one slot of every env, teapots in the others
@@ -171,7 +214,7 @@ def dense_layout(kind, n_env, x2):
     elif kind == "vstage":  # every env holds all three meshes, in a rotating order
         slots = (torch.arange(n_env)[:, None] + torch.arange(3)[None, :]) % 3
     offsets = torch.zeros(n_env, 3, 3)
-    if kind.startswith("sheet") or kind == "vstage":
+    if kind.startswith("sheet") or kind == "vstage" or kind in NEEDLE_KINDS:
         s = 0.1 * x2.clamp(-2.0, 2.0)
         offsets[:, 1, 0], offsets[:, 1, 1], offsets[:, 1, 2] = s, 0.05, 1.0
         offsets[:, 2, 0], offsets[:, 2, 1], offsets[:, 2, 2] = -s, -0.05, 2.0

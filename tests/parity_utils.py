@@ -154,7 +154,7 @@ def oracle_env(case, i, img, shader="flat", faces_per_pixel=100):
 
 
 def run_engine(case, img, n_env=None, faces_per_pixel=100, radius=4.0, pixel_weight=None, render_too=False, shader="flat",
-               cost_order=True, setup_vertex_lds=None):
+               cost_order=True, setup_vertex_lds=None, before_step=None):
     from occlusionenv_amd import _native as nat
     from occlusionenv_amd.engine import OcclusionEngine
 
@@ -169,6 +169,8 @@ def run_engine(case, img, n_env=None, faces_per_pixel=100, radius=4.0, pixel_wei
     obs0, loss0, fs0 = eng.reset_render(None, radius, case["az"][:n], 0.0)
     alphas0 = eng.alphas.clone()
     records0 = snapshot_records(eng)
+    if before_step is not None:  # e.g. move the state (eng.elevation) between the reset render and the step
+        before_step(eng)
     a = case["actions"][:n].to(eng.device).requires_grad_(True)
     obs, reward, done, fs, loss = eng.step(a)
     reward.sum().backward()
@@ -288,7 +290,8 @@ def sliver_depth_bound(fv_face) -> float:
 
 def snapshot_records(eng):
     """The face records the setup kernel left for the LAST render, per (env, object): NDC vertices (n,3,3), original
-    face ids, flags (occ_constants.h: 1 / 2 = first / second half of a z-clipped pair, 4 = z-clipped piece)."""
+    face ids, flags (occ_constants.h: 1 / 2 = first / second half of a z-clipped pair, 4 = z-clipped piece), tangents;
+    ``raw`` = the whole (n, 32) f32 record rows (slot map: occ_constants.h)."""
     torch.cuda.synchronize()
     nrec = eng._ws_tensors["nrec"].cpu().numpy()[: eng.NT * 3]
     rec_off = eng._rec_tensors["rec_off"].cpu().numpy().view(np.int64)
@@ -299,7 +302,8 @@ def snapshot_records(eng):
         r = rec[base * 32: (base + n) * 32].cpu().numpy().reshape(n, 32).copy()
         out.append(dict(fv=torch.from_numpy(r[:, :9].reshape(n, 3, 3).copy()), ids=r[:, 9].view(np.int32).copy(),
                         flags=r[:, 10].view(np.int32).copy(),
-                        tan=r[:, 20:32].reshape(n, 3, 4).copy()))  # per vertex: d x/d el, d y/d el, d x/d az, d y/d az
+                        tan=r[:, 20:32].reshape(n, 3, 4).copy(),  # per vertex: d x/d el, d y/d el, d x/d az, d y/d az
+                        raw=r))
     return out
 
 

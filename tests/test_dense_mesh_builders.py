@@ -56,3 +56,45 @@ def test_sheet_faces_all_front_facing_on_screen_unclipped(kind):
             assert float(area.min()) > 1e-6, (kind, i, phase, o, float(area.min()))
             assert float(fv[..., :2].abs().max()) < 0.9, (kind, i, phase, o)
             assert float(fv[..., 2].min()) > 1.5, (kind, i, phase, o)
+
+
+@pytest.mark.parametrize("kind", D.NEEDLE_KINDS)
+def test_needles_have_one_degenerate_edge_in_the_promised_slot_and_a_visible_area(kind):
+    """In f64 at radius 4, az 0, for the three objects of the needle layout: every face is front-facing with exactly ONE
+    edge of |edge|^2 <= kEpsilon / 4 - the one the kind names - and an area (edge function) of at least 16 kEpsilon; the
+    margins are wide enough that the f32 projection noise TVERT per vertex decides neither.  The three kinds are the
+    same needles with the vertex order rotated."""
+    from oracle import p3d_restate as O
+    from tests.parity_utils import TVERT, make_case
+
+    case = make_case(1, 0, kind, az_range=0.0, device="cpu")
+    assert float(case["az"][0]) == 0.0
+    R, T = O.look_at_view_transform(torch.tensor([4.0], dtype=torch.float64), torch.zeros(1, dtype=torch.float64),
+                                    torch.zeros(1, dtype=torch.float64))
+    slot = D.needle_short_slot(kind)
+    assert (("needles01", "needles02", "needles12")[slot], slot) == (kind, D.NEEDLE_KINDS.index(kind))
+    for o in range(3):
+        v, f = case["pool"].get(int(case["mesh_ids"][0, o]))
+        assert f.shape[0] == D.NEEDLE_COUNT and 200 <= f.shape[0] <= 600
+        fv = O.world_to_ndc(v.double() + case["offsets"][0, o].double(), R[0], T[0])[f].numpy()
+        x, y = fv[..., 0], fv[..., 1]
+        l2 = np.stack([(x[:, b] - x[:, a]) ** 2 + (y[:, b] - y[:, a]) ** 2 for a, b in ((0, 1), (0, 2), (1, 2))], 1)
+        short = l2 <= 1e-8 / 4
+        assert (short.sum(1) == 1).all() and short[:, slot].all(), (kind, o)
+        area = (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0]) - (y[:, 2] - y[:, 0]) * (x[:, 1] - x[:, 0])  # E(v2; v0, v1) > 0: front
+        assert float(area.min()) >= 16 * 1e-8, (kind, o, float(area.min()))
+        # noise: each end of an edge moves by at most TVERT in x and in y -> its length by 2 sqrt 2 TVERT; the area by
+        # TVERT x perimeter (tests/parity_utils.py, TAREA)
+        per = np.sqrt(l2).sum(1)
+        assert ((np.sqrt(l2[:, slot]) + 2 * np.sqrt(2) * TVERT) ** 2 < 1e-8 * 0.5).all()
+        others = np.delete(l2, slot, axis=1)
+        assert ((np.sqrt(others) - 2 * np.sqrt(2) * TVERT) ** 2 > 1e-8 * 1e4).all()
+        assert (area - TVERT * per > 2 * 1e-8).all()
+        assert float(np.abs(fv[..., :2]).max()) < 0.9 and float(fv[..., 2].min()) > 1.5  # on screen, far from the clip plane
+    v0, f0 = D.needles("needles01")
+    v1, _ = D.needles(kind)
+    r = {"needles01": (0, 1, 2), "needles02": (1, 2, 0), "needles12": (2, 0, 1)}[kind]
+    assert torch.equal(v1[f0], v0[f0][:, r, :])
+    # directions all round the clock: every octant holds needles
+    d = (v0[f0][:, 2, :2] - v0[f0][:, 0, :2]).numpy()
+    assert np.bincount((np.floor(np.arctan2(d[:, 1], d[:, 0]) / (np.pi / 4)).astype(int) + 4) % 8, minlength=8).min() >= 20

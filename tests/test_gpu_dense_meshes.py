@@ -349,3 +349,46 @@ def test_sixteen_envs_equal_one_env_bitwise(mesh):
         one = run_engine(sub, 64)
         for k in keys:
             assert torch.equal(big[k][i:i + 1], one[k]), (mesh, i, k)
+
+
+NEEDLE_SEED = 1203
+
+
+@pytest.mark.parametrize("kind", D.NEEDLE_KINDS)
+def test_needles_with_a_degenerate_edge_step_parity(kind, record_property):
+    """Visible faces with one edge of |b - a|^2 ~ 1e-10 << kEpsilon (tests/dense_meshes.py: needles): eval_face takes
+    t = 1 on that edge in the forward pass and 0.5 / kEpsilon for 1 / (l^2 + eps) in the gradient, where the oracle
+    carries the exact rule.  The whole step against the oracle, tolerances and tie budgets unchanged (the action gradient
+    within 1e-4 of the f32 oracle or inside the f64 arbiter's band) - and the records show that the branch ran: the -1
+    sentinel sits in the slot the kind names, and covered pixels have such faces among their candidates."""
+    from oracle import p3d_restate as O
+
+    S, K = 64, 100
+    res = run_parity_case(n_env=2, img=S, seed=NEEDLE_SEED, mesh=kind)
+    print("needles", kind, {k: res[k] for k in ("tie_pixels", "tie_decisions", "covered_pixels", "alpha_maxabs", "grad_rel",
+                                                "grad_arbiter")})
+    check_result(res)
+    got = run_engine(make_case(2, NEEDLE_SEED, kind), S)
+    slot = D.needle_short_slot(kind)
+    n_face = n_sent = 0
+    pix = set()  # (env, y, x) of covered pixels with a sentinel face among the candidates of one of the objects
+    for eo, rec in enumerate(got["records"]):
+        il = rec["raw"][:, 16:19]
+        assert rec["ids"].shape[0] >= 0.9 * D.NEEDLE_COUNT, (kind, eo, "the needles are visible")
+        n_face += il.shape[0]
+        n_sent += int(((il[:, slot] == -1.0) & ((il == -1.0).sum(1) == 1)).sum())
+        sent = (il == -1.0).any(1)
+        alpha = got["alphas"][eo // 3, eo % 3]
+        fv = rec["fv"].float().contiguous()
+        for y, x in torch.nonzero(alpha > 0).tolist():
+            if len(pix) >= 4 * 50:  # four times the threshold is plenty: the rest of the pixels is not walked
+                break
+            c = O.pixel_candidates(fv, S, y, x, O.BLUR_RADIUS, band=0.0)
+            if sent[c["f"][(c["flags"] & 2) != 0]].any():
+                pix.add((eo // 3, y, x))
+    n_pix = len(pix)
+    record_property("sentinel_faces", n_sent)
+    record_property("pixels_with_sentinel_candidates", n_pix)
+    print("needles", kind, "faces", n_face, "sentinel in slot", n_sent, "covered pixels with such a candidate (counted up to 200)", n_pix)
+    assert n_sent >= 0.9 * n_face, (kind, n_sent, n_face)
+    assert n_pix >= 50, (kind, n_pix)
