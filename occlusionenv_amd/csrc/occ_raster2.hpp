@@ -58,7 +58,7 @@
 // OCC_LOG_CAP (include/occlusionenv_amd.h): log entries per wave; must hold a compacted log (64 * OCC_MAX_K) plus the
 // pairs of one batch
 static_assert(OCC_LOG_CAP >= 64 * OCC_MAX_K + 2048 + 64, "OCC_LOG_CAP too small");
-static_assert(OCC_LOG_ENTRY_BYTES == 30, "12 B payload + 8 B (key, tag) + 8 B (key, tag) + 2 B (log index) of the selection's own compacted copy");
+static_assert(OCC_LOG_ENTRY_BYTES == 30, "12 B payload + 8 B (key, tag) + 8 B (key, pixel | log index << 6) of the selection's own compacted copy (+ 2 B no longer used)");
 static_assert(OCC_LOG_CAP % 8 == 0, "the regions of a wave's log stay 16-byte aligned");
 #define OCC_LOG_BYTES ((size_t)OCC_LOG_CAP * OCC_LOG_ENTRY_BYTES)
 
@@ -93,7 +93,6 @@ constexpr int kCopies = 1 << kCopyBits;
 // (Six copies in another format, and final-sweep sub-passes over whole groups of rows: not kept, DESIGN_HISTORY.md H4.)
 constexpr int kAccStride = 65; // accumulator slots per copy: one per pixel, +1 so that the copies of a pixel differ mod 16 (acc_slot)
 
-constexpr uint32_t kNoEntry = 0xFFFFFFFFu;  // tag of a slot past the end of the log (a tag is pixel | face sequence number << 6)
 struct LogPay {  // 12 bytes, moved with one dwordx3 access
     float q, ge, ga;  // 1 - p, g_el, g_az
 };
@@ -102,13 +101,13 @@ struct WaveLog {
     uint2* __restrict__ kt;    // (order-preserving depth key, pixel of the tile 0..63 | face sequence number << 6)
     // What the selection's LATER sweeps read.  Its first sweep (the first histogram pass) copies the entries of
     // the pixels that hold more than K candidates - 63 % of the log of a tile that needs selection on the bench - into
-    // this region, in log order and unchanged, with every entry's index in the log (where its payload is) beside it in
-    // ix2.  The other histogram passes and the final sweep then visit those rows only.
-    // (Index and face number packed into the tag instead: wrong for dense objects, DESIGN_HISTORY.md H4.)
+    // this region, in log order, as (key, pixel | index in the log << 6): the index is where the entry's payload is.
+    // The other histogram passes and the final sweep then visit those rows only, and need nothing but the key, the
+    // pixel and the index - the final sweep picks the accumulator copy by the pixel's arrival index, not by the face
+    // number (which an earlier packing truncated, wrongly for the sub-pass rule of that time: DESIGN_HISTORY.md H4).
     uint2* __restrict__ kt2;
-    uint16_t* __restrict__ ix2;
 };
-static_assert(OCC_LOG_CAP <= 65536, "the compacted copy keeps the log index in sixteen bits");
+static_assert(OCC_LOG_CAP <= 65536, "pixel | log index << 6 fits the tag word of the compacted copy");
 
 // Accumulator slot of pixel pix (= 8 py + px) in copy cpy.  A 16-byte LDS access is served 16 lanes at a time, one per
 // residue of the slot index mod 16: the column is rotated by 3 every second row and the copy stride is 1 mod 16, so that
@@ -211,7 +210,6 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
         lg.pay = reinterpret_cast<LogPay*>(base);
         lg.kt = reinterpret_cast<uint2*>(base + (size_t)OCC_LOG_CAP * 12);
         lg.kt2 = reinterpret_cast<uint2*>(base + (size_t)OCC_LOG_CAP * 20);
-        lg.ix2 = reinterpret_cast<uint16_t*>(base + (size_t)OCC_LOG_CAP * 28);
     }
     ciptr offs = as_const(P.ws.offsets);
     ciptr ord = as_const(reinterpret_cast<const int*>(P.ws.order));  // null: rect order through offs
@@ -365,14 +363,17 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
             const uint2* __restrict__ src = lg.kt;
             int nsrc = nlog;
             bool fmt_b = false;  // the sweeps read the compacted copy (WaveLog.kt2) and its entry format
+            // Slots past the end are loaded from the last entry and never looked at: their users test the slot's index
+            // (in_src).  (A load under `e < nsrc` with a default beside it: where the register allocator wrote the default
+            // AFTER the load into the same registers, every load of a group was followed by s_waitcnt vmcnt(0) - the
+            // four round trips of a group end to end, +4 % on the kernel.)
             auto load_group = [&](const int e0, auto& kt) __attribute__((always_inline)) {
                 constexpr int U = (int)(sizeof(kt) / sizeof(kt[0]));
+                const int elast = max(nsrc - 1, 0);
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int e = e0 + u * 64 + lane;
-                    kt[u] = e < nsrc ? src[e] : make_uint2(0u, kNoEntry);
-                }
+                for (int u = 0; u < U; ++u) kt[u] = src[min(e0 + u * 64 + lane, elast)];
             };
+            auto in_src = [&](const int e0, const int u) __attribute__((always_inline)) -> bool { return e0 + u * 64 + lane < nsrc; };
             constexpr int kGroup = 64 * kSweepU;
             // how the boundary bucket [L, L + 2^sh) of an overflowing pixel is resolved in the final sweep
             enum { kAll = 0, kTies = 1, kList = 2 };
@@ -388,10 +389,10 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
 #pragma unroll
                 for (int i = 0; i < kSelStride; ++i) hist[lane + 64 * i] = 0u;  // the whole array, lane-contiguous
                 wave_lds_sync();
-                auto bump = [&](const uint2 (&kt)[kSweepU]) __attribute__((always_inline)) {
+                auto bump = [&](const int e0, const uint2 (&kt)[kSweepU]) __attribute__((always_inline)) {
 #pragma unroll
                     for (int u = 0; u < kSweepU; ++u) {
-                        if (kt[u].y != kNoEntry) {
+                        if (in_src(e0, u)) {
                             const uint32_t px = kt[u].y & 63u;
                             const uint2 w = s_sel[px];
                             if (w.y < 32u) {
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         // (first pass: every pixel under selection has the SAME window - the tile's - and which pixels those are is a
                         // 64-bit mask: no window look-up in LDS, one dependent round trip less per group of rows)
                         bool ov = false;
-                        if (kt[u].y != kNoEntry) {
+                        if (in_src(e0, u)) {
                             const uint32_t px = kt[u].y & 63u;
                             ov = (((px & 32u) ? ovf_hi : ovf_lo) >> (px & 31u)) & 1u;
                             if (ov) {
@@ -425,8 +426,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         const unsigned long long m = __ballot(ov);
                         if (ov) {
                             const int wpos = n2 + lane_rank(m);
-                            lg.kt2[wpos] = kt[u];
-                            lg.ix2[wpos] = (uint16_t)(e0 + u * 64 + lane);
+                            lg.kt2[wpos] = make_uint2(kt[u].x, (kt[u].y & 63u) | ((uint32_t)(e0 + u * 64 + lane) << 6));
                         }
                         n2 += __popcll(m);
                     }
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
 #pragma unroll
                         for (int gi = 0; gi < kRingG; ++gi) {
                             if (!compact && pass == 0) bump_copy(e0 + gi * kGroup, ring[gi]);
-                            else bump(ring[gi]);
+                            else bump(e0 + gi * kGroup, ring[gi]);
                             load_group(e0 + (kRingG + gi) * kGroup, ring[gi]);
                         }
                     }
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                 LogPay pv[kU];
 #pragma unroll
                 for (int u = 0; u < kU; ++u) {  // decisions in log order (ties are served first come)
-                    if (kt[u].y != kNoEntry) {
+                    if (in_src(e0, u)) {
                         const uint32_t px = kt[u].y & 63u;
                         const uint2 w = s_sel[px];
                         const uint32_t shp = w.y & 255u;
@@ -593,20 +593,15 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                 // payloads have had a group's work to arrive.  Groups are applied in log order, sub-passes as in the evaluation
                 // rounds: the sums come out bit for bit as before.
                 uint2 ring[kRingG][kSweepU];
-                uint32_t ringx[kRingG][kSweepU];  // the entries' indices in the log (their payloads' places)
-                auto load_index = [&](const int e0, uint32_t (&ix)[kSweepU]) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int u = 0; u < kSweepU; ++u) {
-                        const int e = e0 + u * 64 + lane;
-                        ix[u] = fmt_b ? (e < nsrc ? (uint32_t)lg.ix2[e] : 0u) : (uint32_t)e;
-                    }
+                // an entry's index in the log (its payload's place): in the compacted copy it rides in the tag word
+                auto log_index = [&](const int e0, const int u, const uint2 kt) __attribute__((always_inline)) -> uint32_t {
+                    return fmt_b ? kt.y >> 6 : (uint32_t)(e0 + u * 64 + lane);
                 };
                 uint32_t ptag[kSweepU];  // tag | 1 << 31 of an entry that is re-accumulated, else 0
                 LogPay ppay[kSweepU];
 #pragma unroll
                 for (int gi = 0; gi < kRingG; ++gi) {
                     load_group(gi * kGroup, ring[gi]);
-                    load_index(gi * kGroup, ringx[gi]);
                 }
 #pragma unroll
                 for (int u = 0; u < kSweepU; ++u) {
@@ -640,13 +635,13 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                         }
                     }
                 };
-                auto decide = [&](const uint2 (&kt)[kSweepU], const uint32_t (&ix)[kSweepU]) __attribute__((always_inline)) {
+                auto decide = [&](const int e0, const uint2 (&kt)[kSweepU]) __attribute__((always_inline)) {
                     uint32_t readdm = 0u;
                     uint32_t rtag[kSweepU];  // pixel | copy << 6 | sub-pass << 8 of a kept entry
 #pragma unroll
                     for (int u = 0; u < kSweepU; ++u) {  // decisions in log order (ties are served first come)
                         rtag[u] = 0u;
-                        if (kt[u].y != kNoEntry) {
+                        if (in_src(e0, u)) {
                             const uint32_t px = kt[u].y & 63u;
                             const uint2 w = s_sel[px];
                             const uint32_t shp = w.y & 255u;
@@ -657,7 +652,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
                                 } else if (((kt[u].x - w.x) >> shp) == 0u) {
                                     if ((w.y >> 8) == (uint32_t)kList) {
                                         const uint32_t sl = atomicAdd(&s_lcnt[px], 1u);
-                                        if (sl < (uint32_t)kListCap) blist[px * kListCap + sl] = make_uint2(kt[u].x, ix[u]);  // (key, log index)
+                                        if (sl < (uint32_t)kListCap) blist[px * kListCap + sl] = make_uint2(kt[u].x, log_index(e0, u, kt[u]));  // (key, log index)
                                     } else {
                                         r = (int)atomicSub(&s_take[px], 1u) > 0;  // the first `take` arrivals are kept
                                     }
@@ -683,7 +678,7 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
 #pragma unroll
                     for (int u = 0; u < kSweepU; ++u) {
                         const bool r = (readdm >> u) & 1u;
-                        const uint32_t e = ix[u];  // index of the entry in the log itself: where its payload is
+                        const uint32_t e = log_index(e0, u, kt[u]);  // index of the entry in the log itself: where its payload is
                         ptag[u] = r ? (rtag[u] | 0x80000000u) : 0u;
                         ppay[u] = r ? lg.pay[e] : LogPay{1.f, 0.f, 0.f};
                     }
@@ -692,9 +687,8 @@ __global__ __launch_bounds__(64, OCC_RASTER2_WAVES_PER_SIMD) void occ_raster2_ke
 #pragma unroll
                     for (int gi = 0; gi < kRingG; ++gi) {
                         apply();  // the group before this one
-                        decide(ring[gi], ringx[gi]);
+                        decide(e0 + gi * kGroup, ring[gi]);
                         load_group(e0 + (kRingG + gi) * kGroup, ring[gi]);
-                        load_index(e0 + (kRingG + gi) * kGroup, ringx[gi]);
                     }
                 }
                 apply();  // the last group
