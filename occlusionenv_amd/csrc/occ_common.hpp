@@ -77,6 +77,11 @@ __device__ __forceinline__ void block_lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// Wait for every outstanding vector-memory operation of the wave (s_waitcnt vmcnt(0); expcnt and lgkmcnt left alone) as
+// a BUILTIN: hipcc's own wait insertion sees it and then places no further wait for what it covers.  (The same wait
+// in inline assembly is invisible to that pass, and all of its own waits stay.)
+__device__ __forceinline__ void wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);

@@ -550,12 +550,34 @@ __global__ __launch_bounds__(TB, 4) void occ_setup_kernel(OccScene sc, const flo
     const float* __restrict__ pool_verts = sc.pool_verts;
     const int nV = sc.mesh_vert_off[mesh + 1] - vo;
     const bool vlds = vcap > 0 && nV <= vcap;  // block-uniform
+    // vertex indices of the NEXT round's face are fetched one round ahead: the index -> vertex -> projection chain
+    // of a round then starts at the vertex gather.  (The first round's: in flight together with the vertex copy.)
+    int vi0 = 0, vi1 = 0, vi2 = 0;
+    if (tid < nF) {
+        const int* pf = pool_faces + (size_t)(fo + tid) * 3;
+        vi0 = pf[0]; vi1 = pf[1]; vi2 = pf[2];
+    }
     if (vlds) {
-        for (int v = tid; v < nV; v += TB) {
-            const float* pv = pool_verts + (size_t)(vo + v) * 3;
-            s_wv[v] = pv[0] + ox;
-            s_wv[vcap + v] = pv[1] + oy;
-            s_wv[2 * vcap + v] = pv[2] + oz;
+        // ONE round trip: all of a thread's loads are issued before the first is used (a loop of load - wait - write
+        // trips is that many serial round trips to the vertex pool in front of the block's first face)
+        constexpr int VT = (kSetupVcapMax + TB - 1) / TB;  // vertices per thread at most (vcap <= kSetupVcapMax)
+        float px[VT], py[VT], pz[VT];
+#pragma unroll
+        for (int k = 0; k < VT; ++k) {
+            const int v = tid + k * TB;
+            if (v < nV) {
+                const float* pv = pool_verts + (size_t)(vo + v) * 3;
+                px[k] = pv[0]; py[k] = pv[1]; pz[k] = pv[2];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < VT; ++k) {
+            const int v = tid + k * TB;
+            if (v < nV) {
+                s_wv[v] = px[k] + ox;
+                s_wv[vcap + v] = py[k] + oy;
+                s_wv[2 * vcap + v] = pz[k] + oz;
+            }
         }
     }
     auto corner = [&](int vi, float* w) {
@@ -592,13 +614,7 @@ __global__ __launch_bounds__(TB, 4) void occ_setup_kernel(OccScene sc, const flo
     bool overflow = false;
     int rx0 = 1 << 20, ry0 = 1 << 20, rx1 = -1, ry1 = -1;  // this thread's share of the object's block rect
     int round = 0;
-    // vertex indices of the NEXT round's face are fetched one round ahead: the index -> vertex -> projection chain
-    // of a round then starts at the vertex gather
-    int vi0 = 0, vi1 = 0, vi2 = 0;
-    if (tid < nF) {
-        const int* pf = pool_faces + (size_t)(fo + tid) * 3;
-        vi0 = pf[0]; vi1 = pf[1]; vi2 = pf[2];
-    }
+    wait_vmem();  // the first round's indices
     for (int base = 0; base < nF; base += TB, round ^= 1) {
         const int f = base + tid;
         int cnt = 0;
@@ -641,6 +657,12 @@ __global__ __launch_bounds__(TB, 4) void occ_setup_kernel(OccScene sc, const flo
         const int pre = __popcll(m1 & lt) + __popcll(m2 & lt);
         if (lane == 0) s_wcnt[round][wave] = __popcll(m1) + __popcll(m2);
         // (only the wave counts cross this barrier, through LDS: no need to wait for the round's record stores to land)
+        // STORE DRAINS: loads and stores share one counter (vmcnt), and a store stays counted until L2 has acknowledged
+        // it.  The next round's indices are waited for HERE - they have had the whole phase above to arrive, and the only
+        // stores still counted are the previous round's - so that nothing between this round's first record store and the
+        // loop's back edge waits on the counter: a wait behind the stores, for a register they never touch, is a store
+        // round trip to memory per round in front of a barrier that waits for the slowest of the block's waves.
+        wait_vmem();
         block_lds_barrier();
         int woff = 0, itot = 0;
         if (W <= 4) {
@@ -726,6 +748,7 @@ __global__ __launch_bounds__(TB, 4) void occ_setup_kernel(OccScene sc, const flo
                         x0 = min(x0, tmp[1].tx0); y0 = min(y0, tmp[1].ty0);
                         x1 = max(x1, tmp[1].tx1); y1 = max(y1, tmp[1].ty1);
                     }
+                    wait_vmem();  // tmp[] comes back through scratch: waited for in here, not at the join with the fast path
                 }
                 rx0 = min(rx0, x0); ry0 = min(ry0, y0);
                 rx1 = max(rx1, x1); ry1 = max(ry1, y1);
