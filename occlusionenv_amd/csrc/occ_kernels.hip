@@ -416,20 +416,37 @@ extern "C" int occ_step(const OccScene* scene, const OccCameraArgs* camera, floa
     return OCC_OK;
 }
 
+// the forward entry points' argument check; fills the kernels' argument block
+static bool kbuf_args(KbufArgs* a, const float* face_verts, const int64_t* mesh_to_face_first_idx,
+                      const int64_t* num_faces_per_mesh, const int64_t* clipped_faces_neighbor_idx, int n_meshes, int H, int W,
+                      float blur_radius, int faces_per_pixel, int perspective_correct, int clip_barycentric_coords,
+                      int cull_backfaces, int64_t* pix_to_face, float* zbuf, float* bary, float* dists) {
+    if (!face_verts || !mesh_to_face_first_idx || !num_faces_per_mesh || !pix_to_face || !zbuf || !bary || !dists ||
+        n_meshes <= 0 || H <= 0 || W <= 0 || faces_per_pixel <= 0 || blur_radius < 0.f)
+        return false;
+    *a = KbufArgs{face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, n_meshes, H, W,
+                  faces_per_pixel, blur_radius, perspective_correct, clip_barycentric_coords, cull_backfaces, pix_to_face,
+                  zbuf, bary, dists};
+    return true;
+}
+
+static int kbuf_launch_naive(const KbufArgs& a, hipStream_t st) {
+    const long npix = (long)a.N * a.H * a.W;
+    hipLaunchKernelGGL(occ_rast_naive_fwd_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(64), 0, st, a);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
 extern "C" int occ_rasterize_meshes_naive(const float* face_verts, const int64_t* mesh_to_face_first_idx,
                                           const int64_t* num_faces_per_mesh, const int64_t* clipped_faces_neighbor_idx,
                                           int n_meshes, int H, int W, float blur_radius, int faces_per_pixel,
                                           int perspective_correct, int clip_barycentric_coords, int cull_backfaces,
                                           int64_t* pix_to_face, float* zbuf, float* bary, float* dists, void* stream) {
-    if (!face_verts || !mesh_to_face_first_idx || !num_faces_per_mesh || !pix_to_face || !zbuf || !bary || !dists ||
-        n_meshes <= 0 || H <= 0 || W <= 0 || faces_per_pixel <= 0 || blur_radius < 0.f)
+    KbufArgs a;
+    if (!kbuf_args(&a, face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, n_meshes, H, W,
+                   blur_radius, faces_per_pixel, perspective_correct, clip_barycentric_coords, cull_backfaces, pix_to_face,
+                   zbuf, bary, dists))
         return OCC_ERR_ARG;
-    KbufArgs a{face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, n_meshes, H, W,
-               faces_per_pixel, blur_radius, perspective_correct, clip_barycentric_coords, cull_backfaces, pix_to_face,
-               zbuf, bary, dists};
-    const long npix = (long)n_meshes * H * W;
-    hipLaunchKernelGGL(occ_rast_naive_fwd_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+    return kbuf_launch_naive(a, (hipStream_t)stream);
 }
 
 extern "C" int occ_rasterize_meshes_tiled(const float* face_verts, const int64_t* mesh_to_face_first_idx,
@@ -437,43 +454,25 @@ extern "C" int occ_rasterize_meshes_tiled(const float* face_verts, const int64_t
                                           int n_meshes, int H, int W, float blur_radius, int faces_per_pixel,
                                           int perspective_correct, int clip_barycentric_coords, int cull_backfaces,
                                           int64_t* pix_to_face, float* zbuf, float* bary, float* dists, void* stream) {
-    if (!face_verts || !mesh_to_face_first_idx || !num_faces_per_mesh || !pix_to_face || !zbuf || !bary || !dists ||
-        n_meshes <= 0 || H <= 0 || W <= 0 || faces_per_pixel <= 0 || blur_radius < 0.f)
+    KbufArgs a;
+    if (!kbuf_args(&a, face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, n_meshes, H, W,
+                   blur_radius, faces_per_pixel, perspective_correct, clip_barycentric_coords, cull_backfaces, pix_to_face,
+                   zbuf, bary, dists))
         return OCC_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)64 * faces_per_pixel * 8;
-    if (lds > 64 * 1024)  // beyond the (depth, face) lists the kernel keeps in LDS: same results from the naive kernel
-        return occ_rasterize_meshes_naive(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx,
-                                          n_meshes, H, W, blur_radius, faces_per_pixel, perspective_correct,
-                                          clip_barycentric_coords, cull_backfaces, pix_to_face, zbuf, bary, dists, stream);
-    KbufArgs a{face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, n_meshes, H, W,
-               faces_per_pixel, blur_radius, perspective_correct, clip_barycentric_coords, cull_backfaces, pix_to_face,
-               zbuf, bary, dists};
+    if (lds > 64 * 1024)  // beyond the (depth, face) lists the kernels keep in LDS (K > 128): same results from the naive kernel
+        return kbuf_launch_naive(a, st);
     // meshes without clipped-face pairs (no neighbour array, or all -1 for the mesh): the K-buffer does not depend on the
     // arrival order - 4x4 tiles, four faces in flight; meshes with pairs: 8x8 tiles, faces in order.  With an array both
     // kernels are launched and every wave finds out first which of the two its mesh belongs to.
     const int qx = (W + 3) / 4, qy = (H + 3) / 4;
-    hipLaunchKernelGGL(occ_rast_quad_fwd_kernel, dim3((unsigned)(n_meshes * qx * qy)), dim3(64), lds, (hipStream_t)stream, a, qx, qy);
+    hipLaunchKernelGGL(occ_rast_quad_fwd_kernel, dim3((unsigned)(n_meshes * qx * qy)), dim3(64), lds, st, a, qx, qy);
     if (clipped_faces_neighbor_idx) {
         const int tiles_x = (W + 7) / 8, tiles_y = (H + 7) / 8;
-        hipLaunchKernelGGL(occ_rast_tiled_fwd_kernel, dim3((unsigned)(n_meshes * tiles_x * tiles_y)), dim3(64), lds,
-                           (hipStream_t)stream, a, tiles_x, tiles_y, 1);
+        hipLaunchKernelGGL(occ_rast_tiled_fwd_kernel, dim3((unsigned)(n_meshes * tiles_x * tiles_y)), dim3(64), lds, st, a,
+                           tiles_x, tiles_y, 1);
     }
-    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
-}
-
-extern "C" int occ_rasterize_meshes_backward_dists(const float* face_verts, const int64_t* pix_to_face,
-                                                   const float* grad_dists, int64_t n_faces, int n_meshes, int H, int W,
-                                                   int faces_per_pixel, int perspective_correct,
-                                                   int clip_barycentric_coords, float* grad_face_verts, void* stream) {
-    if (!face_verts || !pix_to_face || !grad_dists || !grad_face_verts || n_faces <= 0 || n_meshes <= 0 || H <= 0 ||
-        W <= 0 || faces_per_pixel <= 0)
-        return OCC_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(grad_face_verts, 0, (size_t)n_faces * 9 * sizeof(float), st) != hipSuccess) return OCC_ERR_LAUNCH;
-    const long tot = (long)n_meshes * H * W * faces_per_pixel;
-    hipLaunchKernelGGL(occ_rast_naive_bwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, face_verts,
-                       pix_to_face, grad_dists, n_meshes, H, W, faces_per_pixel, perspective_correct,
-                       clip_barycentric_coords, grad_face_verts);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 
@@ -495,6 +494,16 @@ extern "C" int occ_rasterize_meshes_backward(const float* face_verts, const int6
         hipLaunchKernelGGL(occ_rast_bwd_zbary_kernel, grid, block, 0, st, face_verts, pix_to_face, grad_zbuf, grad_bary,
                            n_meshes, H, W, faces_per_pixel, perspective_correct, clip_barycentric_coords, grad_face_verts);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+// the dists gradient alone: the call above with a required grad_dists and no other gradient
+extern "C" int occ_rasterize_meshes_backward_dists(const float* face_verts, const int64_t* pix_to_face,
+                                                   const float* grad_dists, int64_t n_faces, int n_meshes, int H, int W,
+                                                   int faces_per_pixel, int perspective_correct,
+                                                   int clip_barycentric_coords, float* grad_face_verts, void* stream) {
+    if (!grad_dists) return OCC_ERR_ARG;
+    return occ_rasterize_meshes_backward(face_verts, pix_to_face, nullptr, nullptr, grad_dists, n_faces, n_meshes, H, W,
+                                         faces_per_pixel, perspective_correct, clip_barycentric_coords, grad_face_verts, stream);
 }
 
 extern "C" int occ_sigmoid_alpha_blend_fwd(const float* dists, const int64_t* pix_to_face, int64_t n_pix, int faces_per_pixel,

@@ -1,6 +1,9 @@
-"""Bitwise A/B of two library builds on a few scenes (GPU box): python scripts/dbg/ab_outputs.py libA.so libB.so
-Every output of reset + step (+ render) must be identical."""
-import os, subprocess, sys, tempfile
+"""Bitwise A/B of two library builds on a few scenes (GPU box), one fresh child process per library, in sequence:
+  python scripts/dbg/ab_outputs.py libA.so libB.so                         step mode: every output of reset + step (+ render)
+  python scripts/dbg/ab_outputs.py --oplevel libA.so libB.so [hashes.json]  operator-level K-buffers (ops.rasterize_meshes):
+      the scenes of tests/test_gpu_rasterize_op.py through both entry points, a sha256 per output tensor
+Every output must be identical; the first child that fails ends the run."""
+import hashlib, json, os, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CASES = [(2, 64, 5, "teapot", 4.0), (3, 128, 6, "synthetic", 4.0), (1, 72, 7, "teapot", 4.0), (2, 256, 8, "synthetic", 4.0), (2, 96, 9, "textured", 1.3)]
 KEYS = ("obs0", "alphas0", "fs0", "loss0", "obs", "alphas", "fs", "loss", "reward", "grad", "render")
@@ -10,18 +13,94 @@ CODE = ("import sys, torch; sys.path.insert(0, %r); from tests.parity_utils impo
         "    got = run_engine(make_case(n, seed, mesh), img, radius=radius, render_too=True)\n"
         "    res.append({k: got[k].detach().cpu() for k in %r})\n"
         "torch.save(res, sys.argv[1])\n" % (ROOT, CASES, KEYS))
-import torch
-outs = []
-with tempfile.TemporaryDirectory() as td:
-    for i, lib in enumerate(sys.argv[1:3]):
-        path = os.path.join(td, "o%d.pt" % i)
-        r = subprocess.run([sys.executable, "-c", CODE, path], env=dict(os.environ, OCC_HIP_LIB=os.path.abspath(lib)), capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs.append(torch.load(path))
-bad = 0
-for case, a, b in zip(CASES, outs[0], outs[1]):
-    for k in KEYS:
-        if not torch.equal(a[k], b[k]):
-            bad += 1
-            print("DIFFERENT", case, k, float((a[k] - b[k]).abs().max()))
-print("bitwise A/B over %d cases x %d outputs: %s" % (len(CASES), len(KEYS), "IDENTICAL" if not bad else "%d differ" % bad))
+OUTPUTS = ("pix_to_face", "zbuf", "bary", "dists")
+
+
+def children(libs, argv, load):
+    """Run `python *argv PATH` once per library (OCC_HIP_LIB), one after the other; load(PATH) of each."""
+    outs = []
+    with tempfile.TemporaryDirectory() as td:
+        for i, lib in enumerate(libs):
+            path = os.path.join(td, "o%d" % i)
+            r = subprocess.run([sys.executable, *argv, path], env=dict(os.environ, OCC_HIP_LIB=os.path.abspath(lib)), capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, (lib, r.stderr[-2000:])
+            outs.append(load(path))
+    return outs
+
+
+def oplevel_corpus():
+    """name -> arguments of ops.rasterize_meshes: what tests/test_gpu_rasterize_op.py sets the tiled kernels against the naive one on."""
+    import torch
+    sys.path.insert(0, ROOT)
+    from oracle import p3d_restate as O
+    from occlusionenv_amd.meshes import SyntheticShapeNet, load_obj
+    from tests import test_gpu_rasterize_op as T
+    teapot = load_obj(os.path.join(ROOT, "data", "teapot.obj"))
+    one = lambda fv: (torch.tensor([0]), torch.tensor([fv.shape[0]]))
+    fv, _ = T._teapot_scene_face_verts(teapot)
+    F1 = fv.shape[0]
+    corpus = {}
+    for K in (1, 8, 100):
+        corpus["two teapots (44, 52) K %d" % K] = (torch.cat([fv, fv * torch.tensor([0.7, 0.7, 1.0])]), torch.tensor([0, F1]), torch.tensor([F1, F1]),
+                                                   (44, 52), O.BLUR_RADIUS if K > 1 else 0.0, K, True, K > 1, True, None)
+    fvc, nb = T._teapot_scene_face_verts(teapot, radius=1.2)
+    sq = fvc * torch.tensor([0.25, 0.25, 1.0])
+    corpus["clipped r 1.2 squeezed 64 K 20"] = (sq, *one(sq), 64, O.BLUR_RADIUS, 20, True, True, True, nb)
+    v, f = SyntheticShapeNet(n_models=1, seed=5).models[0]
+    R, Tr = O.look_at_view_transform(torch.tensor([4.0]), torch.tensor([0.0]), torch.tensor([0.3]))
+    big = O.world_to_ndc(v, R[0], Tr[0])[f].contiguous()
+    for size in (128, (50, 38)):
+        corpus["synthetic 5120 faces %s K 100" % (size,)] = (big, *one(big), size, O.BLUR_RADIUS, 100, True, True, True, None)
+    corpus["full lists pair 64 K 3"] = (torch.cat([big, big * torch.tensor([0.5, 0.5, 1.0])]), torch.tensor([0, big.shape[0]]), torch.tensor([big.shape[0]] * 2),
+                                        64, O.BLUR_RADIUS, 3, True, True, True, None)
+    for case, K, size, args in T._random_order_free_scenes():
+        corpus["random %d" % case] = args
+    for name, (cfv, cnb, S, K, blur, clipb, _) in T._persp_off_cases(teapot).items():
+        corpus["perspective off (%s)" % name] = (cfv, *one(cfv), S, blur, K, False, clipb, True, cnb)
+    bfv, bnb, S, blur = T._k_boundary_scene(teapot)
+    for K in (128, 129):
+        corpus["K boundary K %d" % K] = (bfv, *one(bfv), S, blur, K, True, True, True, bnb)
+    return corpus
+
+
+def oplevel_child(path):
+    import torch
+    corpus = oplevel_corpus()
+    from occlusionenv_amd.ops import rasterize_meshes
+    res = {}
+    for name, args in corpus.items():
+        args = tuple(a.cuda() if isinstance(a, torch.Tensor) and a.dtype == torch.float32 else a for a in args[:-1]) + (None if args[-1] is None else args[-1].cuda(),)
+        for naive in (False, True):
+            out = rasterize_meshes(*args, naive=naive)
+            res["%s / %s" % (name, "naive" if naive else "tiled")] = {k: hashlib.sha256(t.cpu().contiguous().numpy().tobytes()).hexdigest() for k, t in zip(OUTPUTS, out)}
+    json.dump(res, open(path, "w"), indent=1)
+
+
+def main(argv):
+    if argv[:1] == ["--oplevel-child"]:
+        return oplevel_child(argv[1])
+    if argv[:1] == ["--oplevel"]:
+        libs = argv[1:3]
+        a, b = children(libs, [os.path.abspath(__file__), "--oplevel-child"], lambda p: json.load(open(p)))
+        assert a.keys() == b.keys()
+        bad = [(c, k) for c in a for k in OUTPUTS if a[c][k] != b[c][k]]
+        for c, k in bad:
+            print("DIFFERENT", c, k)
+        print("bitwise A/B over %d cases x %d outputs: %s" % (len(a), len(OUTPUTS), "IDENTICAL" if not bad else "%d differ" % len(bad)))
+        if len(argv) > 3:
+            json.dump({"libraries": [os.path.basename(l) for l in libs], "identical": not bad, "sha256": [a, b] if bad else a}, open(argv[3], "w"), indent=1)
+        return 1 if bad else 0
+    import torch
+    outs = children(argv[:2], ["-c", CODE], torch.load)
+    bad = 0
+    for case, a, b in zip(CASES, outs[0], outs[1]):
+        for k in KEYS:
+            if not torch.equal(a[k], b[k]):
+                bad += 1
+                print("DIFFERENT", case, k, float((a[k] - b[k]).abs().max()))
+    print("bitwise A/B over %d cases x %d outputs: %s" % (len(CASES), len(KEYS), "IDENTICAL" if not bad else "%d differ" % bad))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

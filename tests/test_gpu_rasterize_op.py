@@ -38,6 +38,84 @@ def test_kbuffer_matches_oracle(teapot, blur, K, radius, naive):
         assert nb is not None and (nb >= 0).any()  # the clipped-pair rule was exercised
 
 
+def _assert_matches_oracle(got, ref):
+    """(pix_to_face, zbuf, bary, dists) of one mesh against the oracle's: the file's tolerances."""
+    p2f, zbuf, bary, dists = got
+    assert torch.equal(p2f, ref[0]), "pix_to_face must be identical (index work is bit-exact)"
+    assert torch.allclose(zbuf, ref[1], atol=1e-6) and torch.allclose(dists, ref[3], atol=1e-7)
+    assert torch.allclose(bary, ref[2], atol=1e-5)
+
+
+def _both_entry_points(fv, nb, S, blur, K, persp, clipb, ref):
+    """One mesh through the tiled and the naive entry point: each against the oracle's `ref`, and tiled = naive bit for
+    bit on all four outputs.  Returns the tiled result (on the CPU)."""
+    from occlusionenv_amd.ops import rasterize_meshes
+
+    outs = []
+    for naive in (False, True):
+        got = rasterize_meshes(fv.cuda(), torch.tensor([0]), torch.tensor([fv.shape[0]]), S, blur, K, persp, clipb, True,
+                               None if nb is None else nb.cuda(), naive=naive)
+        outs.append([t[0].cpu() for t in got])
+        _assert_matches_oracle(outs[-1], ref)
+    for a, b, name in zip(outs[0], outs[1], ("pix_to_face", "zbuf", "bary", "dists")):
+        assert torch.equal(a, b), (name, "tiled != naive")
+    return outs[0]
+
+
+def _persp_off_cases(teapot):
+    """name -> (face_verts, neighbour array, S, K, blur, clip_barycentric_coords, least covered pixels / full lists /
+    entries of paired faces in the oracle's result) of test_perspective_correction_off."""
+    fv, nb = _teapot_scene_face_verts(teapot)
+    fvc, nbc = _teapot_scene_face_verts(teapot, radius=1.2)
+    squeezed = (fvc * torch.tensor([0.25, 0.25, 1.0])).contiguous()  # into view, as in the tiled = naive test
+    return {"a": (fv, nb, 32, 4, O.BLUR_RADIUS, True, (50, 50, 0)),
+            "b": (fv, nb, 32, 4, 0.0, False, (50, 0, 0)),
+            "c": (squeezed, nbc, 48, 4, O.BLUR_RADIUS, True, (30, 20, 20))}
+
+
+@pytest.mark.parametrize("case", ["a", "b", "c"])
+def test_perspective_correction_off(teapot, case):
+    """perspective_correct=False (every other forward call of this file passes True) through both entry points: the teapot
+    with blur and clipping (a: the oracle has 74 covered pixels, 73 full lists), without either (b: 53 covered), and the
+    z-clipped scene squeezed into view with its neighbour array, i.e. the ordered 8x8 kernel (c: 37 covered, 26 full, 28
+    entries of paired faces).  Against the oracle; tiled = naive bit for bit; and the switch matters: the oracle's zbuf
+    with the correction on differs on at least 40 entries that hold the same face (it gives 225, 54, 103)."""
+    fv, nb, S, K, blur, clipb, (min_cov, min_full, min_paired) = _persp_off_cases(teapot)[case]
+    ref = O._Rasterize.apply(fv, nb, S, float(blur), K, False, clipb, True)
+    assert int((ref[0][..., 0] >= 0).sum()) >= min_cov and int((ref[0][..., K - 1] >= 0).sum()) >= min_full
+    if min_paired:
+        assert int((nb[ref[0][ref[0] >= 0]] >= 0).sum()) >= min_paired  # the clipped-pair rule had entries to decide on
+    ref_on = O._Rasterize.apply(fv, nb, S, float(blur), K, True, clipb, True)
+    same_face = (ref[0] >= 0) & (ref[0] == ref_on[0])
+    assert int((same_face & (ref[1] != ref_on[1])).sum()) >= 40
+    _both_entry_points(fv, nb, S, blur, K, False, clipb, ref)
+
+
+def _k_boundary_scene(teapot):
+    """(face_verts, neighbour array, S, blur) of test_faces_per_pixel_128_and_129."""
+    fv, nb = _teapot_scene_face_verts(teapot)
+    return fv, nb, 16, 16 * O.BLUR_RADIUS
+
+
+def test_faces_per_pixel_128_and_129(teapot):
+    """K = 128 is the largest K the tiled kernels take (64 lists of 128 entries of 8 bytes: exactly 64 KiB of LDS), K = 129
+    the first that occ_rasterize_meshes_tiled hands to the naive kernel.  Teapot at 16x16 with 16 * BLUR_RADIUS (the
+    oracle: 34 covered pixels, the longest list 129 long, 10 pixels full at K = 129): both K and both entry points against
+    the oracle, tiled = naive bit for bit, and - no clipped pairs, so a K-buffer is the K smallest (z, face) - the first
+    128 slots of the K = 129 result equal the K = 128 result bit for bit: the order-free tiled kernel against the naive
+    one across the fallback."""
+    fv, nb, S, blur = _k_boundary_scene(teapot)
+    assert nb is None or not bool((nb >= 0).any())
+    res = {}
+    for K in (128, 129):
+        ref = O._Rasterize.apply(fv, nb, S, float(blur), K, True, True, True)
+        if K == 129:
+            assert int((ref[0][..., K - 1] >= 0).sum()) >= 5  # full lists
+        res[K] = _both_entry_points(fv, nb, S, blur, K, True, True, ref)
+    for a, b, name in zip(res[129], res[128], ("pix_to_face", "zbuf", "bary", "dists")):
+        assert torch.equal(a[:, :, :128], b), (name, "first 128 slots at K = 129 != K = 128")
+
+
 def test_two_meshes_and_backward(teapot):
     from occlusionenv_amd.ops import rasterize_meshes
 
@@ -227,18 +305,12 @@ def test_zbuf_and_bary_gradients_match_torch_autograd(teapot):
         assert torch.allclose(g_all, g_zb + g_d, atol=1e-4 * max(scale, float(g_d.abs().max())), rtol=1e-4)
 
 
-def test_order_free_kbuffer_equals_the_naive_one_on_random_scenes():
-    """occ_rast_quad_fwd_kernel (4x4 tiles, four faces in flight, four partial lists per pixel merged by rank: the kernel
-    behind occ_rasterize_meshes_tiled when there are no clipped pairs) against the naive kernel, bit for bit on all four
-    outputs, over random scenes: procedural meshes of three densities, cameras near and far, one to three meshes per call,
-    sides that are multiples of neither 4 nor 8, K from 1 to 128 (lists that never fill up and lists that overflow at
-    every covered pixel), culling on and off, barycentric clipping on and off."""
+def _random_order_free_scenes():
+    """The 14 random scenes of the test below: (case, K, size, arguments of rasterize_meshes)."""
     from occlusionenv_amd.meshes import SyntheticShapeNet
-    from occlusionenv_amd.ops import rasterize_meshes
 
     g = torch.Generator().manual_seed(2024)
     models = SyntheticShapeNet(n_models=6, seed=9, mixed=True).models
-    checked = full = 0
     for case in range(14):
         n_m = 1 + case % 3
         fvs, first, num = [], [], []
@@ -259,7 +331,19 @@ def test_order_free_kbuffer_equals_the_naive_one_on_random_scenes():
         blur = O.BLUR_RADIUS * (1.0, 4.0, 0.0)[case % 3]
         cull, clipb = case % 4 != 3, blur > 0 and case % 5 != 4
         nbr = torch.full((fv.shape[0],), -1, dtype=torch.int64, device="cuda") if case % 2 else None  # clip_faces' array for an unclipped scene
-        args = (fv, torch.tensor(first), torch.tensor(num), size, blur, K, True, clipb, cull, nbr)
+        yield case, K, size, (fv, torch.tensor(first), torch.tensor(num), size, blur, K, True, clipb, cull, nbr)
+
+
+def test_order_free_kbuffer_equals_the_naive_one_on_random_scenes():
+    """occ_rast_quad_fwd_kernel (4x4 tiles, four faces in flight, four partial lists per pixel merged by rank: the kernel
+    behind occ_rasterize_meshes_tiled when there are no clipped pairs) against the naive kernel, bit for bit on all four
+    outputs, over random scenes: procedural meshes of three densities, cameras near and far, one to three meshes per call,
+    sides that are multiples of neither 4 nor 8, K from 1 to 128 (lists that never fill up and lists that overflow at
+    every covered pixel), culling on and off, barycentric clipping on and off."""
+    from occlusionenv_amd.ops import rasterize_meshes
+
+    checked = full = 0
+    for case, K, size, args in _random_order_free_scenes():
         a = rasterize_meshes(*args, naive=False)
         b = rasterize_meshes(*args, naive=True)
         for x, y, name in zip(a, b, ("pix_to_face", "zbuf", "bary", "dists")):
