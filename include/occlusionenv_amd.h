@@ -393,6 +393,17 @@ int occ_encoder_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* 
 /* n_env in [1, 65535]; ws of at least the queried bytes (256-byte aligned). */
 int occ_encoder_forward(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
                         size_t ws_bytes, float* feats, void* stream);
+/*
+ * occ_encoder_forward with a per-env skip mask (additive in ABI 12).  skip: device memory of n_env int32, read by the
+ * kernels when they run (a captured call follows the values it finds at replay); NULL is occ_encoder_forward itself, and
+ * occ_encoder_forward is this call with NULL.  An env with skip[env] != 0 is left alone, as OccScene.skip leaves it alone in
+ * the engine: none of its blocks reads obs or writes anything, and its feats row KEEPS the bits it held before the call.
+ * What the workspace holds for a skipped env afterwards is unspecified and is never read.  Every other env's row is
+ * bitwise what the unmasked call writes.  Same 17 launches on the same grids (sized by n_env: the host needs no count of
+ * the active envs); a skipped env costs its blocks' dispatch, not their work.  Workspace: occ_encoder_workspace_query.
+ */
+int occ_encoder_forward_masked(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
+                               size_t ws_bytes, float* feats, const int32_t* skip, void* stream);
 
 /*
  * Segmentation decoder (model.py:109-125 on top of the encoder above, eval mode): x = the last down output
@@ -424,6 +435,15 @@ int occ_segment_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* 
 int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
                         int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* logit, float* dec_feat,
                         void* stream);
+/*
+ * occ_segment_forward with the skip mask of occ_encoder_forward_masked (additive in ABI 12; NULL is occ_segment_forward
+ * itself).  An env with skip[env] != 0 keeps the bits of its rows of feats, prob, logit and dec_feat; its part of the
+ * workspace (activations, skip tensors, partials) is unspecified and never read.  Every other env's rows are bitwise what
+ * the unmasked call writes.  Same 22 launches; workspace: occ_segment_workspace_query.
+ */
+int occ_segment_forward_masked(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                               int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* logit, float* dec_feat,
+                               const int32_t* skip, void* stream);
 /*
  * Training of the decoder and the classifier with the encoder frozen (additive in ABI 12; csrc/occ_decoder_bwd.hpp).  The
  * decoder's BatchNorm runs with its running statistics, as in inference: with u = convT(x_j) + bias, r = relu(u),

@@ -209,10 +209,14 @@ SYMBOLS = {
     "occ_encoder_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t)]),
     "occ_encoder_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p]),
+    "occ_encoder_forward_masked": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "occ_decoder_packed_floats": (C.c_int64, [C.POINTER(OccEncoderConfig)]),
     "occ_segment_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t)]),
     "occ_segment_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_size_t] + [C.c_void_p] * 5),
+    "occ_segment_forward_masked": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_size_t] + [C.c_void_p] * 6),
     "occ_segment_train_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t),
                                                    C.POINTER(C.c_size_t)]),
     "occ_segment_train_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

@@ -35,14 +35,16 @@
 
 // logit: inference: where the logit is stored, or null.  TRAIN: where the kept copy of prob is stored (no logit is).
 // rkeep (TRAIN): (n, cout, 2H, 2H), where r is stored; not read otherwise.
+// env_skip: the env mask of the inference forwards (enc_env_skipped; `skip` here is the encoder's per-level feature).
 template <int T, int COG, bool FUSE, bool TRAIN = false>
 __global__ __launch_bounds__(256) void occ_dec_up_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                          const float* __restrict__ skip, const float* __restrict__ w, int cin,
                                                          int cout, int H, int tiles_x, const float* __restrict__ cls,
                                                          float* __restrict__ prob, float* __restrict__ logit,
-                                                         float* __restrict__ rkeep) {
+                                                         float* __restrict__ rkeep, const int32_t* __restrict__ env_skip) {
     constexpr int TT = T * T, R = T + 1, RR = R * R;
     __shared__ float s[kEncCC * RR];
+    if (enc_env_skipped<TRAIN>(env_skip, blockIdx.z)) return;
     const int tid = threadIdx.x;
     const int p = tid % TT;
     const int ng = blockDim.x / TT;
@@ -223,13 +225,13 @@ inline SegWs seg_ws_layout(int img, int n) {
 // forwards, occ_decoder_bwd.hpp): the TRAIN instantiation on the same grid; `logit` is then where the kept prob goes.
 template <bool TRAIN>
 static void dec_launch_up_t(const float* x, float* y, const float* skip, const float* w, int cin, int cout, int H, int n,
-                            const float* cls, float* prob, float* logit, hipStream_t st, float* rkeep) {
+                            const float* cls, float* prob, float* logit, hipStream_t st, float* rkeep, const int32_t* env_skip) {
     constexpr int COG = 16;  // 64 accumulators per thread; cout = 128, 64, 32, 16 below the last level
     const int T = enc_tile(H);
     const TileLaunch l = tile_launch(T, H, cls ? 1 : cout / COG, n);
 #define OCC_DEC_UP(TT, CG, FUSE)                                                                                               \
     hipLaunchKernelGGL((occ_dec_up_kernel<TT, CG, FUSE, TRAIN>), l.grid, l.block, 0, st, x, y, skip, w, cin, cout, H, l.tiles_x, cls, \
-                       prob, logit, rkeep)
+                       prob, logit, rkeep, env_skip)
     if (cls) OCC_DEC_UP(16, 8, true);  // the last level: cout = 8, H = S / 2 >= 16
     else if (T == 16) OCC_DEC_UP(16, COG, false);
     else OCC_DEC_UP(8, COG, false);
@@ -237,15 +239,17 @@ static void dec_launch_up_t(const float* x, float* y, const float* skip, const f
 }
 
 static void dec_launch_up(const float* x, float* y, const float* skip, const float* w, int cin, int cout, int H, int n,
-                          const float* cls, float* prob, float* logit, hipStream_t st, float* rkeep = nullptr) {
-    if (rkeep) dec_launch_up_t<true>(x, y, skip, w, cin, cout, H, n, cls, prob, logit, st, rkeep);
-    else dec_launch_up_t<false>(x, y, skip, w, cin, cout, H, n, cls, prob, logit, st, nullptr);
+                          const float* cls, float* prob, float* logit, hipStream_t st, float* rkeep = nullptr,
+                          const int32_t* env_skip = nullptr) {
+    if (rkeep) dec_launch_up_t<true>(x, y, skip, w, cin, cout, H, n, cls, prob, logit, st, rkeep, nullptr);
+    else dec_launch_up_t<false>(x, y, skip, w, cin, cout, H, n, cls, prob, logit, st, nullptr, env_skip);
 }
 
-// Encoder (17 launches, keeping the skips) + decoder (5 launches): 22 launches.  img % 32 == 0.
+// Encoder (17 launches, keeping the skips) + decoder (5 launches): 22 launches.  img % 32 == 0.  env_skip = null, or the env
+// mask: a skipped env's rows of feats, prob, logit and dec_feat keep what they held.
 static void seg_forward(int img, int dil, bool residual, bool separable, const float* enc_packed, const float* dec_packed,
                         const float* obs, int n, char* ws, float* feats, float* prob, float* logit, float* dec_feat,
-                        hipStream_t st) {
+                        hipStream_t st, const int32_t* env_skip = nullptr) {
     const SegWs l = seg_ws_layout(img, n);
     float* b0 = (float*)ws;
     float* b1 = (float*)(ws + l.buf_bytes);
@@ -256,7 +260,7 @@ static void seg_forward(int img, int dil, bool residual, bool separable, const f
         at += l.skip_bytes[lv];
     }
     keep.last = (float*)at;
-    enc_forward(img, dil, residual, separable, enc_packed, obs, n, ws, feats, st, &keep);
+    enc_forward(img, dil, residual, separable, enc_packed, obs, n, ws, feats, st, &keep, env_skip);
 
     const float* w = dec_packed;
     const float* cls = dec_packed + dec_packed_floats() - (kEncCh + 1);
@@ -267,7 +271,7 @@ static void seg_forward(int img, int dil, bool residual, bool separable, const f
         const int c = kEncCh << lv;
         const bool last = j == kEncLevels - 1;
         float* y = last ? dec_feat : (j % 2 == 0 ? b0 : b1);
-        dec_launch_up(x, y, keep.skip[lv], w, 2 * c, c, H, n, last ? cls : nullptr, prob, logit, st);
+        dec_launch_up(x, y, keep.skip[lv], w, 2 * c, c, H, n, last ? cls : nullptr, prob, logit, st, nullptr, env_skip);
         w += 9LL * 2 * c * c + 3LL * c;
         x = y;
         H *= 2;

@@ -35,13 +35,25 @@ constexpr int kEncMaxR = 35;    // staged rows / columns: (16 - 1) * stride 2 + 
 constexpr int kEncLds = kEncCC * kEncMaxR * kEncMaxR;
 constexpr int kEncSepLds = kEncCC * 20 * 20;
 
+// The skip mask of the inference forwards (occ_encoder_forward_masked, occ_segment_forward_masked): skip = null, or one
+// int32 per env; a block whose env has a non-zero entry returns at once, before any LDS access, barrier or memory access
+// other than this one load, so a skipped env costs one block dispatch and one scalar load per block and writes nothing.
+// The env index comes from the grid and the address is the same for the whole block: a scalar load and a uniform branch.
+// TRAIN instantiations take no mask (their launchers pass null) and compile the test away.
+template <bool TRAIN>
+__device__ __forceinline__ bool enc_env_skipped(const int32_t* __restrict__ skip, unsigned env) {
+    if constexpr (TRAIN) return false;
+    else return skip != nullptr && skip[env] != 0;
+}
+
 // rkeep (TRAIN): (n, cout, H, W), where r is stored; not read otherwise.
 template <int T, int COG, bool TRAIN = false>
 __global__ __launch_bounds__(256) void occ_enc_sep_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                           const float* __restrict__ resid, const float* __restrict__ w,
                                                           int cin, int cout, int H, int W, int d, int tiles_x,
-                                                          float* __restrict__ rkeep) {
+                                                          float* __restrict__ rkeep, const int32_t* __restrict__ skip) {
     __shared__ float s[kEncSepLds];
+    if (enc_env_skipped<TRAIN>(skip, blockIdx.z)) return;
     constexpr int TT = T * T;
     const int tid = threadIdx.x;
     const int p = tid % TT;
@@ -118,8 +130,9 @@ __global__ __launch_bounds__(256) void occ_enc_dense_kernel(const float* __restr
                                                             const float* __restrict__ resid, const float* __restrict__ w,
                                                             int cin, int cout, int H, int W, int Ho, int Wo, int stride,
                                                             int d, int tiles_x, float* __restrict__ partials,
-                                                            float* __restrict__ rkeep) {
+                                                            float* __restrict__ rkeep, const int32_t* __restrict__ skip) {
     __shared__ float s[kEncLds];
+    if (enc_env_skipped<TRAIN>(skip, blockIdx.z)) return;
     constexpr int TT = T * T;
     const int tid = threadIdx.x;
     const int p = tid % TT;
@@ -222,7 +235,8 @@ __global__ __launch_bounds__(256) void occ_enc_dense_kernel(const float* __restr
 
 // feats[n][c] = (sum over tiles t in order of partials[n][t][c]) / count
 __global__ __launch_bounds__(kEncFeat) void occ_enc_pool_kernel(const float* __restrict__ partials, int ntiles, float count,
-                                                                float* __restrict__ feats) {
+                                                                float* __restrict__ feats, const int32_t* __restrict__ skip) {
+    if (enc_env_skipped<false>(skip, blockIdx.x)) return;
     const int c = threadIdx.x;
     const float* pe = partials + (size_t)blockIdx.x * ntiles * kEncFeat + c;
     float sum = 0.f;
@@ -287,12 +301,12 @@ inline void enc_ws_layout(int img, int n, size_t* buf_bytes, size_t* part_bytes)
 // instantiation on the same grid, which also stores r there.
 template <int T, bool TRAIN>
 static void enc_launch_sep_t(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int d,
-                             int n, hipStream_t st, float* rkeep) {
+                             int n, hipStream_t st, float* rkeep, const int32_t* skip) {
     const int cog = enc_cog(cout), ng = enc_groups(T, cout);
     const int tiles_x = (H + T - 1) / T;
     const dim3 grid(tiles_x * tiles_x, cout / (cog * ng), n), block(T * T * ng);
 #define OCC_ENC_SEP(COG) \
-    hipLaunchKernelGGL((occ_enc_sep_kernel<T, COG, TRAIN>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, d, tiles_x, rkeep)
+    hipLaunchKernelGGL((occ_enc_sep_kernel<T, COG, TRAIN>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, d, tiles_x, rkeep, skip)
     if (cog == 8) OCC_ENC_SEP(8);
     else if (cog == 16) OCC_ENC_SEP(16);
     else OCC_ENC_SEP(32);
@@ -300,25 +314,25 @@ static void enc_launch_sep_t(const float* x, float* y, const float* resid, const
 }
 
 static void enc_launch_sep(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int d, int n,
-                           hipStream_t st, float* rkeep = nullptr) {
+                           hipStream_t st, float* rkeep = nullptr, const int32_t* skip = nullptr) {
     const bool t16 = enc_tile(H) == 16;
-    if (rkeep) t16 ? enc_launch_sep_t<16, true>(x, y, resid, w, cin, cout, H, d, n, st, rkeep)
-                   : enc_launch_sep_t<8, true>(x, y, resid, w, cin, cout, H, d, n, st, rkeep);
-    else t16 ? enc_launch_sep_t<16, false>(x, y, resid, w, cin, cout, H, d, n, st, nullptr)
-             : enc_launch_sep_t<8, false>(x, y, resid, w, cin, cout, H, d, n, st, nullptr);
+    if (rkeep) t16 ? enc_launch_sep_t<16, true>(x, y, resid, w, cin, cout, H, d, n, st, rkeep, nullptr)
+                   : enc_launch_sep_t<8, true>(x, y, resid, w, cin, cout, H, d, n, st, rkeep, nullptr);
+    else t16 ? enc_launch_sep_t<16, false>(x, y, resid, w, cin, cout, H, d, n, st, nullptr, skip)
+             : enc_launch_sep_t<8, false>(x, y, resid, w, cin, cout, H, d, n, st, nullptr, skip);
 }
 
 // keep (inference, with partials): the last down also stores its output.  With rkeep it does so where y is not null.
 template <int T, bool TRAIN>
 static void enc_launch_dense_t(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int stride,
-                               int d, int n, float* partials, bool keep, hipStream_t st, float* rkeep) {
+                               int d, int n, float* partials, bool keep, hipStream_t st, float* rkeep, const int32_t* skip) {
     const int Ho = enc_out_size(H, stride);
     const int cog = enc_cog(cout), ng = enc_groups(T, cout);
     const int tiles_x = (Ho + T - 1) / T;
     const dim3 grid(tiles_x * tiles_x, cout / (cog * ng), n), block(T * T * ng);
 #define OCC_ENC_DENSE(COG, POOL, KEEP)                                                                                          \
     hipLaunchKernelGGL((occ_enc_dense_kernel<T, COG, POOL, KEEP, TRAIN>), grid, block, 0, st, x, y, resid, w, cin, cout, H, H, Ho, Ho, \
-                       stride, d, tiles_x, partials, rkeep)
+                       stride, d, tiles_x, partials, rkeep, skip)
     if (partials) {  // the last down: cout = 256
         if constexpr (TRAIN) OCC_ENC_DENSE(32, true, false);
         else if (keep) OCC_ENC_DENSE(32, true, true);
@@ -330,12 +344,13 @@ static void enc_launch_dense_t(const float* x, float* y, const float* resid, con
 }
 
 static void enc_launch_dense(const float* x, float* y, const float* resid, const float* w, int cin, int cout, int H, int stride,
-                             int d, int n, float* partials, hipStream_t st, bool keep = false, float* rkeep = nullptr) {
+                             int d, int n, float* partials, hipStream_t st, bool keep = false, float* rkeep = nullptr,
+                             const int32_t* skip = nullptr) {
     const bool t16 = enc_tile(enc_out_size(H, stride)) == 16;
-    if (rkeep) t16 ? enc_launch_dense_t<16, true>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, rkeep)
-                   : enc_launch_dense_t<8, true>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, rkeep);
-    else t16 ? enc_launch_dense_t<16, false>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, nullptr)
-             : enc_launch_dense_t<8, false>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, nullptr);
+    if (rkeep) t16 ? enc_launch_dense_t<16, true>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, rkeep, nullptr)
+                   : enc_launch_dense_t<8, true>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, rkeep, nullptr);
+    else t16 ? enc_launch_dense_t<16, false>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, nullptr, skip)
+             : enc_launch_dense_t<8, false>(x, y, resid, w, cin, cout, H, stride, d, n, partials, keep, st, nullptr, skip);
 }
 
 // The whole encoder on n envs: 17 launches (the initial layer, two layers and a down per level, the pool).
@@ -343,13 +358,15 @@ static void enc_launch_dense(const float* x, float* y, const float* resid, const
 // down output (occ_segment_forward, occ_decoder.hpp): ws holds b0, b1 and the partials; every level's Layer 2 writes its
 // skip tensor instead of b2 and the last down also stores its output.  The same kernels run on the same values in the
 // same order either way, so the pooled feature is the same to the bit.
+// skip = null, or the env mask (enc_env_skipped): the same 17 launches on the same grids; the blocks of a skipped env return
+// at once, so its feats row and its part of every buffer keep what they held.
 struct EncKeep {
     float* skip[kEncLevels];  // (n, 8 << lv, S >> lv, S >> lv): Layer 2 (+ residual), what the down conv reads
     float* last;              // (n, 256, S / 32, S / 32)
 };
 
 static void enc_forward(int img, int dil, bool residual, bool separable, const float* packed, const float* obs, int n, char* ws,
-                        float* feats, hipStream_t st, const EncKeep* keep = nullptr) {
+                        float* feats, hipStream_t st, const EncKeep* keep = nullptr, const int32_t* skip = nullptr) {
     size_t buf_bytes, part_bytes;
     enc_ws_layout(img, n, &buf_bytes, &part_bytes);
     float* b0 = (float*)ws;
@@ -359,24 +376,24 @@ static void enc_forward(int img, int dil, bool residual, bool separable, const f
     const float* w = packed;
     int H = img;
     // initial: Conv(4 -> 8) with dilation 1 (model.py:92)
-    if (separable) enc_launch_sep(obs, b0, nullptr, w, 4, kEncCh, H, 1, n, st);
-    else enc_launch_dense(obs, b0, nullptr, w, 4, kEncCh, H, 1, 1, n, nullptr, st);
+    if (separable) enc_launch_sep(obs, b0, nullptr, w, 4, kEncCh, H, 1, n, st, nullptr, skip);
+    else enc_launch_dense(obs, b0, nullptr, w, 4, kEncCh, H, 1, 1, n, nullptr, st, false, nullptr, skip);
     w += enc_layer_floats(4, kEncCh, separable);
     for (int lv = 0; lv < kEncLevels; ++lv) {
         const int c = kEncCh << lv;
         if (keep) b2 = keep->skip[lv];
         // Layer 1: b0 -> b1; Layer 2: b1 (+ b0) -> b2; down: b2 -> b0 (or the partials of the pooled feature)
-        if (separable) enc_launch_sep(b0, b1, nullptr, w, c, c, H, dil, n, st);
-        else enc_launch_dense(b0, b1, nullptr, w, c, c, H, 1, dil, n, nullptr, st);
+        if (separable) enc_launch_sep(b0, b1, nullptr, w, c, c, H, dil, n, st, nullptr, skip);
+        else enc_launch_dense(b0, b1, nullptr, w, c, c, H, 1, dil, n, nullptr, st, false, nullptr, skip);
         w += enc_layer_floats(c, c, separable);
-        if (separable) enc_launch_sep(b1, b2, residual ? b0 : nullptr, w, c, c, H, dil, n, st);
-        else enc_launch_dense(b1, b2, residual ? b0 : nullptr, w, c, c, H, 1, dil, n, nullptr, st);
+        if (separable) enc_launch_sep(b1, b2, residual ? b0 : nullptr, w, c, c, H, dil, n, st, nullptr, skip);
+        else enc_launch_dense(b1, b2, residual ? b0 : nullptr, w, c, c, H, 1, dil, n, nullptr, st, false, nullptr, skip);
         w += enc_layer_floats(c, c, separable);
         const bool last = lv == kEncLevels - 1;
         enc_launch_dense(b2, last && keep ? keep->last : b0, nullptr, w, c, 2 * c, H, 2, 1, n, last ? part : nullptr, st,
-                         last && keep);
+                         last && keep, nullptr, skip);
         w += enc_layer_floats(c, 2 * c, false);
         H = enc_out_size(H, 2);
     }
-    hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, part, enc_tiles(H), (float)(H * H), feats);
+    hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, part, enc_tiles(H), (float)(H * H), feats, skip);
 }

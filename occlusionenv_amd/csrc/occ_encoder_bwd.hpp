@@ -450,7 +450,7 @@ static void enc_train_forward(int img, int dil, bool residual, bool separable, c
     }
     if (bn) return;
     const int Hl = L[15].Ho;
-    hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, F(l.part), enc_tiles(Hl), (float)(Hl * Hl), feats);
+    hipLaunchKernelGGL(occ_enc_pool_kernel, dim3(n), dim3(kEncFeat), 0, st, F(l.part), enc_tiles(Hl), (float)(Hl * Hl), feats, nullptr);
 }
 
 template <int T, int CIB, int COB, int STRIDE>

@@ -681,16 +681,21 @@ extern "C" int occ_encoder_workspace_query(const OccEncoderConfig* cfg, int n_en
     return OCC_OK;
 }
 
-extern "C" int occ_encoder_forward(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
-                                   size_t ws_bytes, float* feats, void* stream) {
+extern "C" int occ_encoder_forward_masked(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env,
+                                          void* ws, size_t ws_bytes, float* feats, const int32_t* skip, void* stream) {
     static_assert(kEncFeat == OCC_ENCODER_FEATURES, "occ_encoder.hpp and the header disagree");
     if (!enc_cfg_ok(cfg) || !packed_weights || !obs || n_env <= 0 || n_env > 65535 || !ws || !feats) return OCC_ERR_ARG;
     size_t need = 0;
     occ_encoder_workspace_query(cfg, n_env, &need);
     if (ws_bytes < need) return OCC_ERR_ARG;
     enc_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, packed_weights, obs, n_env, (char*)ws, feats,
-                (hipStream_t)stream);
+                (hipStream_t)stream, nullptr, skip);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_encoder_forward(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
+                                   size_t ws_bytes, float* feats, void* stream) {
+    return occ_encoder_forward_masked(cfg, packed_weights, obs, n_env, ws, ws_bytes, feats, nullptr, stream);
 }
 
 // ---- segmentation decoder (occ_decoder.hpp) ----------------------------------------------------------------------------
@@ -705,9 +710,9 @@ extern "C" int occ_segment_workspace_query(const OccEncoderConfig* cfg, int n_en
     return OCC_OK;
 }
 
-extern "C" int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
-                                   int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* logit, float* dec_feat,
-                                   void* stream) {
+extern "C" int occ_segment_forward_masked(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed,
+                                          const float* obs, int n_env, void* ws, size_t ws_bytes, float* feats, float* prob,
+                                          float* logit, float* dec_feat, const int32_t* skip, void* stream) {
     if (!enc_cfg_ok(cfg) || cfg->img % 32 != 0 || !enc_packed || !dec_packed || !obs || n_env <= 0 || n_env > 65535 || !ws ||
         !feats || !prob)
         return OCC_ERR_ARG;
@@ -717,8 +722,15 @@ extern "C" int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc
     occ_segment_workspace_query(cfg, n_env, &need);
     if (ws_bytes < need) return OCC_ERR_ARG;
     seg_forward(cfg->img, cfg->dilation, cfg->residual != 0, cfg->separable != 0, enc_packed, dec_packed, obs, n_env, (char*)ws,
-                feats, prob, logit, dec_feat, (hipStream_t)stream);
+                feats, prob, logit, dec_feat, (hipStream_t)stream, skip);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_segment_forward(const OccEncoderConfig* cfg, const float* enc_packed, const float* dec_packed, const float* obs,
+                                   int n_env, void* ws, size_t ws_bytes, float* feats, float* prob, float* logit, float* dec_feat,
+                                   void* stream) {
+    return occ_segment_forward_masked(cfg, enc_packed, dec_packed, obs, n_env, ws, ws_bytes, feats, prob, logit, dec_feat, nullptr,
+                                      stream);
 }
 
 // ---- training (occ_decoder_bwd.hpp, occ_encoder_bwd.hpp, occ_fullnet_bwd.hpp): the argument checks ----------------------

@@ -21,6 +21,12 @@ The segmentation decoder (csrc/occ_decoder.hpp; model.py:109-125,147-150) is pic
 of pretrainer.py:127-141, ``enc.validation_losses(...)`` one batch of ``PreTrainer.val()`` (losses and metrics from one read
 of the maps, csrc/occ_criterion.hpp); both hand on to ``segmentation.py``, the home of everything that consumes a predicted map.
 
+Every forward call takes ``skip=`` and ``out=``: a caller who holds a batch of which only some rows have changed passes an
+(N,) int32 or bool mask on the device, and the rows it marks are left alone (``occ_encoder_forward_masked``,
+``occ_segment_forward_masked``: their blocks return at once, nothing of them is read or written).  With ``out=`` such rows
+keep the bits they held; without it they are zero.  The grid stays sized for N and the mask is read on the device, so the
+host needs no count of the active rows and a captured call follows the mask it finds at replay.
+
 Whole-module checkpoints (``torch.save(model)``, as pretrainer.py writes them) need the reference's ``model.py`` to
 unpickle; with it on the path use ``FrozenEncoder.from_module(torch.load(path, weights_only=False))``.
 """
@@ -210,6 +216,8 @@ class FrozenEncoder:
     Calls are split into chunks of at most ``max_chunk`` envs (one workspace per (chunk size, S), kept and reused);
     every env's features are computed independently, so the chunking changes no bit."""
 
+    takes_skip_mask = True  # ppo.BatchedPPO.features: this encoder is called with skip= and out=
+
     def __init__(self, packed: np.ndarray, separable: bool, dilation: int, residual: bool, preset: str, grad_head=None,
                  heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None, decoder=None,
                  decoder_state: Optional[dict] = None, encoder_state: Optional[dict] = None):
@@ -386,17 +394,63 @@ class FrozenEncoder:
             self._ws[key] = ws
         return ws
 
-    def _forward(self, obs: torch.Tensor, decoder: bool, want_logits: bool = False, want_features: bool = False):
+    @staticmethod
+    def _check_skip(skip, obs: torch.Tensor):
+        """The skip mask of a forward call as a contiguous (N,) int32 tensor (None stays None); ValueError otherwise."""
+        if skip is None:
+            return None
+        if not isinstance(skip, torch.Tensor) or skip.dtype not in (torch.int32, torch.bool):
+            raise ValueError("skip must be an int32 or bool tensor, got " +
+                             (str(skip.dtype) if isinstance(skip, torch.Tensor) else type(skip).__name__))
+        if skip.dim() != 1 or skip.shape[0] != obs.shape[0]:
+            raise ValueError(f"skip must be ({int(obs.shape[0])},), one entry per row of obs, got {tuple(skip.shape)}")
+        if skip.device != obs.device:
+            raise ValueError(f"skip is on {skip.device}, obs on {obs.device}")
+        return skip.detach().to(torch.int32).contiguous()
+
+    @staticmethod
+    def _check_out(name: str, out, shape, device) -> None:
+        """``out`` is a tensor a native call can write rows of in place: f32, contiguous, of ``shape``, on ``device``."""
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+            raise ValueError(f"out ({name}) must be a float32 tensor")
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError(f"out ({name}) must be {tuple(shape)}, got {tuple(out.shape)}")
+        if out.device != device:
+            raise ValueError(f"out ({name}) is on {out.device}, obs on {device}")
+        if not out.is_contiguous():
+            raise ValueError(f"out ({name}) must be contiguous")
+
+    @staticmethod
+    def _out_tuple(out, names) -> tuple:
+        """``out`` of a call that returns ``names`` -> one entry per name (None: no ``out`` given)."""
+        if out is None:
+            return (None,) * len(names)
+        if isinstance(out, torch.Tensor):
+            out = (out,)
+        if not isinstance(out, (tuple, list)) or len(out) != len(names):
+            raise ValueError(f"out must hold {len(names)} tensor(s) in the call's return order ({', '.join(names)})")
+        return tuple(out)
+
+    def _forward(self, obs: torch.Tensor, decoder: bool, want_logits: bool = False, want_features: bool = False, skip=None,
+                 out=(None, None, None, None)):
         """-> (pooled (N,256), prob (N,1,S,S), logits, decoder feature (N,8,S,S)), None for what was not asked for: one
-        occ_segment_forward (``decoder``) or occ_encoder_forward per chunk on the caller's stream."""
+        occ_segment_forward (``decoder``) or occ_encoder_forward per chunk on the caller's stream.  ``skip``: the (N,) mask of
+        rows to leave alone (the ``_masked`` entry points; every chunk takes its slice).  ``out``: the tensors to write into,
+        in the order of the return value (None: a fresh one, zero where a row is skipped); their skipped rows keep their
+        bits.  Everything is checked before anything native runs."""
         img = self._check_obs(obs, decoder)
-        obs = obs.detach().to(torch.float32).contiguous()
         n_all = int(obs.shape[0])
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=obs.device)  # noqa: E731
-        feats = new(n_all, FEATURES)
-        prob = new(n_all, 1, img, img) if decoder else None
-        logits = new(n_all, 1, img, img) if want_logits else None
-        dfeat = new(n_all, CH, img, img) if want_features else None
+        skip = self._check_skip(skip, obs)
+        shapes = ((n_all, FEATURES), (n_all, 1, img, img), (n_all, 1, img, img), (n_all, CH, img, img))
+        wanted = (True, decoder, want_logits, want_features)
+        for name, o, shape, want in zip(("features", "prob", "logits", "decoder feature"), out, shapes, wanted):
+            if o is not None and want:
+                self._check_out(name, o, shape, obs.device)
+        obs = obs.detach().to(torch.float32).contiguous()
+        alloc = torch.empty if skip is None else torch.zeros
+        feats, prob, logits, dfeat = (
+            (alloc(shape, dtype=torch.float32, device=obs.device) if o is None else o) if want else None
+            for o, shape, want in zip(out, shapes, wanted))
         if n_all == 0:
             return feats, prob, logits, dfeat
         lib, cfg, stream = nat.load(), self._cfg(img), nat.stream_ptr(obs.device)
@@ -404,26 +458,53 @@ class FrozenEncoder:
         for lo, n in nat.row_chunks(n_all, self.max_chunk):
             ws = self._workspace("segment" if decoder else "encoder", n, img)
             obs_lo, feats_lo = nat.ptr(obs, lo * 4 * pix), nat.ptr(feats, lo * 4 * FEATURES)
-            if decoder:
+            maps = (nat.ptr(prob, lo * pix), nat.ptr(logits, lo * pix), nat.ptr(dfeat, lo * CH * pix))
+            if decoder and skip is None:
                 nat.check(lib.occ_segment_forward(C.byref(cfg), nat.ptr(self.packed), nat.ptr(self.dec_packed), obs_lo, n, nat.ptr(ws),
-                                                  ws.numel(), feats_lo, nat.ptr(prob, lo * pix), nat.ptr(logits, lo * pix),
-                                                  nat.ptr(dfeat, lo * CH * pix), stream), "occ_segment_forward")
-            else:
+                                                  ws.numel(), feats_lo, *maps, stream), "occ_segment_forward")
+            elif decoder:
+                nat.check(lib.occ_segment_forward_masked(C.byref(cfg), nat.ptr(self.packed), nat.ptr(self.dec_packed), obs_lo, n,
+                                                         nat.ptr(ws), ws.numel(), feats_lo, *maps, nat.ptr(skip, 4 * lo), stream),
+                          "occ_segment_forward_masked")
+            elif skip is None:
                 nat.check(lib.occ_encoder_forward(C.byref(cfg), nat.ptr(self.packed), obs_lo, n, nat.ptr(ws), ws.numel(), feats_lo,
                                                   stream), "occ_encoder_forward")
+            else:
+                nat.check(lib.occ_encoder_forward_masked(C.byref(cfg), nat.ptr(self.packed), obs_lo, n, nat.ptr(ws), ws.numel(),
+                                                         feats_lo, nat.ptr(skip, 4 * lo), stream), "occ_encoder_forward_masked")
         return feats, prob, logits, dfeat
 
     @torch.no_grad()
-    def __call__(self, obs: torch.Tensor) -> torch.Tensor:
-        return self._forward(obs, False)[0]
+    def __call__(self, obs: torch.Tensor, skip=None, out=None) -> torch.Tensor:
+        """The pooled (N,256) feature.  ``skip``: an (N,) int32 or bool tensor on the encoder's device; a row with a non-zero
+        entry is left alone: its blocks return at once and nothing of it is read or written (the mask is read on the device
+        when the kernels run, so a captured call follows the values it finds at replay).  ``out``: the (N,256) f32
+        contiguous tensor to write into, whose skipped rows keep their bits; without it skipped rows of the result are zero."""
+        (o,) = self._out_tuple(out, ("features",))
+        return self._forward(obs, False, skip=skip, out=(o, None, None, None))[0]
+
+    def _masked_head(self, feats: torch.Tensor, skip, out):
+        """``grad_head(feats)`` on all rows (no count of the active ones, no sync); a skipped row keeps the bits of ``out``
+        or, without ``out``, is zero."""
+        g = self.grad_head(feats)
+        if skip is None:
+            return g if out is None else out.copy_(g)
+        keep = (skip != 0).unsqueeze(1)
+        if out is None:
+            return torch.where(keep, torch.zeros_like(g), g)
+        return out.copy_(torch.where(keep, out, g))
 
     @torch.no_grad()
-    def predict_grad(self, obs: torch.Tensor) -> torch.Tensor:
+    def predict_grad(self, obs: torch.Tensor, skip=None, out=None) -> torch.Tensor:
         """(N,2): ``FullNetwork.gradPredictor(pooled)`` (no tanh, model.py:164) or ``tanh(PredictorNet.output(pooled))``
-        (model.py:81-85)."""
+        (model.py:81-85).  ``skip`` as in ``__call__``; ``out``: the (N,2) f32 contiguous tensor to write into."""
         if self.grad_w is None:
             raise ValueError("this checkpoint has no gradPredictor / output head")
-        return self.grad_head(self(obs))
+        (o,) = self._out_tuple(out, ("grad",))
+        if o is not None:
+            self._check_obs(obs, False)
+            self._check_out("grad", o, (int(obs.shape[0]), 2), obs.device)
+        return self._masked_head(self(obs, skip=skip), skip, o)
 
     @torch.no_grad()
     def grad_head(self, feats: torch.Tensor) -> torch.Tensor:
@@ -434,29 +515,38 @@ class FrozenEncoder:
         return torch.tanh(g) if self.grad_tanh else g
 
     # ---- segmentation decoder --------------------------------------------------------------------------------------
-    def _segment(self, obs: torch.Tensor, want_logits: bool, want_features: bool):
+    def _segment(self, obs: torch.Tensor, want_logits: bool, want_features: bool, skip=None, out=(None, None, None, None)):
         """-> (pooled (N,256), prob (N,1,S,S), logits or None, decoder feature (N,8,S,S) or None): one occ_segment_forward
         per chunk on the caller's stream."""
-        return self._forward(obs, True, want_logits, want_features)
+        return self._forward(obs, True, want_logits, want_features, skip, out)
 
     @torch.no_grad()
-    def segment(self, obs: torch.Tensor, return_logits: bool = False, return_features: bool = False):
+    def segment(self, obs: torch.Tensor, return_logits: bool = False, return_features: bool = False, skip=None, out=None):
         """The predicted occlusion map ``sigmoid(segmenter(encoder(obs)))`` (model.py:159), (N,1,S,S) f32; S a multiple of
         32.  With ``return_features`` the (N,8,S,S) decoder feature comes first, as in ``Segmenter.forward`` (model.py:
-        135-140): ``(features, predictions)``; with ``return_logits`` the classifier's output before the sigmoid comes last."""
-        _f, prob, logits, dfeat = self._segment(obs, return_logits, return_features)
-        out = ((dfeat,) if return_features else ()) + (prob,) + ((logits,) if return_logits else ())
-        return out[0] if len(out) == 1 else out
+        135-140): ``(features, predictions)``; with ``return_logits`` the classifier's output before the sigmoid comes last.
+        ``skip`` as in ``__call__``; ``out``: the tensors to write into, a tuple in the order of the return value (a lone
+        tensor when only the map is returned)."""
+        names = (("decoder feature",) if return_features else ()) + ("prob",) + (("logits",) if return_logits else ())
+        given = dict(zip(names, self._out_tuple(out, names)))
+        _f, prob, logits, dfeat = self._segment(obs, return_logits, return_features, skip,
+                                                (None, given.get("prob"), given.get("logits"), given.get("decoder feature")))
+        res = ((dfeat,) if return_features else ()) + (prob,) + ((logits,) if return_logits else ())
+        return res[0] if len(res) == 1 else res
 
     @torch.no_grad()
-    def forward_full(self, obs: torch.Tensor):
+    def forward_full(self, obs: torch.Tensor, skip=None, out=None):
         """``FullNetwork.forward`` (model.py:156-166) from one pass over the encoder: (pooled (N,256), segm (N,1,S,S),
-        grad (N,2)).  The pooled feature is bitwise ``self(obs)``."""
+        grad (N,2)).  The pooled feature is bitwise ``self(obs)``.  ``skip`` as in ``__call__``; ``out``: a tuple
+        (pooled, segm, grad) to write into."""
         if self.grad_w is None:
             raise ValueError("this checkpoint has no gradPredictor / output head")
-        feats, prob, _l, _d = self._segment(obs, False, False)
-        g = torch.addmm(self.grad_b, feats, self.grad_w.t())
-        return feats, prob, (torch.tanh(g) if self.grad_tanh else g)
+        o_feats, o_prob, o_grad = self._out_tuple(out, ("features", "prob", "grad"))
+        if o_grad is not None:
+            self._check_obs(obs, True)
+            self._check_out("grad", o_grad, (int(obs.shape[0]), 2), obs.device)
+        feats, prob, _l, _d = self._segment(obs, False, False, skip, (o_feats, o_prob, None, None))
+        return feats, prob, self._masked_head(feats, skip, o_grad)
 
     def occlusion_metrics(self, pred: torch.Tensor, target: torch.Tensor) -> dict:
         """The judgement of pretrainer.py:133-141 on a batch: both maps thresholded at 0.5; per-env int64 counts

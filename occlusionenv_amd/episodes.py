@@ -11,7 +11,8 @@ stop (``SimpleVecEnv.step`` would reset it), so the loop drives the engine itsel
 skip=skip)``, the controller's network if it has one, and one ``occ_episode_advance`` launch (csrc/occ_episode.hpp) that does
 on the device what the reference's loops do on the host - the update of the action, the NaN test of the raw gradient, the
 traces, the ``finished`` / step-cap test - and freezes the envs that are through: their row of ``skip`` is set, and the next
-step's launch leaves them alone.  Nothing on the host reads a device value inside a step.
+step's launch leaves them alone.  The network takes the same mask (``enc(obs, skip=, out=)``): a frozen env's blocks return at
+once and its features keep their bits.  Nothing on the host reads a device value inside a step.
 
 ``write_iterations`` writes the counts as the reference's ``iterations_{raw,random,model,rl}_3.txt``, which its
 ``BayesianTTest.py``, ``plotter.py`` and ``iterator_diagram.py`` read; ``summarise_iterations`` gives the plain statistics.
@@ -140,7 +141,7 @@ def _run(eng, ctrl, max_step: int, az, gen, poll_every: int, trace: bool) -> dic
     ep = _Episodes(N, max_step, dev, first, trace)
     want_grad = ctrl.rule == nat.EPISODE_GRADIENT
     ones = {}
-    feats_all = None
+    feats_all = feats_work = None
     steps = polls = compactions = row_steps = 0
     for i in range(max_step):
         rows, w = ep.rows, int(ep.action.shape[0])
@@ -157,15 +158,22 @@ def _run(eng, ctrl, max_step: int, az, gen, poll_every: int, trace: bool) -> dic
             noise = _randn(N, gen, dev)
             noise = noise if rows is None else noise[rows]
         else:
-            # The network runs on the working set (it has no skip mask; rows of frozen envs hold anything and are not read).
+            # The network runs on the working set under the mask the engine step of this iteration took (ep.skip before
+            # advance changes it): the blocks of a frozen env return at once, and its row of features keeps the bits it
+            # held, in a buffer of the working set's rows (gathered from feats_all after every compaction).
             # The heads always run on all N rows of features, frozen ones kept from before, and the agent's noise is drawn
             # for all N: what a row gets then does not depend on who else is still in the working set.
             with torch.no_grad():
-                f = ctrl.enc(obs) if ctrl.rule == nat.EPISODE_MODEL else ctrl.agent.features(obs)
-                if rows is None:
-                    feats_all = f
+                net = ctrl.enc if ctrl.rule == nat.EPISODE_MODEL else ctrl.agent.features
+                if feats_all is None:
+                    feats_all = net(obs, skip=ep.skip)  # (the first step: nobody is frozen yet)
+                elif rows is None:
+                    net(obs, skip=ep.skip, out=feats_all)
                 else:
-                    feats_all.index_copy_(0, rows, f)
+                    if feats_work is None:
+                        feats_work = feats_all[rows]
+                    net(obs, skip=ep.skip, out=feats_work)
+                    feats_all.index_copy_(0, rows, feats_work)
                 if ctrl.rule == nat.EPISODE_MODEL:
                     pred = ctrl.enc.grad_head(feats_all)
                 else:
@@ -181,6 +189,7 @@ def _run(eng, ctrl, max_step: int, az, gen, poll_every: int, trace: bool) -> dic
             if 2 * left < w:  # a long tail of unfinished envs does not pay for the whole batch
                 ep.compact(torch.nonzero(ep.active).reshape(-1))
                 compactions += 1
+                feats_work = None  # (the working set has changed: its feature rows are gathered anew)
     res = ep.write_back()
     eng.check_status()  # (a host sync: the clock below has seen the last launch finish)
     seconds = time.perf_counter() - t0
@@ -208,7 +217,8 @@ def evaluate_controllers(venv, controllers, max_step: int = 50, azimuth=None, sc
     ``randn(N, 2)`` per step for the whole batch whoever is still active; the agent's sampling draws for all N envs as well
     (for an ``Agent``, ``generator`` must live on the agent's device, as for ``select_action``).  Every ``poll_every`` steps the
     host reads one int, the number of envs still active: at zero the loop ends, and when fewer than half of the rows it
-    works on are active it goes on with those alone (``engine.step(env_ids=...)``, the network on that subset).  The results
+    works on are active it goes on with those alone (``engine.step(env_ids=...)``, the network on that subset; between polls
+    the network skips the frozen rows of the working set through its ``skip`` mask).  The results
     are the same, bit for bit, for every ``poll_every``.
 
     Per controller a dict: ``iterations`` (N,) int64, the reference's ``i + 1`` at ``finished`` or at the cap ``max_step``;

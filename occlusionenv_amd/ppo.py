@@ -96,7 +96,9 @@ class BatchedPPO:
         """``encoder``: any callable obs (N,4,S,S) -> features (N,256), run under no_grad - the socket for the frozen
         encoder whose pooled features the reference stores (PPO.py:47,155-157: ``FullNetwork.forward``'s first output,
         model.py:157-166), e.g. ``encoder.FrozenEncoder`` (``from_fullnetwork``).  Default: ``rollout.pooled_features``
-        (8x8 average pooling)."""
+        (8x8 average pooling).  An encoder that can leave rows alone itself says so with an attribute ``takes_skip_mask =
+        True`` and is then called as ``encoder(obs, skip=, out=)`` (``FrozenEncoder`` does); any other callable is only
+        ever called as ``encoder(obs)`` (``features``)."""
         self.encoder = encoder
         self.gamma, self.eps_clip, self.K_epochs = gamma, eps_clip, K_epochs
         self.action_std = action_std_init
@@ -154,19 +156,46 @@ class BatchedPPO:
         return agent
 
     # ---- acting (PPO.py:152-164) ------------------------------------------------------------
-    def features(self, obs: torch.Tensor) -> torch.Tensor:
-        """obs (N,4,S,S) -> the (N,256) features the heads act on."""
+    def features(self, obs: torch.Tensor, skip=None, out=None) -> torch.Tensor:
+        """obs (N,4,S,S) -> the (N,256) features the heads act on.  ``skip``: an (N,) int32 or bool mask of rows to leave
+        alone, ``out``: the (N,256) f32 contiguous tensor to write into, both as in ``encoder.FrozenEncoder.__call__``: a
+        skipped row keeps the bits of ``out`` or, without ``out``, is zero.  An encoder with ``takes_skip_mask`` (a
+        ``FrozenEncoder``) gets both and skips the work of such a row; any other encoder, and the pooled path without one, is
+        called as before, on every row, and the contract is honoured afterwards."""
+        if skip is None and out is None:
+            return self._all_rows(obs)
+        if self.encoder is not None and getattr(self.encoder, "takes_skip_mask", False):
+            with torch.no_grad():
+                return self._checked(self.encoder(obs, skip=skip, out=out), obs)
+        from .encoder import FrozenEncoder
+
+        if skip is not None:
+            skip = FrozenEncoder._check_skip(skip, obs)
+        if out is not None:
+            FrozenEncoder._check_out("features", out, (int(obs.shape[0]), 256), obs.device)
+        feats = self._all_rows(obs)
+        if skip is not None:
+            keep = (skip != 0).unsqueeze(1)
+            feats = torch.where(keep, torch.zeros_like(feats) if out is None else out, feats)
+        return feats if out is None else out.copy_(feats)
+
+    def _all_rows(self, obs: torch.Tensor) -> torch.Tensor:
+        """The features of every row: the encoder called as ``encoder(obs)``, or the 8x8 pooling."""
         if self.encoder is None:
             return rollout.pooled_features(obs)
         with torch.no_grad():  # PPO.py:154: the encoder is frozen
-            feats = self.encoder(obs)
+            return self._checked(self.encoder(obs), obs)
+
+    @staticmethod
+    def _checked(feats: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
         if feats.shape != (obs.shape[0], 256):
             raise ValueError(f"the encoder must map (N,4,S,S) to (N,256) features, got {tuple(feats.shape)}")
         return feats.detach().to(torch.float32).contiguous()
 
-    def select_action(self, obs: torch.Tensor, generator: Optional[torch.Generator] = None):
-        """obs (N,4,S,S) -> (features, action, logprob) from the OLD policy."""
-        feats = self.features(obs)
+    def select_action(self, obs: torch.Tensor, generator: Optional[torch.Generator] = None, skip=None):
+        """obs (N,4,S,S) -> (features, action, logprob) from the OLD policy.  ``skip`` as in ``features``: the features of
+        a skipped row are zero; the noise is drawn for all N rows, so what the other rows get does not depend on the mask."""
+        feats = self.features(obs, skip=skip)
         action, logprob = self.policy_old.act(feats, generator)
         return feats, action, logprob
 
