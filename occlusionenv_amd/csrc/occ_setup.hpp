@@ -412,9 +412,14 @@ __device__ __forceinline__ void world_corner(const float* __restrict__ pool_vert
     w[2] = pv[2] + oz;
 }
 
+// The order of the roundings is spelled out.  Written as w0 R0 + w1 R3 + w2 R6 + T the contraction into FMAs was the
+// compiler's choice per call site, and it chose differently for the third vertex of occ_setup_kernel<true> (w0 R0 rounded,
+// w1 R3 fused) than everywhere else (w1 R3 rounded, w0 R0 fused): a step with gradients and one without wrote records one
+// ulp apart in that vertex for a fifth of the faces.  This is the form every other site had.
 __device__ __forceinline__ void view_pos(const CamRT& c, const float* w, VVert& q) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) q.v[j] = w[0] * c.R[j] + w[1] * c.R[3 + j] + w[2] * c.R[6 + j] + c.T[j];
+    for (int j = 0; j < 3; ++j)
+        q.v[j] = __fadd_rn(fmaf(w[2], c.R[6 + j], fmaf(w[0], c.R[j], __fmul_rn(w[1], c.R[3 + j]))), c.T[j]);
 }
 template <bool GRAD>
 __device__ __forceinline__ void view_from_world(const CamRT& c, const float* w, VVert& q) {

@@ -307,6 +307,30 @@ def snapshot_records(eng):
     return out
 
 
+def tracked_buffers_hold_background(eng):
+    """The invariant region tracking rests on (OccRenderOut.rect_prev): outside rect[e] the obs / full_state rows of every
+    persistent output set of ``eng`` are background, and the alphas state is zero outside its own rects.  Checked on the
+    device, reserve rows included; raises AssertionError.  Returns, per output set, (pixels inside the rects, all pixels)."""
+    S = eng.S
+    ys, xs = torch.meshgrid(torch.arange(S, device="cuda"), torch.arange(S, device="cuda"), indexing="ij")
+
+    def outside(rect):
+        r = rect.long()
+        return ~((xs[None] >= r[:, 0, None, None]) & (xs[None] <= r[:, 2, None, None]) & (ys[None] >= r[:, 1, None, None]) &
+                 (ys[None] <= r[:, 3, None, None]))
+
+    inside = []
+    for slot in eng._ring or []:
+        out = outside(slot["rect"][slot["cur"]])  # (NT,S,S)
+        obs, fs = slot["obs"], slot["fs"]
+        assert bool((obs[:, :3].permute(0, 2, 3, 1)[out] == 1.0).all()) and bool((obs[:, 3][out] == -1.0).all())
+        assert bool((fs[out] == torch.tensor([3.0, 3.0, 3.0, 0.0], device="cuda")).all())
+        inside.append((int((~out).sum()), out.numel()))
+    outa = outside(eng._arect[eng._arect_cur])
+    assert bool((eng._alphas_all.permute(0, 2, 3, 1)[outa] == 0.0).all())
+    return inside
+
+
 def face_noise_bounds(fv_unclipped) -> np.ndarray:
     """Per ORIGINAL face: bound on the NDC displacement of any vertex of the face (or of its z-clipped pieces) under
     view-space coordinate noise TVIEW (module docstring, NEAR AND Z-CLIPPED FACES); never below TVERT."""

@@ -141,22 +141,12 @@ def test_ring_sets_hold_background_outside_their_rects(ds):
     N, S = 32, 64
     venv = _make_venv(ds, N, S, ring=2)
     _rollout(venv, 9, {2: [1, 2, 3], 6: [7]})
-    eng = venv.engine
-    ys, xs = torch.meshgrid(torch.arange(S, device="cuda"), torch.arange(S, device="cuda"), indexing="ij")
+    from tests.parity_utils import tracked_buffers_hold_background
 
-    def outside(rect):
-        r = rect.long()
-        return ~((xs[None] >= r[:, 0, None, None]) & (xs[None] <= r[:, 2, None, None]) & (ys[None] >= r[:, 1, None, None]) &
-                 (ys[None] <= r[:, 3, None, None]))
-
-    for slot in eng._ring:
-        out = outside(slot["rect"][slot["cur"]])  # (NT,S,S)
-        obs, fs = slot["obs"], slot["fs"]
-        assert bool((obs[:, :3].permute(0, 2, 3, 1)[out] == 1.0).all()) and bool((obs[:, 3][out] == -1.0).all())
-        assert bool((fs[out] == torch.tensor([3.0, 3.0, 3.0, 0.0], device="cuda")).all())
-        assert int((~out).sum()) < out.numel()  # and the rects are not simply everything
-    outa = outside(eng._arect[eng._arect_cur])
-    assert bool((eng._alphas_all.permute(0, 2, 3, 1)[outa] == 0.0).all())
+    inside = tracked_buffers_hold_background(venv.engine)
+    assert len(inside) == 2
+    for n_in, n_all in inside:
+        assert n_in < n_all  # and the rects are not simply everything
 
 
 def test_fused_step_equals_the_separate_calls(ds):
