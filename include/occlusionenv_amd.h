@@ -1078,6 +1078,61 @@ int occ_episode_advance(const uint8_t* done, const float* reward, const float* f
                         int32_t* nan_steps, float* trace_reward, float* trace_full_reward, int32_t* report, void* stream);
 
 /*
+ * The PPO training loop on the device (additive in ABI 12; csrc/occ_rollout.hpp, tests/rollout_model.py): what
+ * trainRL.py:189-247 and PPO.py:152-188 do on the host around every env.step, for n_env envs per launch.  All three:
+ * one launch on `stream`, no atomics, nothing allocated or synchronised, OCC_ERR_ARG before the launch.
+ *
+ * occ_ppo_act (one wave per env): the old policy's action for feats (n,256) f32 -
+ *   mean = feats w_a^T + b_a  (w_a (2,256), b_a (2));  action = fadd(mean, fmul(noise, action_std))  (noise (n,2): the
+ *   caller's standard normal draws);  logprob = -0.5 sum_j (a_j - mean_j)^2 / var - 0.5 (2 log 2 pi + 2 log var), with
+ *   var = action_std^2 in f32 - in the lane partition, reduction and expressions of occ_ppo_update's epoch, so that the
+ *   epoch recomputes the same mean and quadratic term for the sample when it is given the same f32 var; the constant is
+ *   rounded once from double here (occ_ppo_update sums it in f32, which loses up to 1e-7 where the logarithms cancel).
+ *   action (n,2) and logprob (n) are written, mean (n,2) if not NULL.  feat_buf (T,n,256), action_buf (T,n,2),
+ *   logprob_buf (T,n): all three or none; row t of each also receives the env's feature row, action and logprob.
+ *   Row e of every output depends on row e of the inputs only.  OCC_ERR_ARG: a null pointer among the required ones,
+ *   n_env < 1, action_std <= 0 (or NaN), some but not all buffers, or with buffers T < 1 or t outside [0, T).
+ *
+ * occ_rollout_advance (one block), after the step's occ_auto_reset: reward (n) f32, done (n) u8, code (n) int32 with
+ *   0 = the episode goes on, 1 = it ended done, 2 = it ended by the time limit (the first n_env words of occ_auto_reset's
+ *   report).  Per env: ep_return = fadd(ep_return, reward), ep_len += 1, and with rewards / dones ((T,n) f32, both or
+ *   neither) rewards[t,e] = reward[e], dones[t,e] = done[e] ? 1 : 0.  Then for every env with code != 0, in env-index
+ *   order: running = the first episode ever ? return : fadd(fmul(0.95f, running), fmul(0.05f, return)) (trainRL.py:236),
+ *   entry (env, ep_return, ep_len, code, timestep, running) goes to slot (n_episodes % cap) of the ring, n_episodes += 1,
+ *   code_counts[code - 1] += 1, sums += (return, length) in f64, and the env's ep_return / ep_len restart at zero.
+ *   Entries the host has not read when n_episodes passes them by cap are overwritten.  OCC_ERR_ARG: a null pointer among
+ *   reward / done / code / the state, n_env < 1, cap < 1, one buffer without the other, or with buffers T < 1 or t
+ *   outside [0, T).
+ *
+ * occ_ppo_returns (one block): rewards, dones (T,n) f32 -> per env the reversed scan of PPO.py:178-185,
+ *   running = fadd(r, fmul(fmul(gamma, running), 1 - done)), to raw_returns (T n) if not NULL; stats[0] = mean and
+ *   stats[1] = unbiased standard deviation of the M = T n returns in f64 (two passes, a summation order fixed by M);
+ *   returns (M) = fdiv(fsub(ret, (float)mean), fadd((float)std, 1e-7f)), the tensor occ_ppo_update takes.
+ *   OCC_ERR_ARG: a null pointer (raw_returns may be NULL), T < 1, n_env < 1 or M < 2 (the deviation is undefined).
+ */
+typedef struct OccRolloutState {
+    float* ep_return;             /* (n_env) */
+    int32_t* ep_len;              /* (n_env) */
+    int32_t* ring_env;            /* (cap) each */
+    float* ring_return;
+    int32_t* ring_length;
+    int32_t* ring_code;
+    int64_t* ring_timestep;
+    float* ring_running;          /* the running reward after the entry's episode */
+    int64_t* n_episodes;         /* (1) every completion ever */
+    int64_t* code_counts;         /* (2) ended done, ended by the time limit */
+    double* sums;                 /* (2) sum of the completed returns, of their lengths */
+    float* running;               /* (1) the running reward */
+} OccRolloutState;
+int occ_ppo_act(const float* feats, const float* w_a, const float* b_a, const float* noise, float action_std, int n_env,
+                float* action, float* logprob, float* mean, float* feat_buf, float* action_buf, float* logprob_buf, int t,
+                int T, void* stream);
+int occ_rollout_advance(const float* reward, const uint8_t* done, const int32_t* code, int n_env, int t, int T,
+                        int64_t timestep, float* rewards, float* dones, const OccRolloutState* state, int cap, void* stream);
+int occ_ppo_returns(const float* rewards, const float* dones, int T, int n_env, float gamma, float* returns,
+                    float* raw_returns, double* stats, void* stream);
+
+/*
  * Measurement hooks (bench.py only; not part of the reference surface).  While enabled, occ_render
  * brackets its dominant kernel (occ_raster2_kernel) with HIP events on the launch stream.
  * occ_profile_read synchronises the recorded events (host sync!), returns the summed duration in

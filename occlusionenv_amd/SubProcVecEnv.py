@@ -164,9 +164,22 @@ class SimpleVecEnv(VecEnv):
         # set is not overwritten before the side stream that still reads it - RecordExchange packs step k's records while
         # step k + 1 renders - is done); _last_set = the set of the previous step
         self._last_set = None
+        self._codes = None                  # episode_end_codes of the last step
 
     def step_async(self, actions):
         self.actions = actions
+
+    @property
+    def episode_end_codes(self) -> torch.Tensor:
+        """How the last step ended every env's episode, as an (N,) int32 device tensor: 0 = it goes on, 1 = done, 2 =
+        reset by the time limit (``max_ep_len``; ``dones`` stays False and ``infos[i]["TimeLimit.truncated"]`` is set).
+        With the reserve this is a view of the auto-reset report the step's pairing launch wrote on the device (nothing is
+        copied or waited for); without one it is built from the flags the step read back anyway.  Read-only, and valid
+        until the next step.  What ``monitor.EpisodeMonitor.advance`` takes: a time-limit reset is in neither ``rewards``
+        nor ``dones``."""
+        if self._codes is None:
+            raise RuntimeError("episode_end_codes: no step has run yet")
+        return self._codes
 
     def use_output_ring(self, k: int) -> None:
         """Switch the engine to k >= 2 persistent output sets (0: back to fresh tensors every step).  Needs the reserve
@@ -375,6 +388,7 @@ class SimpleVecEnv(VecEnv):
             pend = eng.auto_reset(out)
             infos = _LazyInfos(out["pos"], full_state, loss, resolve=self._drain)
             self._pending = (pend, obs, out, infos)
+            self._codes = pend["report"][:N]
             # new candidate scenes for the slots emptied one step ago: off the critical path (the GPU is busy
             # with this step); they are rendered from the next step on
             self._refill_reserve(empty)
@@ -391,12 +405,15 @@ class SimpleVecEnv(VecEnv):
         if fl[-1]:
             eng.check_status()
         fin = fl[:N] != 0
+        codes = fin.astype(np.int32)
         self._age_host += 1
         if self.max_ep_len:  # the time limit (trainRL.py:191-229): reset, not done
             expired = (self._age_host >= int(self.max_ep_len)) & ~fin
             for i in np.nonzero(expired)[0].tolist():
                 infos.set(i, "TimeLimit.truncated", True)
+            codes[expired] = 2
             fin = fin | expired
+        self._codes = torch.from_numpy(codes).to(eng.device)
         fin_l = np.nonzero(fin)[0].tolist()
         if fin_l:
             # save final observation where user can get it, then reset (SubProcVecEnv.py:211-214)

@@ -141,6 +141,12 @@ class OccPpoState(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w_a", "b_a", "w_v", "b_v", "adam_m", "adam_v", "adam_step")]
 
 
+class OccRolloutState(C.Structure):
+    """include/occlusionenv_amd.h: OccRolloutState (episode accumulators, ring and totals of occ_rollout_advance)."""
+    _fields_ = [(n, C.c_void_p) for n in ("ep_return", "ep_len", "ring_env", "ring_return", "ring_length", "ring_code",
+                                          "ring_timestep", "ring_running", "n_episodes", "code_counts", "sums", "running")]
+
+
 PPO_FEATURES = 256
 PPO_PARAMS = 3 * PPO_FEATURES + 3
 PPO_SCRATCH_FLOATS = 128 * (PPO_PARAMS + 2)  # for the default OCC_PPO_MAX_BLOCKS; ppo_scratch_floats() asks the library
@@ -274,6 +280,10 @@ SYMBOLS = {
     "occ_seg_criterion_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "occ_episode_advance": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "occ_ppo_act": (C.c_int, [C.c_void_p] * 4 + [C.c_float, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    "occ_rollout_advance": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.POINTER(OccRolloutState), C.c_int, C.c_void_p]),
+    "occ_ppo_returns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 4),
     "occ_profile_enable": (C.c_int, [C.c_int]),
     "occ_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

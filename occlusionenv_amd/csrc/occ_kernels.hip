@@ -94,6 +94,7 @@ namespace occ {
 #include "occ_datapack.hpp"
 #include "occ_resize.hpp"
 #include "occ_jpeg.hpp"
+#include "occ_rollout.hpp"
 #include "occ_episode.hpp"
 
 }  // namespace occ
@@ -651,6 +652,59 @@ extern "C" int occ_episode_advance(const uint8_t* done, const float* reward, con
                   finished, nan_steps, trace_reward, trace_full_reward, report};
     const int threads = n_env >= 1024 ? 1024 : ((n_env + 63) & ~63);
     hipLaunchKernelGGL(occ_episode_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_ppo_act(const float* feats, const float* w_a, const float* b_a, const float* noise, float action_std,
+                           int n_env, float* action, float* logprob, float* mean, float* feat_buf, float* action_buf,
+                           float* logprob_buf, int t, int T, void* stream) {
+    if (!feats || !w_a || !b_a || !noise || !(action_std > 0.f) || n_env <= 0 || !action || !logprob) return OCC_ERR_ARG;
+    const bool buffered = feat_buf || action_buf || logprob_buf;
+    if (buffered && (!feat_buf || !action_buf || !logprob_buf || T <= 0 || t < 0 || t >= T)) return OCC_ERR_ARG;
+    PpoActArgs A;
+    A.feats = feats; A.w_a = w_a; A.b_a = b_a; A.noise = noise; A.action_std = action_std; A.n = n_env;
+    // The variance is the f32 square, and 1 / var the f32 quotient occ_ppo_update forms from a variance it is given: the
+    // quadratic term is then the epoch's, bit for bit.  The constant is formed in double and rounded once: near std = 0.4
+    // the two logarithms cancel (the constant passes through zero), and occ_ppo_update's f32 sum is then a hundred ulps of
+    // the constant off - 4e-8 in absolute terms, which is all the first epoch's recomputed log-probability differs by.
+    const float action_var = action_std * action_std;
+    A.inv_var = 1.0f / action_var;
+    A.lp_const = (float)(-0.5 * (2.0 * 1.8378770664093453 + 2.0 * log((double)action_var)));
+    A.action = action; A.logprob = logprob; A.mean = mean;
+    A.feat_buf = feat_buf; A.action_buf = action_buf; A.logprob_buf = logprob_buf;
+    A.row0 = buffered ? (long long)t * n_env : 0;
+    hipLaunchKernelGGL(occ_ppo_act_kernel, dim3((n_env + kActWaves - 1) / kActWaves), dim3(64 * kActWaves), 0, (hipStream_t)stream, A);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_rollout_advance(const float* reward, const uint8_t* done, const int32_t* code, int n_env, int t, int T,
+                                   int64_t timestep, float* rewards, float* dones, const OccRolloutState* state, int cap,
+                                   void* stream) {
+    if (!reward || !done || !code || n_env <= 0 || cap <= 0 || !state) return OCC_ERR_ARG;
+    if (!state->ep_return || !state->ep_len || !state->ring_env || !state->ring_return || !state->ring_length ||
+        !state->ring_code || !state->ring_timestep || !state->ring_running || !state->n_episodes || !state->code_counts || !state->sums || !state->running)
+        return OCC_ERR_ARG;
+    const bool buffered = rewards || dones;
+    if (buffered && (!rewards || !dones || T <= 0 || t < 0 || t >= T)) return OCC_ERR_ARG;
+    RolloutArgs a;
+    a.reward = reward; a.done = done; a.code = code; a.n = n_env; a.cap = cap;
+    a.row0 = buffered ? (long long)t * n_env : 0;
+    a.timestep = (long long)timestep;
+    a.rewards = rewards; a.dones = dones; a.ep_return = state->ep_return; a.ep_len = state->ep_len;
+    a.ring_env = state->ring_env; a.ring_return = state->ring_return; a.ring_length = state->ring_length;
+    a.ring_code = state->ring_code; a.ring_timestep = (long long*)state->ring_timestep; a.ring_running = state->ring_running;
+    a.n_episodes = (long long*)state->n_episodes; a.code_counts = (long long*)state->code_counts;
+    a.sums = state->sums; a.running = state->running;
+    // (always 16 waves: block_prefix_1024 adds up the counts of all sixteen)
+    hipLaunchKernelGGL(occ_rollout_advance_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
+}
+
+extern "C" int occ_ppo_returns(const float* rewards, const float* dones, int T, int n_env, float gamma, float* returns,
+                               float* raw_returns, double* stats, void* stream) {
+    if (!rewards || !dones || !returns || !stats || T <= 0 || n_env <= 0 || (int64_t)T * n_env < 2) return OCC_ERR_ARG;
+    ReturnsArgs a{rewards, dones, T, n_env, gamma, returns, raw_returns, stats};
+    hipLaunchKernelGGL(occ_ppo_returns_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 

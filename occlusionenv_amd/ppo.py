@@ -18,6 +18,12 @@ On the GPU the K epochs of an update run in the library (``occ_ppo_update``, csr
 does forward, loss, backward and the Adam step over the 771 parameters (80 epochs over 12 800 samples: 1.3 ms instead
 of 35 ms of framework launches).  ``fused=False`` keeps the torch implementation (the reference for the tests, and the
 CPU path of the gloo rehearsals).
+
+``train_ppo`` is the reference's whole training loop (trainRL.py:165-250: rollouts, updates, action-std decay,
+checkpoints and the episode log) on one rank: acting is one launch that also fills the step's row of a ``RolloutBuffer``
+(``act_into``, ``occ_ppo_act``), the episode bookkeeping another (``monitor.EpisodeMonitor``, ``occ_rollout_advance``), and
+``update_from`` runs ``occ_ppo_returns`` and ``occ_ppo_update`` on the buffer's own tensors (csrc/occ_rollout.hpp).
+``train_rollouts`` stays the loop of the multi-rank rollout and of the torch path.
 """
 from __future__ import annotations
 
@@ -83,6 +89,29 @@ class ActorCriticHeads(nn.Module):
         value = self.value_head(feats).squeeze(-1)
         lp, ent = self._logprob_entropy(mean, action)
         return lp, value, ent
+
+
+class RolloutBuffer:
+    """The rollout of T vector steps of n envs as five contiguous tensors (PPO.py:13-33's lists): ``feats`` (T,n,256),
+    ``actions`` (T,n,2), ``logprobs`` (T,n), ``rewards`` (T,n), ``dones`` (T,n) as 0.0 / 1.0.  ``BatchedPPO.act_into``
+    writes the first three of a step, ``monitor.EpisodeMonitor.advance`` the other two; ``BatchedPPO.update_from`` hands
+    them to the library as they are."""
+
+    def __init__(self, T: int, n: int, device):
+        if T <= 0 or n <= 0:
+            raise ValueError("RolloutBuffer needs T >= 1 and n >= 1")
+        self.T, self.n = int(T), int(n)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.feats = torch.zeros(self.T, self.n, 256, **f32)
+        self.actions = torch.zeros(self.T, self.n, 2, **f32)
+        self.logprobs = torch.zeros(self.T, self.n, **f32)
+        self.rewards = torch.zeros(self.T, self.n, **f32)
+        self.dones = torch.zeros(self.T, self.n, **f32)
+
+    def records(self) -> torch.Tensor:
+        """The (T,n,261) record layout of ``rollout.pack_records`` (a copy; for callers of the older interface)."""
+        return torch.cat([self.feats, self.actions, self.logprobs.unsqueeze(-1), self.rewards.unsqueeze(-1),
+                          self.dones.unsqueeze(-1)], dim=-1)
 
 
 class BatchedPPO:
@@ -199,6 +228,61 @@ class BatchedPPO:
         action, logprob = self.policy_old.act(feats, generator)
         return feats, action, logprob
 
+    def _need_fused(self, what: str) -> None:
+        if not self.fused:
+            raise nat.NativeError(f"{what} runs in the HIP library on CUDA/ROCm tensors only (fused=True); the torch path is "
+                                  "select_action / update")
+
+    def act_into(self, obs: torch.Tensor, buf: "RolloutBuffer", t: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """``select_action`` with the heads, the sample and the log-probability in ONE launch (``occ_ppo_act``,
+        csrc/occ_rollout.hpp), which also writes the acting state's features, the action and the log-probability into row
+        ``t`` of ``buf``.  The features are computed as in ``select_action`` and the noise is the same ``torch.randn`` draw
+        from ``generator``; the arithmetic of mean and log-probability is the update kernel's, not torch's, so the two
+        ways of acting agree to rounding, not in every bit.  Returns the (N,2) action."""
+        self._need_fused("act_into")
+        return self.act_features_into(self.features(obs), buf, t, generator)
+
+    def act_features_into(self, feats: torch.Tensor, buf: "RolloutBuffer", t: int,
+                          generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """``act_into`` for a caller that already holds the (N,256) f32 contiguous features of the acting state."""
+        self._need_fused("act_into")
+        n = int(feats.shape[0])
+        if feats.shape != (n, nat.PPO_FEATURES) or feats.dtype != torch.float32 or not feats.is_contiguous():
+            raise ValueError("act_features_into: the features must be a contiguous (N,256) float32 tensor")
+        if not 0 <= t < buf.T or buf.n != n or buf.feats.device != feats.device:
+            raise ValueError(f"act_into: step {t} of a ({buf.T}, {buf.n}) buffer on {buf.feats.device} for {n} envs on {feats.device}")
+        head = self.policy_old.action_head
+        if head.weight.shape != (2, nat.PPO_FEATURES):
+            raise nat.NativeError("occ_ppo_act is built for 256 features and 2 action components (PPO.py / model.py)")
+        noise = torch.randn((n, 2), device=feats.device, dtype=torch.float32, generator=generator)
+        action = torch.empty(n, 2, dtype=torch.float32, device=feats.device)
+        logprob = torch.empty(n, dtype=torch.float32, device=feats.device)
+        with torch.no_grad():
+            nat.check(nat.load().occ_ppo_act(nat.ptr(feats), nat.ptr(head.weight), nat.ptr(head.bias), nat.ptr(noise),
+                                             float(self.action_std), n, nat.ptr(action), nat.ptr(logprob), None,
+                                             nat.ptr(buf.feats), nat.ptr(buf.actions), nat.ptr(buf.logprobs), int(t), buf.T,
+                                             nat.stream_ptr(feats.device)), "occ_ppo_act")
+        return action
+
+    def update_from(self, buf: "RolloutBuffer") -> dict:
+        """``update`` on a full ``RolloutBuffer``: ``occ_ppo_returns`` (one launch: the Monte-Carlo returns of
+        PPO.py:178-185 and their normalisation, statistics in f64) and then ``occ_ppo_update`` on the buffer's own
+        tensors - no stack, no slice, no copy.  Ends as ``update`` ends: ``policy_old`` synchronised, the same stats dict."""
+        self._need_fused("update_from")
+        import numpy as np
+
+        M = buf.T * buf.n
+        dev = buf.feats.device
+        returns = torch.empty(M, dtype=torch.float32, device=dev)
+        self._return_stats = torch.empty(2, dtype=torch.float64, device=dev)  # (mean, std) of the raw returns, on the device
+        nat.check(nat.load().occ_ppo_returns(nat.ptr(buf.rewards), nat.ptr(buf.dones), buf.T, buf.n, float(self.gamma),
+                                             nat.ptr(returns), None, nat.ptr(self._return_stats), nat.stream_ptr(dev)),
+                  "occ_ppo_returns")
+        std32 = np.float32(self.action_std)
+        losses, vlosses = self._fused_epochs(buf.feats.view(M, 256), buf.actions.view(M, 2), buf.logprobs.view(M), returns,
+                                             action_var=float(std32 * std32))
+        return self._finish_update(losses, vlosses, M)
+
     def store(self, record: torch.Tensor) -> None:
         self.records.append(record)
 
@@ -282,8 +366,10 @@ class BatchedPPO:
                     vlosses.append(v)
         return self._finish_update(torch.stack(losses), torch.stack(vlosses), int(feats.shape[0]))
 
-    def _fused_epochs(self, feats, actions, old_lp, returns):
-        """The K epochs in the library (csrc/occ_ppo.hpp): parameters and Adam state are updated in place."""
+    def _fused_epochs(self, feats, actions, old_lp, returns, action_var: Optional[float] = None):
+        """The K epochs in the library (csrc/occ_ppo.hpp): parameters and Adam state are updated in place.
+        ``action_var``: the variance to pass instead of ``action_std ** 2`` (``update_from``: the f32 square that
+        ``occ_ppo_act`` used)."""
         pol, st = self.policy, self._fused_state
         if feats.shape[1] != nat.PPO_FEATURES or pol.action_dim != 2:
             raise nat.NativeError("occ_ppo_update is built for 256 features and 2 action components (PPO.py / model.py)")
@@ -301,7 +387,7 @@ class BatchedPPO:
         with torch.no_grad():
             nat.check(nat.load().occ_ppo_update(
                 nat.ptr(feats), nat.ptr(actions), nat.ptr(old_lp), nat.ptr(returns), int(feats.shape[0]),
-                float(self.action_std) ** 2, float(self.eps_clip), float(g_a["lr"]), float(g_v["lr"]), float(b1), float(b2),
+                float(self.action_std) ** 2 if action_var is None else float(action_var), float(self.eps_clip), float(g_a["lr"]), float(g_v["lr"]), float(b1), float(b2),
                 float(g_a["eps"]), C.byref(ps), int(self.K_epochs), nat.ptr(losses), nat.ptr(st["scratch"]),
                 nat.ptr(st["counter"]), stream), "occ_ppo_update")
         self._keep = (feats, actions, old_lp, returns)  # alive until the stream has run the launches
@@ -374,5 +460,90 @@ def train_rollouts(venv, agent: BatchedPPO, n_updates: int = 1, T: int = 50, wit
         agent.store(xch.wait())
         st = agent.update()
         st["mean_reward"] = float(rew_sum) / T
+        stats.append(st)
+    return stats
+
+
+def train_ppo(venv, agent: BatchedPPO, max_training_timesteps: int = int(2e4), T: int = 50, max_ep_len: Optional[int] = 50,
+              action_std_decay_rate: float = 0.05, min_action_std: float = 0.1, action_std_decay_freq: int = int(1.5e4),
+              save_model_freq: int = int(5e3), checkpoint_path=None, log_path=None,
+              generator: Optional[torch.Generator] = None, on_step=None, with_action_grad: bool = False,
+              stagger: bool = True, monitor=None) -> list:
+    """``trainRL.train()`` (trainRL.py:165-250) on the batched env, with its training log: roll out, update every T
+    vector steps, decay the action std, save checkpoints, and append ``episode,timestep,reward,running_reward,length``
+    to ``log_path``.  The defaults are the script's, scaled to a short run (trainRL.py:22-56).
+
+    ``venv.reset()``; then per vector step ``agent.act_into`` (features, then one launch), ``venv.step``,
+    ``monitor.advance`` (one launch: returns, lengths, the episode ring, the buffer's rewards and dones) and the hook;
+    after every T steps ``agent.update_from`` and one ``monitor.drain()``, whose rows go to the CSV.  The loop itself
+    waits for the device once per update, in the drain (``update_from`` reads its losses back as ``update`` does, and
+    ``venv.step`` keeps its own one sync per step).
+
+    A timestep is one env step, so a vector step advances the counter by N.  ``decay_action_std``
+    and ``agent.save(checkpoint_path)`` (skipped without a path) run once for each multiple of their frequency that the
+    counter crosses in a vector step - the reference tests ``time_step % freq == 0``, which a counter moving N at a time
+    may step over.  The loop stops after the update during which the counter passes ``max_training_timesteps``
+    (``while time_step <= max_training_timesteps``, trainRL.py:189).
+
+    ``on_step(action, rewards, step)`` is called after every step and its ``monitor.advance``; ``step`` is a dict with
+    ``t``, ``timestep``, ``feats`` and ``logprob`` (row t of the buffer), ``dones``, ``codes``, ``infos``, ``obs`` (the next
+    observation) and ``buffer`` (the ``RolloutBuffer``, rows 0..t of this update filled).  ``with_action_grad``: as in ``train_rollouts``.  ``monitor``: an ``EpisodeMonitor`` to continue; by
+    default a new one whose ring holds N T entries, so that no episode of an update is lost.
+
+    Returns the per-update stats of ``update_from`` plus ``mean_reward`` (mean step reward), ``episodes`` (completed in
+    the update's T steps), ``mean_return`` and ``mean_length`` over them (NaN without one), ``lost`` and
+    ``running_reward``, ``timestep`` and ``action_std``.
+
+    One rank only: with an initialised process group of more than one rank this raises.  The multi-rank rollout stays
+    with ``train_rollouts`` and ``rollout.RecordExchange``.  From the same seed the two loops do not give the same bits:
+    the acting arithmetic differs in rounding (``act_into``)."""
+    import torch.distributed as dist
+
+    from .monitor import EpisodeMonitor
+
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise RuntimeError("train_ppo runs on one rank; the multi-rank rollout is train_rollouts with rollout.RecordExchange")
+    obs = venv.reset()[:, 0]
+    if max_ep_len is not None:
+        venv.max_ep_len = int(max_ep_len)
+        if stagger:
+            venv.stagger_ages()
+    n, dev = int(obs.shape[0]), obs.device
+    if monitor is None:
+        monitor = EpisodeMonitor(n, dev, capacity=n * T)  # an env ends at most T episodes between two drains: none is lost
+    monitor.reset()
+    buf = RolloutBuffer(T, n, dev)
+    mean_host = torch.empty((), dtype=torch.float32).pin_memory()
+    time_step, stats = 0, []
+    while time_step <= max_training_timesteps:
+        for t in range(T):
+            action = agent.act_into(obs, buf, t, generator).requires_grad_(with_action_grad)
+            obs, rewards, dones, infos = venv.step(action)
+            if with_action_grad:
+                rewards.sum().backward()
+            codes = venv.episode_end_codes
+            before, time_step = time_step, time_step + n
+            monitor.advance(rewards, codes, dones, buffer=buf, t=t, timestep=time_step)
+            if on_step is not None:
+                on_step(action, rewards, dict(t=t, timestep=time_step, feats=buf.feats[t], logprob=buf.logprobs[t], dones=dones,
+                                              codes=codes, infos=infos, obs=obs, buffer=buf))
+            for _ in range(time_step // action_std_decay_freq - before // action_std_decay_freq):
+                agent.decay_action_std(action_std_decay_rate, min_action_std)  # trainRL.py:214-215
+            for _ in range(time_step // save_model_freq - before // save_model_freq):
+                if checkpoint_path is not None:
+                    agent.save(checkpoint_path)  # trainRL.py:218-225
+        # the mean step reward travels to pinned memory behind the rollout; the update's read-back of its losses is later
+        # on the same stream, so the value has arrived by then without a wait of its own
+        mean_host.copy_(buf.rewards.mean(), non_blocking=True)
+        st = agent.update_from(buf)
+        eps = monitor.drain()
+        if log_path is not None:
+            monitor.write_csv(log_path, eps)
+        k = len(eps["ret"])
+        st.update(mean_reward=float(mean_host), episodes=k + eps["lost"], lost=eps["lost"],
+                  mean_return=float(eps["ret"].astype("float64").mean()) if k else float("nan"),
+                  mean_length=float(eps["length"].mean()) if k else float("nan"),
+                  running_reward=float(eps["running"][-1]) if k else eps["totals"]["running_reward"],
+                  timestep=time_step, action_std=agent.action_std)
         stats.append(st)
     return stats
