@@ -406,6 +406,44 @@ int occ_encoder_forward_masked(const OccEncoderConfig* cfg, const float* packed_
                                size_t ws_bytes, float* feats, const int32_t* skip, void* stream);
 
 /*
+ * bf16 inference mode of the SEPARABLE encoder (additive in ABI 12; cfg->separable must be 1, any dilation / residual / S the
+ * f32 path takes).  The same network, the same 17 launches, the same skip mask; what differs is where values are rounded
+ * (always to nearest even, to bfloat16):
+ *   - contraction operands: the depthwise pair's result (formed in f32, then rounded), the pointwise weights and the dense
+ *     down weights; the contractions of 16 input channels and more run on v_mfma_f32_32x32x16_bf16, f32 accumulation;
+ *   - stored activations: relu(conv) * bn_scale + bn_shift (+ the residual, read back as bf16, added in f32) is rounded once
+ *     when stored.  The last down is not stored: the pooled feature is summed from its unrounded f32 values in a fixed order.
+ * The observation, the depthwise taps, biases, BN scale / shift, every accumulator and epilogue, the pool partials and
+ * feats are f32.  No atomics: feats are bitwise independent of n_env, of an env's position and of repeat calls.  The
+ * activations are kept channel-last, (n, H, W, c) bf16.
+ *
+ * Packed buffer (occ_encoder_bf16_packed_bytes bytes; occ_encoder_bf16_pack makes it from the f32 buffer of
+ * occ_encoder_packed_floats, on the host): the layers in the f32 order, each 16-byte aligned:
+ *   cin <= 8 (initial, level 0's Layer 1, Layer 2 and down): the f32 layout above, float for float, with every pw[][] / w[][][]
+ *     entry replaced by its bf16 rounding widened back to f32 (the low 16 bits are zero).
+ *   separable Conv(c -> c), c >= 16:  dw[c / 8][6][8] f32: per group of 8 channels the taps v0 v1 v2 h0 h1 h2, each for the
+ *     group's 8 channels | F[c / 16][max(c, 32) / 32][64][8] bf16 | bias[c] | bn_scale[c] | bn_shift[c] f32
+ *   down Conv(c -> 2c), c >= 16:      F[9 c / 16][2c / 32][64][8] bf16 | bias[2c] | bn_scale[2c] | bn_shift[2c] f32
+ * F[kb][ct][lane][j] is the MFMA A fragment of k-step kb and weight tile ct: the weight of contraction index
+ * k = 16 kb + 8 (lane >> 5) + j and output channel co = 32 ct + 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3), m = lane & 31
+ * (zero where co >= cout: c = 16 fills half a tile).  Separable: k is the input channel, the weight pw[k][co].  Down:
+ * k = tap * c + ci, tap = ky * 3 + kx, the weight w[ci][tap][co].  Weights are rounded in integer arithmetic; all f32
+ * parts are copied bit for bit.
+ */
+/* Bytes of the bf16 packed buffer; -1 unless cfg->separable == 1. */
+int64_t occ_encoder_bf16_packed_bytes(const OccEncoderConfig* cfg);
+/* Host only, no device call: packed_f32 (occ_encoder_packed_floats floats, host memory) -> out (occ_encoder_bf16_packed_bytes
+ * bytes, host memory).  OCC_ERR_ARG unless cfg->separable == 1. */
+int occ_encoder_bf16_pack(const OccEncoderConfig* cfg, const float* packed_f32, void* out);
+/* Device workspace bytes of occ_encoder_forward_bf16: three (n_env,S,S,8) bf16 activation buffers and the f32 per-tile
+ * partials (n_env, ceil(S_5 / 8)^2, 256), S_5 the side after five downs; each part rounded up to 256 bytes. */
+int occ_encoder_bf16_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* bytes);
+/* As occ_encoder_forward_masked (skip may be NULL) on the bf16 packed buffer (device memory, 16-byte aligned, as ws);
+ * cfg->separable == 0 is OCC_ERR_ARG before any launch.  Nothing allocated or synchronised (capturable). */
+int occ_encoder_forward_bf16(const OccEncoderConfig* cfg, const void* packed_bf16, const float* obs, int n_env, void* ws,
+                             size_t ws_bytes, float* feats, const int32_t* skip, void* stream);
+
+/*
  * Segmentation decoder (model.py:109-125 on top of the encoder above, eval mode): x = the last down output
  * (n_env,256,S/32,S/32); for j = 0..4, c = 128, 64, 32, 16, 8: x = up_j(x) + skip, where up_j = TrConv(2c -> c) =
  * bn(relu(ConvTranspose2d(2c, c, 3, stride 2, padding 1, output_padding 1))) (BN folded as above) and skip is the

@@ -217,6 +217,11 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p]),
     "occ_encoder_forward_masked": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "occ_encoder_bf16_packed_bytes": (C.c_int64, [C.POINTER(OccEncoderConfig)]),
+    "occ_encoder_bf16_pack": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p]),
+    "occ_encoder_bf16_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t)]),
+    "occ_encoder_forward_bf16": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "occ_decoder_packed_floats": (C.c_int64, [C.POINTER(OccEncoderConfig)]),
     "occ_segment_workspace_query": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_int, C.POINTER(C.c_size_t)]),
     "occ_segment_forward": (C.c_int, [C.POINTER(OccEncoderConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

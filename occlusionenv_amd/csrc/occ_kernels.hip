@@ -27,6 +27,7 @@
 // second pass over the K-buffer, no atomics into grad_face_verts and no saved fragments.  It
 // equals what autograd + _C.rasterize_meshes_backward produce.
 //
+//   occ_enc16_*_kernel  the bf16 inference mode of the separable encoder (occ_encoder_bf16.hpp): bf16 storage, MFMA contractions
 //   occ_enc_*_kernel    the frozen encoder of the PPO features (occ_encoder.hpp): fused separable layer, dense 3x3
 //                       conv, last down fused with the average pool
 //   occ_dec_up_kernel   the segmentation decoder of the same network (occ_decoder.hpp): transposed conv + skip add per
@@ -63,6 +64,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -82,6 +84,7 @@ namespace occ {
 #include "occ_oplevel.hpp"
 #include "occ_ppo.hpp"
 #include "occ_encoder.hpp"
+#include "occ_encoder_bf16.hpp"
 #include "occ_decoder.hpp"
 #include "occ_decoder_bwd.hpp"
 #include "occ_encoder_bwd.hpp"
@@ -750,6 +753,39 @@ extern "C" int occ_encoder_forward_masked(const OccEncoderConfig* cfg, const flo
 extern "C" int occ_encoder_forward(const OccEncoderConfig* cfg, const float* packed_weights, const float* obs, int n_env, void* ws,
                                    size_t ws_bytes, float* feats, void* stream) {
     return occ_encoder_forward_masked(cfg, packed_weights, obs, n_env, ws, ws_bytes, feats, nullptr, stream);
+}
+
+// ---- bf16 inference mode of the separable encoder (occ_encoder_bf16.hpp) --------------------------------------------------
+extern "C" int64_t occ_encoder_bf16_packed_bytes(const OccEncoderConfig* cfg) {
+    if (!cfg || cfg->separable != 1) return -1;
+    return enc16_packed_bytes();
+}
+
+extern "C" int occ_encoder_bf16_pack(const OccEncoderConfig* cfg, const float* packed_f32, void* out) {
+    if (!cfg || cfg->separable != 1 || !packed_f32 || !out) return OCC_ERR_ARG;
+    enc16_pack(packed_f32, (char*)out);
+    return OCC_OK;
+}
+
+extern "C" int occ_encoder_bf16_workspace_query(const OccEncoderConfig* cfg, int n_env, size_t* bytes) {
+    if (!enc_cfg_ok(cfg) || cfg->separable != 1 || n_env <= 0 || !bytes) return OCC_ERR_ARG;
+    size_t buf, part;
+    enc16_ws_layout(cfg->img, n_env, &buf, &part);
+    *bytes = 3 * buf + part;
+    return OCC_OK;
+}
+
+extern "C" int occ_encoder_forward_bf16(const OccEncoderConfig* cfg, const void* packed_bf16, const float* obs, int n_env, void* ws,
+                                        size_t ws_bytes, float* feats, const int32_t* skip, void* stream) {
+    if (!enc_cfg_ok(cfg) || cfg->separable != 1 || !packed_bf16 || !obs || n_env <= 0 || n_env > 65535 || !ws || !feats)
+        return OCC_ERR_ARG;
+    if (((uintptr_t)packed_bf16 | (uintptr_t)ws) & 15) return OCC_ERR_ARG;  // 16-byte accesses
+    size_t need = 0;
+    occ_encoder_bf16_workspace_query(cfg, n_env, &need);
+    if (ws_bytes < need) return OCC_ERR_ARG;
+    enc16_forward(cfg->img, cfg->dilation, cfg->residual != 0, (const char*)packed_bf16, obs, n_env, (char*)ws, feats,
+                  (hipStream_t)stream, skip);
+    return hipGetLastError() == hipSuccess ? OCC_OK : OCC_ERR_LAUNCH;
 }
 
 // ---- segmentation decoder (occ_decoder.hpp) ----------------------------------------------------------------------------

@@ -27,6 +27,13 @@ Every forward call takes ``skip=`` and ``out=``: a caller who holds a batch of w
 keep the bits they held; without it they are zero.  The grid stays sized for N and the mask is read on the device, so the
 host needs no count of the active rows and a captured call follows the mask it finds at replay.
 
+``precision="bf16"`` (separable encoders only; csrc/occ_encoder_bf16.hpp) is a reduced-precision inference mode of the
+pooled feature: activations are stored as bfloat16, the contractions take bf16 operands (on the matrix cores from 16 input
+channels up) and accumulate in f32; the observation, the depthwise taps, biases, the BN affine, every epilogue and ``feats``
+stay f32, and the heads run in torch f32 on the f32 ``feats``.  ``enc(obs, skip=, out=)`` and ``enc.predict_grad`` work as
+in f32, with the same guarantees on bits (repeat calls, batch position, chunking); ``segment``, ``forward_full`` and the
+training wrappers need the f32 mode (``enc.with_precision("f32")``).
+
 Whole-module checkpoints (``torch.save(model)``, as pretrainer.py writes them) need the reference's ``model.py`` to
 unpickle; with it on the path use ``FrozenEncoder.from_module(torch.load(path, weights_only=False))``.
 """
@@ -56,6 +63,7 @@ DECODER_KEYS = {
     "ppo": ("segmenter.0.features.", "segmenter.1."),
     "segmenter": ("decoder.features.", "classifier."),
 }
+PRECISIONS = ("f32", "bf16")
 
 
 def _layer_floats(cin: int, cout: int, separable: bool) -> int:
@@ -217,10 +225,16 @@ class FrozenEncoder:
     every env's features are computed independently, so the chunking changes no bit."""
 
     takes_skip_mask = True  # ppo.BatchedPPO.features: this encoder is called with skip= and out=
+    precision = "f32"       # the mode: "f32", or "bf16" (inference of the pooled feature only; the module docstring)
+    packed_bf16 = None      # the bf16 mode's packed buffer on the device
 
     def __init__(self, packed: np.ndarray, separable: bool, dilation: int, residual: bool, preset: str, grad_head=None,
                  heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None, decoder=None,
-                 decoder_state: Optional[dict] = None, encoder_state: Optional[dict] = None):
+                 decoder_state: Optional[dict] = None, encoder_state: Optional[dict] = None, precision: str = "f32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        if precision == "bf16" and not separable:
+            raise ValueError("precision='bf16' exists for the separable encoder only; this state dict holds the dense one")
         if dilation not in (1, 2):
             raise ValueError(f"dilation must be 1 or 2, got {dilation}")
         if int(max_chunk) < 1:
@@ -238,6 +252,8 @@ class FrozenEncoder:
         if lib.occ_encoder_packed_floats(C.byref(cfg)) != self.packed_host.size:
             raise nat.NativeError("packed encoder weights do not match the library's layout")
         self.packed = torch.from_numpy(self.packed_host).to(self.device)
+        self.precision = precision
+        self.packed_bf16 = self._pack_bf16() if precision == "bf16" else None
         self.grad_tanh = PRESETS[preset][2] if preset in PRESETS else False
         self.grad_w = self.grad_b = None
         if grad_head is not None:
@@ -254,6 +270,38 @@ class FrozenEncoder:
                 raise nat.NativeError("packed decoder weights do not match the library's layout")
             self.dec_packed = torch.from_numpy(self.dec_packed_host).to(self.device)
 
+    def _pack_bf16(self) -> torch.Tensor:
+        """The bf16 mode's packed buffer (include/occlusionenv_amd.h) of ``packed_host``, on the device: made on the host by
+        ``occ_encoder_bf16_pack``."""
+        lib, cfg = nat.load(), self._cfg(64)
+        nbytes = int(lib.occ_encoder_bf16_packed_bytes(C.byref(cfg)))
+        if nbytes <= 0:
+            raise nat.NativeError("occ_encoder_bf16_packed_bytes rejected the configuration")
+        host = np.empty(nbytes, dtype=np.uint8)
+        nat.check(lib.occ_encoder_bf16_pack(C.byref(cfg), self.packed_host.ctypes.data_as(C.c_void_p),
+                                            host.ctypes.data_as(C.c_void_p)), "occ_encoder_bf16_pack")
+        return torch.from_numpy(host).to(self.device)
+
+    def with_precision(self, precision: str) -> "FrozenEncoder":
+        """A ``FrozenEncoder`` over this one's state (weights, heads, decoder: shared, not copied) that runs in ``precision``
+        ("f32" or "bf16").  This encoder is left as it is."""
+        import copy
+
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        if precision == "bf16" and not self.separable:
+            raise ValueError("precision='bf16' exists for the separable encoder only; this encoder is the dense one")
+        new = copy.copy(self)
+        new._ws = {}
+        new.precision = precision
+        new.packed_bf16 = new._pack_bf16() if precision == "bf16" else None
+        return new
+
+    def _f32_only(self, what: str) -> None:
+        if self.precision != "f32":
+            raise ValueError(f"{what}: precision={self.precision!r} is inference of the pooled feature only; "
+                             "use enc.with_precision('f32')")
+
     @property
     def has_decoder(self) -> bool:
         """Whether the checkpoint held the segmentation decoder (``segment`` / ``forward_full`` need it)."""
@@ -262,10 +310,11 @@ class FrozenEncoder:
     # ---- construction ------------------------------------------------------------------------------------------
     @classmethod
     def from_state_dict(cls, sd, preset: str = "ppo", dilation: Optional[int] = None, residual: Optional[bool] = None,
-                        device="cuda", max_chunk: int = 256) -> "FrozenEncoder":
+                        device="cuda", max_chunk: int = 256, precision: str = "f32") -> "FrozenEncoder":
         """A ``FullNetwork`` (preset "ppo"), ``PredictorNet`` (preset "predictor") or ``Segmenter`` (preset "segmenter")
         state dict.  The dilation and the residual flag are not in a state dict: they come from the preset unless given.
-        The segmentation decoder is loaded when its keys are there (``has_decoder``)."""
+        The segmentation decoder is loaded when its keys are there (``has_decoder``).  ``precision``: "f32", or "bf16" for
+        the reduced-precision inference mode of a separable encoder (the module docstring)."""
         if preset not in PRESETS:
             raise ValueError(f"unknown preset {preset!r}; one of {sorted(PRESETS)}")
         if preset == "segmenter" and any(k.startswith(("segmenter.0.", "gradPredictor.")) for k in sd):
@@ -290,7 +339,7 @@ class FrozenEncoder:
                 heads[name[:-1]] = (_get(sd, name + "weight", (rows, FEATURES)), _get(sd, name + "bias", (rows,)))
         return cls(packed, separable, d0 if dilation is None else int(dilation), r0 if residual is None else bool(residual),
                    preset, grad_head, heads, device, max_chunk, offsets, decoder, decoder_state,
-                   encoder_tensors(sd, prefix, separable, ghead))
+                   encoder_tensors(sd, prefix, separable, ghead), precision)
 
     def with_decoder(self, sd) -> "FrozenEncoder":
         """A ``FrozenEncoder`` with this one's encoder (the packed weights are shared, not copied) and the decoder of
@@ -325,6 +374,8 @@ class FrozenEncoder:
         new.packed_host = np.ascontiguousarray(packed, dtype=np.float32)
         new.packed = torch.from_numpy(new.packed_host).to(self.device)
         new.layer_offsets = list(offsets)
+        if new.precision == "bf16":
+            new.packed_bf16 = new._pack_bf16()
         if ghead is not None and ghead + "weight" in sd:
             new.grad_w = _get(sd, ghead + "weight", (2, FEATURES)).to(self.device, torch.float32).contiguous()
             new.grad_b = _get(sd, ghead + "bias", (2,)).to(self.device, torch.float32).contiguous()
@@ -336,7 +387,7 @@ class FrozenEncoder:
         return self.with_encoder(sd).with_decoder(sd)
 
     @classmethod
-    def from_module(cls, m, device="cuda", max_chunk: int = 256) -> "FrozenEncoder":
+    def from_module(cls, m, device="cuda", max_chunk: int = 256, precision: str = "f32") -> "FrozenEncoder":
         """A ``FullNetwork``, ``PredictorNet`` or ``Segmenter`` module: dilation and residual are read from the module
         (the dilation of the first block's Layer 1 conv, ``ConvBlock.residual``)."""
         if hasattr(m, "encoder") and hasattr(m, "gradPredictor"):
@@ -350,14 +401,14 @@ class FrozenEncoder:
         block = enc.features[0]
         conv = block.net[0].conv
         dil = conv[0].dilation[0] if isinstance(conv, torch.nn.Sequential) else conv.dilation[0]
-        return cls.from_state_dict(m.state_dict(), preset, int(dil), bool(block.residual), device, max_chunk)
+        return cls.from_state_dict(m.state_dict(), preset, int(dil), bool(block.residual), device, max_chunk, precision)
 
     @classmethod
     def from_file(cls, path, preset: str = "ppo", dilation: Optional[int] = None, residual: Optional[bool] = None,
-                  device="cuda", max_chunk: int = 256) -> "FrozenEncoder":
+                  device="cuda", max_chunk: int = 256, precision: str = "f32") -> "FrozenEncoder":
         """A state dict saved with ``torch.save(model.state_dict(), path)`` (loaded with weights_only=True)."""
         sd = torch.load(path, map_location="cpu", weights_only=True)
-        return cls.from_state_dict(sd, preset, dilation, residual, device, max_chunk)
+        return cls.from_state_dict(sd, preset, dilation, residual, device, max_chunk, precision)
 
     # ---- inference -------------------------------------------------------------------------------------------------
     def _cfg(self, img: int) -> nat.OccEncoderConfig:
@@ -438,7 +489,10 @@ class FrozenEncoder:
         rows to leave alone (the ``_masked`` entry points; every chunk takes its slice).  ``out``: the tensors to write into,
         in the order of the return value (None: a fresh one, zero where a row is skipped); their skipped rows keep their
         bits.  Everything is checked before anything native runs."""
+        if decoder:
+            self._f32_only("the segmentation decoder")
         img = self._check_obs(obs, decoder)
+        bf16 = self.precision == "bf16"
         n_all = int(obs.shape[0])
         skip = self._check_skip(skip, obs)
         shapes = ((n_all, FEATURES), (n_all, 1, img, img), (n_all, 1, img, img), (n_all, CH, img, img))
@@ -456,10 +510,14 @@ class FrozenEncoder:
         lib, cfg, stream = nat.load(), self._cfg(img), nat.stream_ptr(obs.device)
         pix = 4 * img * img  # bytes of one f32 map
         for lo, n in nat.row_chunks(n_all, self.max_chunk):
-            ws = self._workspace("segment" if decoder else "encoder", n, img)
+            ws = self._workspace("segment" if decoder else "encoder_bf16" if bf16 else "encoder", n, img)
             obs_lo, feats_lo = nat.ptr(obs, lo * 4 * pix), nat.ptr(feats, lo * 4 * FEATURES)
             maps = (nat.ptr(prob, lo * pix), nat.ptr(logits, lo * pix), nat.ptr(dfeat, lo * CH * pix))
-            if decoder and skip is None:
+            if bf16:
+                nat.check(lib.occ_encoder_forward_bf16(C.byref(cfg), nat.ptr(self.packed_bf16), obs_lo, n, nat.ptr(ws), ws.numel(),
+                                                       feats_lo, None if skip is None else nat.ptr(skip, 4 * lo), stream),
+                          "occ_encoder_forward_bf16")
+            elif decoder and skip is None:
                 nat.check(lib.occ_segment_forward(C.byref(cfg), nat.ptr(self.packed), nat.ptr(self.dec_packed), obs_lo, n, nat.ptr(ws),
                                                   ws.numel(), feats_lo, *maps, stream), "occ_segment_forward")
             elif decoder:
@@ -527,6 +585,7 @@ class FrozenEncoder:
         135-140): ``(features, predictions)``; with ``return_logits`` the classifier's output before the sigmoid comes last.
         ``skip`` as in ``__call__``; ``out``: the tensors to write into, a tuple in the order of the return value (a lone
         tensor when only the map is returned)."""
+        self._f32_only("segment")
         names = (("decoder feature",) if return_features else ()) + ("prob",) + (("logits",) if return_logits else ())
         given = dict(zip(names, self._out_tuple(out, names)))
         _f, prob, logits, dfeat = self._segment(obs, return_logits, return_features, skip,
@@ -539,6 +598,7 @@ class FrozenEncoder:
         """``FullNetwork.forward`` (model.py:156-166) from one pass over the encoder: (pooled (N,256), segm (N,1,S,S),
         grad (N,2)).  The pooled feature is bitwise ``self(obs)``.  ``skip`` as in ``__call__``; ``out``: a tuple
         (pooled, segm, grad) to write into."""
+        self._f32_only("forward_full")
         if self.grad_w is None:
             raise ValueError("this checkpoint has no gradPredictor / output head")
         o_feats, o_prob, o_grad = self._out_tuple(out, ("features", "prob", "grad"))

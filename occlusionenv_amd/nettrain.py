@@ -239,6 +239,9 @@ class TrainableNet(torch.nn.Module):
     BN_SYMBOLS: Optional[Tuple[str, str, str]] = None  # the three for batch-statistics BatchNorm, where the step offers it
 
     def __init__(self, enc: FrozenEncoder, parts, state):
+        if getattr(enc, "precision", "f32") != "f32":
+            raise ValueError(f"training needs the f32 encoder: precision={enc.precision!r} is inference of the pooled feature "
+                             "only; use enc.with_precision('f32')")
         super().__init__()
         self.enc = enc  # a plain attribute, not part of the state dict: the preset, the flags, the device and max_chunk
         self.parts = tuple(parts)

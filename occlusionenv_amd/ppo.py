@@ -162,17 +162,19 @@ class BatchedPPO:
 
     @classmethod
     def from_fullnetwork(cls, sd_or_module, dilation: Optional[int] = None, residual: Optional[bool] = None,
-                         max_chunk: int = 256, **kw) -> "BatchedPPO":
+                         max_chunk: int = 256, precision: str = "f32", **kw) -> "BatchedPPO":
         """The reference's agent (PPO.py:47-48): a FullNetwork checkpoint (state dict, or the module itself) gives the
         frozen encoder (``encoder.FrozenEncoder``, preset "ppo") and the initial action / value heads of ``policy`` and
-        ``policy_old`` (model.py:153-154,168-171).  ``kw``: the other BatchedPPO arguments (device default "cuda")."""
+        ``policy_old`` (model.py:153-154,168-171).  ``precision``: "f32", or "bf16" for the encoder's reduced-precision
+        inference mode (``encoder.FrozenEncoder``); the heads stay f32.  ``kw``: the other BatchedPPO arguments (device default "cuda")."""
         from .encoder import FrozenEncoder
 
         kw.setdefault("device", "cuda")
         if isinstance(sd_or_module, nn.Module):
-            enc = FrozenEncoder.from_module(sd_or_module, device=kw["device"], max_chunk=max_chunk)
+            enc = FrozenEncoder.from_module(sd_or_module, device=kw["device"], max_chunk=max_chunk, precision=precision)
         else:
-            enc = FrozenEncoder.from_state_dict(sd_or_module, "ppo", dilation, residual, device=kw["device"], max_chunk=max_chunk)
+            enc = FrozenEncoder.from_state_dict(sd_or_module, "ppo", dilation, residual, device=kw["device"], max_chunk=max_chunk,
+                                                precision=precision)
         if set(enc.heads) != {"action_head", "value_head"}:
             raise ValueError("the checkpoint has no action_head / value_head")
         agent = cls(encoder=enc, **kw)

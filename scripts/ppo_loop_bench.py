@@ -13,6 +13,13 @@ between the two; medians are compared, the larger min-max spread is the margin. 
 events (and, apart, copies and memsets) under ``torch.profiler`` of what each loop itself adds to a step around the encoder
 and ``venv.step``, and of its update.  Last, ``occ_ppo_act`` and ``occ_rollout_advance`` alone, ``--calls`` launches between
 two device events.
+
+``--precision bf16`` adds a third loop to the same interleaved samples: ``ppo.train_ppo`` with the agent of
+``BatchedPPO.from_fullnetwork(sd, precision="bf16")`` (the encoder's bf16 inference mode, csrc/occ_encoder_bf16.hpp), and
+reports its rollout step and update next to the f32 ``train_ppo`` of the same session under ``rollout_step_bf16`` /
+``update_bf16``.  Without the flag the script does what it did.
+
+    python scripts/ppo_loop_bench.py --precision bf16 --out profiles/ppo_loop_bf16_bench.json
 """
 import argparse
 import os
@@ -78,6 +85,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--iters", type=int, default=7)
     ap.add_argument("--calls", type=int, default=50, help="launches per sample of the two kernels alone")
+    ap.add_argument("--precision", choices=("f32", "bf16"), default="f32", help="bf16: also time train_ppo with the bf16 encoder")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ppo_loop_bench needs a GPU"
@@ -88,6 +96,8 @@ def main():
     sd = golden_state_dict(np.load(os.path.join(ROOT, "tests", "golden", "encoder_golden.npz")), "ppo")
     venv = make_venv(n, args.img, args.models)
     agents = {k: ppo.BatchedPPO.from_fullnetwork(sd, seed=0, K_epochs=args.K) for k in ("train_rollouts", "train_ppo")}
+    if args.precision == "bf16":
+        agents["train_ppo_bf16"] = ppo.BatchedPPO.from_fullnetwork(sd, seed=0, K_epochs=args.K, precision="bf16")
     gen = torch.Generator(device="cuda").manual_seed(0)
 
     def one(name):
@@ -117,6 +127,11 @@ def main():
                                    n="train_ppo", r="train_rollouts")
     out["update"] = bl.named(bl.compare(update_ms["train_ppo"], update_ms["train_rollouts"]), bl.ONE_RIVAL_NOT_SLOWER,
                              n="train_ppo", r="train_rollouts")
+    if args.precision == "bf16":  # reported, no bar: the same loop, the encoder's mode apart
+        out["rollout_step_bf16"] = bl.named(bl.compare(step_ms["train_ppo_bf16"], step_ms["train_ppo"]), bl.ONE_RIVAL,
+                                            n="train_ppo_bf16", r="train_ppo")
+        out["update_bf16"] = bl.named(bl.compare(update_ms["train_ppo_bf16"], update_ms["train_ppo"]), bl.ONE_RIVAL_NOT_SLOWER,
+                                      n="train_ppo_bf16", r="train_ppo")
 
     # ---- what each loop itself launches around the encoder and venv.step, on the tensors of a real step ----------------
     old, new = agents["train_rollouts"], agents["train_ppo"]
@@ -160,6 +175,8 @@ def main():
     bl.emit({k: v for k, v in out.items() if not isinstance(v, dict)})
     bl.emit(out["rollout_step"])
     bl.emit(out["update"])
+    if args.precision == "bf16":
+        bl.emit(out["rollout_step_bf16"])
     bl.write(out, args.out)
 
 
