@@ -3,9 +3,10 @@
 The reference's agent runs every observation through a frozen, pretrained ``FullNetwork`` and keeps the 256-d average
 pool of the encoder's last ``down`` output (PPO.py:47,152-162; model.py:142-171); the gradient predictors read the same
 feature (``FullNetwork.gradPredictor``, model.py:164, no tanh; ``PredictorNet.output`` + tanh, model.py:81-85).
-``FrozenEncoder`` loads such a network's weights once (parsed and checked on the CPU, BatchNorm folded to a per-channel
-affine, packed in the layout include/occlusionenv_amd.h documents, uploaded) and runs ``occ_encoder_forward`` on the
-caller's stream: no host sync, no allocation once the workspace of a batch size exists, capturable in a HIP graph.
+``FrozenEncoder`` loads such a network's weights once (parsed, checked, BatchNorm folded to a per-channel affine and packed
+on the CPU by ``netlayout``, whose names are importable here, in the layout include/occlusionenv_amd.h documents, uploaded)
+and runs ``occ_encoder_forward`` on the caller's stream: no host sync, no allocation once the workspace of a batch size
+exists, capturable in a HIP graph.
 
 Presets (model.py: a state dict stores neither the dilation nor the residual flag):
 
@@ -39,8 +40,8 @@ unpickle; with it on the path use ``FrozenEncoder.from_module(torch.load(path, w
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
-import re
 from typing import Optional
 
 import numpy as np
@@ -48,173 +49,21 @@ import torch
 
 from . import _native as nat
 from . import segmentation
+from .netlayout import (BN_EPS, CH, DECODER_KEYS, FEATURES, LEVELS, PRESETS, _get, decoder_packed_floats, decoder_plan,  # noqa: F401
+                        decoder_tensors, encoder_tensors, layer_plan, pack_decoder, pack_state_dict, packed_floats)
 from .segmentation import seg_counts  # noqa: F401
 
-CH, LEVELS, FEATURES = 8, 5, 256
-BN_EPS = 1e-5
-PRESETS = {
-    # name: (key prefix, grad head, tanh on the grad head, dilation, residual)
-    "ppo": ("encoder.", "gradPredictor.", False, 2, True),
-    "predictor": ("features.", "output.", True, 1, False),
-    "segmenter": ("encoder.", None, False, 1, True),
-}
-# name: (key prefix of Decoder.features, key prefix of the 1x1 classifier); "predictor" has no decoder
-DECODER_KEYS = {
-    "ppo": ("segmenter.0.features.", "segmenter.1."),
-    "segmenter": ("decoder.features.", "classifier."),
-}
 PRECISIONS = ("f32", "bf16")
+# (the decoder runs, a skip mask is given) -> the f32 entry point of a forward call
+FORWARD_ENTRY = {(False, False): "occ_encoder_forward", (False, True): "occ_encoder_forward_masked",
+                 (True, False): "occ_segment_forward", (True, True): "occ_segment_forward_masked"}
 
 
-def _layer_floats(cin: int, cout: int, separable: bool) -> int:
-    return 6 * cin + cin * cout + 3 * cout if separable else 9 * cin * cout + 3 * cout
-
-
-def layer_plan(separable: bool):
-    """[(state-dict stem relative to the encoder prefix, cin, cout, separable, stride)] in packed order."""
-    plan = [("initial.", 4, CH, separable, 1)]
-    for lv in range(LEVELS):
-        c = CH << lv
-        plan += [(f"features.{lv}.net.Layer 1.", c, c, separable, 1), (f"features.{lv}.net.Layer 2.", c, c, separable, 1),
-                 (f"features.{lv}.down.", c, 2 * c, False, 2)]
-    return plan
-
-
-def packed_floats(separable: bool) -> int:
-    return sum(_layer_floats(ci, co, sep) for _, ci, co, sep, _ in layer_plan(separable))
-
-
-def _get(sd, key, shape=None):
-    if key not in sd:
-        raise ValueError(f"encoder state dict: missing key {key!r}")
-    t = torch.as_tensor(sd[key]).detach().to("cpu", torch.float64)
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"encoder state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)} "
-                         "(only ch=8, levels=5, layers=2, k=3 give the 256 features)")
-    return t
-
-
-def fold_bn(sd, stem: str, cout: int):
-    """BN after the ReLU (model.py:21-22) as y = relu(.) * scale + shift, in f64."""
-    g = _get(sd, stem + "bn.weight", (cout,))
-    b = _get(sd, stem + "bn.bias", (cout,))
-    m = _get(sd, stem + "bn.running_mean", (cout,))
-    v = _get(sd, stem + "bn.running_var", (cout,))
-    scale = g / torch.sqrt(v + BN_EPS)
-    return scale, b - m * scale
-
-
-def _check_structure(sd, prefix: str):
-    """The rejections of the contract: levels != 5, a third layer, a missing encoder."""
-    stems = [k[len(prefix):] for k in sd if k.startswith(prefix)]
-    if not stems:
-        raise ValueError(f"encoder state dict: no key starts with {prefix!r} (wrong preset?)")
-    levels = {int(m.group(1)) for s in stems for m in [re.match(r"features\.(\d+)\.", s)] if m}
-    if levels != set(range(LEVELS)):
-        raise ValueError(f"encoder state dict: levels {sorted(levels)}; only levels=5 gives 256 features")
-    layers = {m.group(1) for s in stems for m in [re.match(r"features\.\d+\.net\.Layer (\d+)\.", s)] if m}
-    if layers != {"1", "2"}:
-        raise ValueError(f"encoder state dict: layers {sorted(layers)} per block; only layers=2 is supported")
-    if prefix + "initial.conv.0.weight" in sd:
-        return True
-    if prefix + "initial.conv.weight" in sd:
-        return False
-    raise ValueError(f"encoder state dict: missing key {prefix + 'initial.conv.weight'!r}")
-
-
-def pack_state_dict(sd, prefix: str):
-    """Parse, check and fold a state dict -> (separable, packed f32 numpy buffer, [offset of every layer])."""
-    separable = _check_structure(sd, prefix)
-    w0 = _get(sd, prefix + ("initial.conv.2.weight" if separable else "initial.conv.weight"))
-    if w0.shape[0] != CH:
-        raise ValueError(f"encoder state dict: ch = {w0.shape[0]}; only ch=8 gives 256 features")
-    parts, offsets, off = [], [], 0
-    for stem, cin, cout, sep, _stride in layer_plan(separable):
-        stem = prefix + stem
-        if sep:
-            dv = _get(sd, stem + "conv.0.weight", (cin, 1, 3, 1))[:, 0, :, 0]
-            dh = _get(sd, stem + "conv.1.weight", (cin, 1, 1, 3))[:, 0, 0, :]
-            pw = _get(sd, stem + "conv.2.weight", (cout, cin, 1, 1))[:, :, 0, 0].t()
-            bias = _get(sd, stem + "conv.2.bias", (cout,))
-            body = [dv.reshape(-1), dh.reshape(-1), pw.reshape(-1)]
-        else:
-            w = _get(sd, stem + "conv.weight", (cout, cin, 3, 3))
-            bias = _get(sd, stem + "conv.bias", (cout,))
-            body = [w.permute(1, 2, 3, 0).reshape(-1)]
-        scale, shift = fold_bn(sd, stem, cout)
-        offsets.append(off)
-        layer = torch.cat(body + [bias, scale, shift])
-        assert layer.numel() == _layer_floats(cin, cout, sep)
-        parts.append(layer)
-        off += layer.numel()
-    return separable, torch.cat(parts).to(torch.float32).numpy(), offsets
-
-
-def decoder_plan():
-    """[(index j in Decoder.features, cin = 2c, cout = c)] in packed (= decoder) order: c = 128, 64, 32, 16, 8."""
-    return [(j, 2 * (CH << (LEVELS - 1 - j)), CH << (LEVELS - 1 - j)) for j in range(LEVELS)]
-
-
-def decoder_packed_floats() -> int:
-    return sum(9 * cin * cout + 3 * cout for _, cin, cout in decoder_plan()) + CH + 1
-
-
-def pack_decoder(sd, prefix: str, classifier: str):
-    """Parse, check and fold the decoder of a state dict -> packed f32 numpy buffer (include/occlusionenv_amd.h).
-
-    Only the ``up`` TrConv of every block is read: TrConvBlock.forward returns ``self.up(x)`` and discards what its
-    ``net`` layers computed (model.py:63-67), so ``{prefix}{j}.net.*`` keys are neither needed nor used."""
-    stems = [k[len(prefix):] for k in sd if k.startswith(prefix)]
-    if not stems:
-        raise ValueError(f"decoder state dict: no key starts with {prefix!r}")
-    levels = {int(m.group(1)) for s in stems for m in [re.match(r"(\d+)\.", s)] if m}
-    if levels != set(range(LEVELS)):
-        raise ValueError(f"decoder state dict: levels {sorted(levels)}; only levels=5 matches the encoder's five skips")
-    parts = []
-    for j, cin, cout in decoder_plan():
-        stem = f"{prefix}{j}.up."
-        wkey = stem + "conv.weight"
-        if wkey not in sd:
-            raise ValueError(f"decoder state dict: missing key {wkey!r}")
-        w = torch.as_tensor(sd[wkey])
-        if w.dim() == 4 and (w.shape[0] != cin or w.shape[1] != cout):
-            raise ValueError(f"decoder state dict: {wkey!r} maps {w.shape[0]} -> {w.shape[1]} channels, expected {cin} -> {cout} "
-                             "(only ch=8, levels=5 is supported)")
-        w = _get(sd, wkey, (cin, cout, 3, 3))  # ConvTranspose2d: input channels first
-        bias = _get(sd, stem + "conv.bias", (cout,))
-        scale, shift = fold_bn(sd, stem, cout)
-        parts += [w.permute(0, 2, 3, 1).reshape(-1), bias, scale, shift]
-    parts += [_get(sd, classifier + "weight", (1, CH, 1, 1)).reshape(-1), _get(sd, classifier + "bias", (1,))]
-    buf = torch.cat(parts).to(torch.float32).numpy()
-    assert buf.size == decoder_packed_floats()
-    return buf
-
-
-DECODER_TENSORS = ("conv.weight", "conv.bias", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var")
-
-
-def decoder_tensors(sd, prefix: str, classifier: str) -> dict:
-    """The unfolded tensors ``pack_decoder`` reads, under their full state-dict keys (what ``seghead.SegmentationHead``
-    trains and ``FrozenEncoder.with_decoder`` takes back); call after ``pack_decoder`` has checked them."""
-    keys = [f"{prefix}{j}.up.{t}" for j, _cin, _cout in decoder_plan() for t in DECODER_TENSORS]
-    keys += [classifier + "weight", classifier + "bias"]
-    return {k: torch.as_tensor(sd[k]).detach().to("cpu").clone() for k in keys}
-
-
-ENCODER_TENSORS = ("conv.weight", "conv.bias", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var")
-
-
-def encoder_tensors(sd, prefix: str, separable: bool, grad_head: Optional[str] = None) -> dict:
-    """The unfolded tensors ``pack_state_dict`` reads, under their full state-dict keys, plus the grad head's when it is
-    there (what ``enctrain.TrainableEncoder`` trains and ``FrozenEncoder.with_encoder`` takes back); call after
-    ``pack_state_dict`` has checked them."""
-    keys = []
-    for stem, _cin, _cout, sep, _stride in layer_plan(separable):
-        conv = ("conv.0.weight", "conv.1.weight", "conv.2.weight", "conv.2.bias") if sep else ENCODER_TENSORS[:2]
-        keys += [prefix + stem + t for t in conv + ENCODER_TENSORS[2:]]
-    if grad_head is not None and grad_head + "weight" in sd:
-        keys += [grad_head + "weight", grad_head + "bias"]
-    return {k: torch.as_tensor(sd[k]).detach().to("cpu").clone() for k in keys}
+def _check_precision(precision: str, separable: bool, what: str) -> None:
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    if precision == "bf16" and not separable:
+        raise ValueError(f"precision='bf16' exists for the separable encoder only; {what} the dense one")
 
 
 class FrozenEncoder:
@@ -231,10 +80,7 @@ class FrozenEncoder:
     def __init__(self, packed: np.ndarray, separable: bool, dilation: int, residual: bool, preset: str, grad_head=None,
                  heads: Optional[dict] = None, device="cuda", max_chunk: int = 256, offsets=None, decoder=None,
                  decoder_state: Optional[dict] = None, encoder_state: Optional[dict] = None, precision: str = "f32"):
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
-        if precision == "bf16" and not separable:
-            raise ValueError("precision='bf16' exists for the separable encoder only; this state dict holds the dense one")
+        _check_precision(precision, separable, "this state dict holds")
         if dilation not in (1, 2):
             raise ValueError(f"dilation must be 1 or 2, got {dilation}")
         if int(max_chunk) < 1:
@@ -245,30 +91,35 @@ class FrozenEncoder:
         if self.device.type != "cuda":
             raise nat.NativeError("FrozenEncoder runs in the HIP library: it needs a CUDA/ROCm device; there is no CPU fallback")
         self.max_chunk = int(max_chunk)
-        self.packed_host = np.ascontiguousarray(packed, dtype=np.float32)
         self.layer_offsets = list(offsets or [])
         lib = nat.load()
         cfg = self._cfg(64)
-        if lib.occ_encoder_packed_floats(C.byref(cfg)) != self.packed_host.size:
+        if lib.occ_encoder_packed_floats(C.byref(cfg)) != np.size(packed):
             raise nat.NativeError("packed encoder weights do not match the library's layout")
-        self.packed = torch.from_numpy(self.packed_host).to(self.device)
+        self.packed_host, self.packed = self._upload(packed)
         self.precision = precision
         self.packed_bf16 = self._pack_bf16() if precision == "bf16" else None
         self.grad_tanh = PRESETS[preset][2] if preset in PRESETS else False
         self.grad_w = self.grad_b = None
         if grad_head is not None:
-            self.grad_w = grad_head[0].to(self.device, torch.float32).contiguous()
-            self.grad_b = grad_head[1].to(self.device, torch.float32).contiguous()
+            self.grad_w, self.grad_b = self._head(grad_head)
         self.heads = heads or {}
         self._ws = {}  # (kind, chunk size, S) -> workspace
         self.dec_packed_host = self.dec_packed = None
         self.decoder_state = decoder_state  # the decoder's unfolded tensors by state-dict key (None without a decoder)
         self.encoder_state = encoder_state  # the encoder's (and the grad head's) unfolded tensors by state-dict key
         if decoder is not None:
-            self.dec_packed_host = np.ascontiguousarray(decoder, dtype=np.float32)
-            if lib.occ_decoder_packed_floats(C.byref(cfg)) != self.dec_packed_host.size:
+            if lib.occ_decoder_packed_floats(C.byref(cfg)) != np.size(decoder):
                 raise nat.NativeError("packed decoder weights do not match the library's layout")
-            self.dec_packed = torch.from_numpy(self.dec_packed_host).to(self.device)
+            self.dec_packed_host, self.dec_packed = self._upload(decoder)
+
+    def _upload(self, packed):
+        """A packed host buffer as (contiguous f32 numpy array, its copy on the device)."""
+        host = np.ascontiguousarray(packed, dtype=np.float32)
+        return host, torch.from_numpy(host).to(self.device)
+
+    def _head(self, weight_bias):
+        return tuple(t.to(self.device, torch.float32).contiguous() for t in weight_bias)
 
     def _pack_bf16(self) -> torch.Tensor:
         """The bf16 mode's packed buffer (include/occlusionenv_amd.h) of ``packed_host``, on the device: made on the host by
@@ -282,20 +133,27 @@ class FrozenEncoder:
                                             host.ctypes.data_as(C.c_void_p)), "occ_encoder_bf16_pack")
         return torch.from_numpy(host).to(self.device)
 
+    def _derived(self, packed=None, decoder=None, **fields) -> "FrozenEncoder":
+        """A copy of this encoder with ``fields`` replaced; what is not replaced is shared, not copied.  It starts with no
+        workspaces; ``packed`` / ``decoder`` are new packed host buffers, uploaded here, and the bf16 buffer is packed again
+        whenever ``packed`` or the precision changed.  This encoder is left as it is."""
+        new = copy.copy(self)
+        new._ws = {}
+        for name, value in fields.items():
+            setattr(new, name, value)
+        if packed is not None:
+            new.packed_host, new.packed = self._upload(packed)
+        if decoder is not None:
+            new.dec_packed_host, new.dec_packed = self._upload(decoder)
+        if packed is not None or "precision" in fields:
+            new.packed_bf16 = new._pack_bf16() if new.precision == "bf16" else None
+        return new
+
     def with_precision(self, precision: str) -> "FrozenEncoder":
         """A ``FrozenEncoder`` over this one's state (weights, heads, decoder: shared, not copied) that runs in ``precision``
         ("f32" or "bf16").  This encoder is left as it is."""
-        import copy
-
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
-        if precision == "bf16" and not self.separable:
-            raise ValueError("precision='bf16' exists for the separable encoder only; this encoder is the dense one")
-        new = copy.copy(self)
-        new._ws = {}
-        new.precision = precision
-        new.packed_bf16 = new._pack_bf16() if precision == "bf16" else None
-        return new
+        _check_precision(precision, self.separable, "this encoder is")
+        return self._derived(precision=precision)
 
     def _f32_only(self, what: str) -> None:
         if self.precision != "f32":
@@ -345,42 +203,24 @@ class FrozenEncoder:
         """A ``FrozenEncoder`` with this one's encoder (the packed weights are shared, not copied) and the decoder of
         ``sd``, a state dict holding the decoder and classifier keys of this preset (``DECODER_KEYS``), such as
         ``seghead.SegmentationHead.state_dict()`` after fine-tuning.  This encoder is left as it is."""
-        import copy
-
         if self.preset not in DECODER_KEYS:
             raise ValueError(f"preset {self.preset!r} has no segmentation decoder")
         dprefix, dcls = DECODER_KEYS[self.preset]
-        packed = pack_decoder(sd, dprefix, dcls)
-        new = copy.copy(self)
-        new._ws = {}
-        new.dec_packed_host = np.ascontiguousarray(packed, dtype=np.float32)
-        new.dec_packed = torch.from_numpy(new.dec_packed_host).to(self.device)
-        new.decoder_state = decoder_tensors(sd, dprefix, dcls)
-        return new
+        return self._derived(decoder=pack_decoder(sd, dprefix, dcls), decoder_state=decoder_tensors(sd, dprefix, dcls))
 
     def with_encoder(self, sd) -> "FrozenEncoder":
         """A ``FrozenEncoder`` with the encoder (and, when its keys are in ``sd``, the grad head) of ``sd``, a state dict
         under this preset's keys such as ``enctrain.TrainableEncoder.state_dict()`` after training, and this one's dilation,
         residual flag and decoder.  This encoder is left as it is."""
-        import copy
-
         prefix, ghead = PRESETS[self.preset][0], PRESETS[self.preset][1]
         separable, packed, offsets = pack_state_dict(sd, prefix)
         if separable != self.separable:
             raise ValueError("with_encoder: the state dict's encoder is " + ("separable" if separable else "dense") +
                              ", this encoder is not")
-        new = copy.copy(self)
-        new._ws = {}
-        new.packed_host = np.ascontiguousarray(packed, dtype=np.float32)
-        new.packed = torch.from_numpy(new.packed_host).to(self.device)
-        new.layer_offsets = list(offsets)
-        if new.precision == "bf16":
-            new.packed_bf16 = new._pack_bf16()
+        fields = dict(layer_offsets=list(offsets))
         if ghead is not None and ghead + "weight" in sd:
-            new.grad_w = _get(sd, ghead + "weight", (2, FEATURES)).to(self.device, torch.float32).contiguous()
-            new.grad_b = _get(sd, ghead + "bias", (2,)).to(self.device, torch.float32).contiguous()
-        new.encoder_state = encoder_tensors(sd, prefix, separable, ghead)
-        return new
+            fields["grad_w"], fields["grad_b"] = self._head((_get(sd, ghead + "weight", (2, FEATURES)), _get(sd, ghead + "bias", (2,))))
+        return self._derived(packed=packed, encoder_state=encoder_tensors(sd, prefix, separable, ghead), **fields)
 
     def with_state(self, sd) -> "FrozenEncoder":
         """``with_encoder(sd).with_decoder(sd)``: the whole trained network of ``fullnet.TrainableFullNetwork.state_dict()``."""
@@ -507,29 +347,22 @@ class FrozenEncoder:
             for o, shape, want in zip(out, shapes, wanted))
         if n_all == 0:
             return feats, prob, logits, dfeat
-        lib, cfg, stream = nat.load(), self._cfg(img), nat.stream_ptr(obs.device)
+        # the entry point, its workspace and the packed weights it reads (bf16 is encoder only: the decoder needs f32)
+        masked = bf16 or skip is not None  # the bf16 entry point takes the mask always, None when no row is skipped
+        kind = "encoder_bf16" if bf16 else "segment" if decoder else "encoder"
+        name = "occ_encoder_forward_bf16" if bf16 else FORWARD_ENTRY[decoder, masked]
+        weights = [self.packed_bf16] if bf16 else [self.packed, self.dec_packed] if decoder else [self.packed]
+        entry, cfg, stream = getattr(nat.load(), name), self._cfg(img), nat.stream_ptr(obs.device)
         pix = 4 * img * img  # bytes of one f32 map
         for lo, n in nat.row_chunks(n_all, self.max_chunk):
-            ws = self._workspace("segment" if decoder else "encoder_bf16" if bf16 else "encoder", n, img)
-            obs_lo, feats_lo = nat.ptr(obs, lo * 4 * pix), nat.ptr(feats, lo * 4 * FEATURES)
-            maps = (nat.ptr(prob, lo * pix), nat.ptr(logits, lo * pix), nat.ptr(dfeat, lo * CH * pix))
-            if bf16:
-                nat.check(lib.occ_encoder_forward_bf16(C.byref(cfg), nat.ptr(self.packed_bf16), obs_lo, n, nat.ptr(ws), ws.numel(),
-                                                       feats_lo, None if skip is None else nat.ptr(skip, 4 * lo), stream),
-                          "occ_encoder_forward_bf16")
-            elif decoder and skip is None:
-                nat.check(lib.occ_segment_forward(C.byref(cfg), nat.ptr(self.packed), nat.ptr(self.dec_packed), obs_lo, n, nat.ptr(ws),
-                                                  ws.numel(), feats_lo, *maps, stream), "occ_segment_forward")
-            elif decoder:
-                nat.check(lib.occ_segment_forward_masked(C.byref(cfg), nat.ptr(self.packed), nat.ptr(self.dec_packed), obs_lo, n,
-                                                         nat.ptr(ws), ws.numel(), feats_lo, *maps, nat.ptr(skip, 4 * lo), stream),
-                          "occ_segment_forward_masked")
-            elif skip is None:
-                nat.check(lib.occ_encoder_forward(C.byref(cfg), nat.ptr(self.packed), obs_lo, n, nat.ptr(ws), ws.numel(), feats_lo,
-                                                  stream), "occ_encoder_forward")
-            else:
-                nat.check(lib.occ_encoder_forward_masked(C.byref(cfg), nat.ptr(self.packed), obs_lo, n, nat.ptr(ws), ws.numel(),
-                                                         feats_lo, nat.ptr(skip, 4 * lo), stream), "occ_encoder_forward_masked")
+            ws = self._workspace(kind, n, img)
+            outs = [nat.ptr(feats, lo * 4 * FEATURES)]
+            if decoder:
+                outs += [nat.ptr(prob, lo * pix), nat.ptr(logits, lo * pix), nat.ptr(dfeat, lo * CH * pix)]
+            if masked:
+                outs.append(None if skip is None else nat.ptr(skip, 4 * lo))
+            nat.check(entry(C.byref(cfg), *[nat.ptr(w) for w in weights], nat.ptr(obs, lo * 4 * pix), n, nat.ptr(ws), ws.numel(),
+                            *outs, stream), name)
         return feats, prob, logits, dfeat
 
     @torch.no_grad()

@@ -3,7 +3,7 @@ dense ``FullNetwork`` / ``Segmenter`` encoder as trainable parameters, driven by
 
 ``TrainableEncoder.from_encoder(enc)`` takes a ``FrozenEncoder``.  ``net(obs)`` is the pooled feature (N,256), bitwise
 ``enc(obs)`` while the parameters are the checkpoint's, and one ``torch.autograd.Function``: forward folds the current
-BatchNorm parameters on the device in f64, packs them in the layout of ``encoder.pack_state_dict`` and runs
+BatchNorm parameters on the device in f64, packs them in the layout of ``netlayout.pack_state_dict`` and runs
 ``occ_encoder_train_forward``; backward runs ``occ_encoder_backward`` and maps the packed gradient back to the parameters.
 ``obs`` gets no gradient.  ``net.predict_grad(obs)`` is the grad head (``Linear(256, 2)``, with tanh for ``PredictorNet``) in
 torch on ``net(obs)``, so ``F.mse_loss(net.predict_grad(obs), target).backward()`` is one step of train_predict.py.  Any torch
@@ -19,9 +19,9 @@ one chunk (``N <= enc.max_chunk``), and the kept activations belong to the lates
 raises.  The gradient reaches the encoder through the pooled feature only; where the segmentation loss trains the encoder
 too (the pretrainer's step), the decoder's skip and input gradients join the encoder's in ``fullnet.TrainableFullNetwork``.
 
-The host path (fold, packed layout, parameters under the checkpoint's keys, workspace, the autograd function) is
-``nettrain.TrainableNet``'s, shared with ``seghead`` and ``fullnet``; here are the guards, the native symbols, the grad head
-and the view of the kept activations.
+The host path (parameters under the checkpoint's keys, workspace, the autograd function) is ``nettrain.TrainableNet``'s,
+shared with ``seghead`` and ``fullnet``, the fold and the packed layout are ``netlayout``'s; here are the guards, the native
+symbols, the grad head and the view of the kept activations.
 """
 from __future__ import annotations
 
@@ -29,7 +29,7 @@ import torch
 
 from .encoder import PRESETS, FrozenEncoder
 from .nettrain import TrainableNet, align256, encoder_part
-from .nettrain import pack_encoder_buffer, unpack_encoder_buffer  # noqa: F401  (the encoder's packed layout, importable here)
+from .netlayout import pack_encoder_buffer, unpack_encoder_buffer  # noqa: F401  (the encoder's packed layout, importable here)
 
 
 class PooledFeatureNet(TrainableNet):

@@ -5,7 +5,7 @@ what ``PreTrainer.train()`` (pretrainer.py:112-159) back-propagates through.
 ``TrainableFullNetwork.from_encoder(enc)`` takes a ``FrozenEncoder`` whose checkpoint held the decoder (presets "ppo" and
 "segmenter").  One ``torch.autograd.Function`` returns the pooled feature (N,256) and the predicted map (N,1,S,S), both
 differentiable: forward folds the current BatchNorm parameters on the device in f64, packs encoder and decoder in the
-layouts of ``encoder.pack_state_dict`` / ``encoder.pack_decoder`` and runs ``occ_fullnet_train_forward`` (the encoder runs
+layouts of ``netlayout.pack_state_dict`` / ``netlayout.pack_decoder`` and runs ``occ_fullnet_train_forward`` (the encoder runs
 once); backward runs ``occ_fullnet_backward`` on both upstream gradients (an absent one arrives as zeros) and maps the two
 packed gradients back to the parameters.  ``obs`` gets no gradient.  While the parameters are the checkpoint's the pooled
 feature is bitwise ``enc(obs)`` and the map bitwise ``enc.segment(obs)``.
@@ -37,9 +37,9 @@ forward: a backward of an earlier forward raises.
 ``netoptim.PackedAdamW(net)`` moves the trainable values into packed masters and takes the optimizer step in one native
 launch; ``net.sync_parameters()`` (and ``net.state_dict()``, which calls it) writes them back under the checkpoint's keys.
 
-The host path (fold, packed layouts, parameters under the checkpoint's keys, workspace, the autograd function) is
-``nettrain.TrainableNet``'s on two parts, the encoder's and the decoder's; here are the guards, the native symbols and the
-heads.  The heads and ``forward`` are ``JointNet``'s, which ``sepfullnet.TrainableSeparableFullNetwork`` (the separable
+The host path (parameters under the checkpoint's keys, workspace, the autograd function) is ``nettrain.TrainableNet``'s on
+two ``netlayout.Part``s, the encoder's and the decoder's, which hold the packed layouts; here are the guards, the native
+symbols and the heads.  The heads and ``forward`` are ``JointNet``'s, which ``sepfullnet.TrainableSeparableFullNetwork`` (the separable
 encoder's joint step) shares.
 """
 from __future__ import annotations

@@ -10,10 +10,10 @@ checkpoint tensor or half of a BatchNorm (scale, shift) pair, and AdamW is eleme
 ``PackedAdamW(net)`` makes ``net`` packed-resident (``net._resident``, a ``PackedState``):
 
   * per part one master tensor in packed order whose BatchNorm slots hold raw gamma and beta, built once from the current
-    parameters with the part's own ``Part.pack``; a flat tensor (weight | bias) for the grad head.  These are the trainable
+    parameters with the part's own ``netlayout.Part.pack``; a flat tensor (weight | bias) for the grad head.  These are the trainable
     leaves: plain attributes, not registered parameters, so the state-dict keys stay the checkpoint's;
   * per part the packed buffer the forward reads, written by the optimizer's kernel: a copy of the master with, under running
-    statistics, every (gamma, beta) folded to (scale, shift) in f64 as ``nettrain.fold_bn_vectors`` folds them, to the bit;
+    statistics, every (gamma, beta) folded to (scale, shift) in f64 as ``netlayout.fold_bn_vectors`` folds them, to the bit;
   * ``net(obs)`` runs ``nettrain._PackedStep``: the native forward on those buffers, the packed gradients returned unchanged
     as the masters' ``.grad`` (autograd adds the gradients of several backward calls); the head's ``linear`` reads views of
     the flat tensor;

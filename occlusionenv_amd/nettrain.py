@@ -1,10 +1,10 @@
 """The one host path of the native training wrappers: ``seghead.SegmentationHead`` (decoder and classifier),
 ``enctrain.TrainableEncoder`` (dense encoder), ``septrain.TrainableSeparableEncoder`` (separable encoder),
 ``fullnet.TrainableFullNetwork`` (dense encoder and decoder) and ``sepfullnet.TrainableSeparableFullNetwork`` (separable
-encoder and decoder).  Each of them is a ``TrainableNet`` over one or two ``Part``s,
-and one ``torch.autograd.Function`` runs them all: forward folds the current
-BatchNorm parameters on the device in f64, packs every part in the library's layout and runs the native train forward;
-backward runs the native backward and maps each part's packed gradient back to the parameters.
+encoder and decoder).  Each of them is a ``TrainableNet`` over one or two ``netlayout.Part``s, and one
+``torch.autograd.Function`` runs them all: forward folds the current BatchNorm parameters on the device in f64
+(``netlayout.fold_bn_vectors``), packs every part in the library's layout (``Part.pack``) and runs the native train forward;
+backward runs the native backward and maps each part's packed gradient back to the parameters (``Part.unpack``).
 
 BatchNorm keeps its running statistics (buffers); only its affine parameters train.  The joint networks
 (``fullnet.JointNet``) also offer ``batch_stats=True``, ``nn.BatchNorm2d`` in train mode as pretrainer.py runs it: while
@@ -22,132 +22,17 @@ wrote to the same native forward and returns the packed gradients as they are; n
 from __future__ import annotations
 
 import ctypes as C
-from typing import Callable, NamedTuple, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 
 from . import _native as nat
-from .encoder import (BN_EPS, CH, DECODER_KEYS, FEATURES, PRESETS, FrozenEncoder, decoder_packed_floats, decoder_plan, layer_plan,
-                      packed_floats)
-
-LEAVES = ("conv.weight", "conv.bias", "bn.weight", "bn.bias")  # the four parameters of a dense layer, in packed order
-# those of a separable layer: depthwise (3,1), depthwise (1,3), pointwise, its bias, then the BatchNorm affine
-SEP_LEAVES = ("conv.0.weight", "conv.1.weight", "conv.2.weight", "conv.2.bias", "bn.weight", "bn.bias")
-ENCODER_PERM, DECODER_PERM = (1, 2, 3, 0), (0, 2, 3, 1)  # conv (cout,cin,3,3) / transposed conv (cin,cout,3,3) -> (cin,3,3,cout)
-
-
-# ---- the BatchNorm fold and the packed layout, as pure functions of tensors on any device ----------------------------------
-def fold_bn_vectors(gamma, beta, mean, var):
-    """-> (scale, shift, rstd) in f64: y = relu(.) * scale + shift (``encoder.fold_bn`` on c-vectors)."""
-    rstd = 1.0 / torch.sqrt(var.double() + BN_EPS)
-    scale = gamma.double() * rstd
-    return scale, beta.double() - mean.double() * scale, rstd
-
-
-def bn_param_grads(dscale, dshift, mean, var):
-    """(dgamma, dbeta) in f64 from the gradients of the folded affine: scale = gamma rstd, shift = beta - mean gamma rstd."""
-    rstd = 1.0 / torch.sqrt(var.double() + BN_EPS)
-    return (dscale.double() - mean.double() * dshift.double()) * rstd, dshift.double()
-
-
-def pack_layers(layers, perm, tail=()) -> torch.Tensor:
-    """layers: (w, bias, scale, shift) each, ``w.permute(perm)`` being (cin,3,3,cout) -> the packed f32 buffer
-    w[ci][ky * 3 + kx][co] | bias | scale | shift per layer, then the ``tail`` tensors."""
-    parts = []
-    for w, b, s, t in layers:
-        parts += [w.permute(*perm).reshape(-1), b.reshape(-1), s.reshape(-1), t.reshape(-1)]
-    parts += [x.reshape(-1) for x in tail]
-    return torch.cat([p.to(torch.float32) for p in parts])
-
-
-def unpack_layers(buf: torch.Tensor, plan, perm):
-    """The inverse of ``pack_layers`` for layers of ``plan`` = [(cin, cout)] -> ([(w, bias, scale, shift)], views of ``buf``;
-    the offset of the tail)."""
-    inverse = [perm.index(d) for d in range(4)]
-    layers, off = [], 0
-    for cin, cout in plan:
-        w = buf[off:off + 9 * cin * cout].reshape(cin, 3, 3, cout).permute(*inverse)
-        off += 9 * cin * cout
-        layers.append((w, buf[off:off + cout], buf[off + cout:off + 2 * cout], buf[off + 2 * cout:off + 3 * cout]))
-        off += 3 * cout
-    return layers, off
-
-
-def _encoder_plan():
-    return [(cin, cout) for _stem, cin, cout, _sep, _stride in layer_plan(False)]
-
-
-def pack_encoder_buffer(layers) -> torch.Tensor:
-    """layers: sixteen (w (cout,cin,3,3), bias, scale, shift) -> the packed f32 buffer of the dense encoder
-    (``encoder.pack_state_dict``)."""
-    buf = pack_layers(layers, ENCODER_PERM)
-    assert buf.numel() == packed_floats(False)
-    return buf
-
-
-def unpack_encoder_buffer(buf: torch.Tensor):
-    """The inverse of ``pack_encoder_buffer`` -> [(w (cout,cin,3,3), bias, scale, shift)] x 16, views of ``buf``."""
-    if buf.numel() != packed_floats(False):
-        raise ValueError(f"packed dense encoder buffer has {buf.numel()} floats, expected {packed_floats(False)}")
-    return unpack_layers(buf, _encoder_plan(), ENCODER_PERM)[0]
-
-
-def _sep_plan():
-    return [(cin, cout, sep) for _stem, cin, cout, sep, _stride in layer_plan(True)]
-
-
-def pack_sep_encoder_buffer(layers) -> torch.Tensor:
-    """layers: sixteen tuples in packed order, a separable layer (wv (cin,1,3,1), wh (cin,1,1,3), pw (cout,cin,1,1), bias,
-    scale, shift), a down (w (cout,cin,3,3), bias, scale, shift) -> the packed f32 buffer of the separable encoder
-    (``encoder.pack_state_dict``): wv[ci][3] | wh[ci][3] | pw[ci][co] | bias | scale | shift per separable layer, the dense
-    layout per down."""
-    parts = []
-    for layer in layers:
-        if len(layer) == 6:
-            wv, wh, pw, b, s, t = layer
-            parts += [wv.reshape(-1), wh.reshape(-1), pw[:, :, 0, 0].t().reshape(-1), b.reshape(-1), s.reshape(-1), t.reshape(-1)]
-        else:
-            parts.append(pack_layers([layer], ENCODER_PERM))
-    buf = torch.cat([p.to(torch.float32) for p in parts])
-    assert buf.numel() == packed_floats(True)
-    return buf
-
-
-def unpack_sep_encoder_buffer(buf: torch.Tensor):
-    """The inverse of ``pack_sep_encoder_buffer`` -> sixteen tuples of views of ``buf`` in the checkpoint's shapes."""
-    if buf.numel() != packed_floats(True):
-        raise ValueError(f"packed separable encoder buffer has {buf.numel()} floats, expected {packed_floats(True)}")
-    layers, off = [], 0
-    for cin, cout, sep in _sep_plan():
-        if sep:
-            wv = buf[off:off + 3 * cin].reshape(cin, 1, 3, 1)
-            wh = buf[off + 3 * cin:off + 6 * cin].reshape(cin, 1, 1, 3)
-            off += 6 * cin
-            pw = buf[off:off + cin * cout].reshape(cin, cout).t().reshape(cout, cin, 1, 1)
-            off += cin * cout
-            layers.append((wv, wh, pw, buf[off:off + cout], buf[off + cout:off + 2 * cout], buf[off + 2 * cout:off + 3 * cout]))
-            off += 3 * cout
-        else:
-            (layer,), used = unpack_layers(buf[off:], [(cin, cout)], ENCODER_PERM)
-            layers.append(layer)
-            off += used
-    return layers
-
-
-def pack_decoder_buffer(levels, cls_w, cls_b) -> torch.Tensor:
-    """levels: five (w (2c,c,3,3), bias, scale, shift) -> the packed f32 buffer of the decoder, then cls_w[8] | cls_b
-    (``encoder.pack_decoder``)."""
-    buf = pack_layers(levels, DECODER_PERM, (cls_w, cls_b))
-    assert buf.numel() == decoder_packed_floats()
-    return buf
-
-
-def unpack_decoder_buffer(buf: torch.Tensor):
-    """The inverse of ``pack_decoder_buffer`` -> ([(w (2c,c,3,3), bias, scale, shift)] x 5, cls_w (1,8,1,1), cls_b (1,))."""
-    if buf.numel() != decoder_packed_floats():
-        raise ValueError(f"packed decoder buffer has {buf.numel()} floats, expected {decoder_packed_floats()}")
-    levels, off = unpack_layers(buf, [(cin, cout) for _j, cin, cout in decoder_plan()], DECODER_PERM)
-    return levels, buf[off:off + CH].reshape(1, CH, 1, 1), buf[off + CH:off + CH + 1]
+from .encoder import FrozenEncoder
+# the fold and the packed layout, as pure functions of tensors on any device: netlayout's, importable here as before
+from .netlayout import (DECODER_PERM, ENCODER_PERM, FEATURES, LEAVES, SEP_LEAVES, Part, bn_layer_shapes, bn_param_grads,  # noqa: F401
+                        decoder_part, encoder_part, fold_bn_vectors, pack_decoder_buffer, pack_encoder_buffer, pack_layers,
+                        pack_sep_encoder_buffer, sep_encoder_part, unpack_decoder_buffer, unpack_encoder_buffer, unpack_layers,
+                        unpack_sep_encoder_buffer)
 
 
 def align256(b: int) -> int:
@@ -156,16 +41,6 @@ def align256(b: int) -> int:
 
 
 BN_MOMENTUM = 0.1  # nn.BatchNorm2d's default, which the reference's layers keep
-
-
-def bn_layer_shapes(img: int):
-    """[(channels, pixels of one env's plane)] of the 21 BatchNorm layers of the joint network on side ``img``, in packed
-    order (16 encoder layers, 5 decoder levels): the layout of ``bn_stats`` (mean[c] | var_biased[c] per layer)."""
-    shapes, h = [], img
-    for _stem, _cin, cout, _sep, stride in layer_plan(False):
-        h = (h + stride - 1) // stride
-        shapes.append((cout, h * h))
-    return shapes + [(cout, ((img // 16) << j) ** 2) for j, _cin, cout in decoder_plan()]
 
 
 def register_under_key(module: torch.nn.Module, key: str, t: torch.Tensor, buffer: bool) -> None:
@@ -181,48 +56,6 @@ def register_under_key(module: torch.nn.Module, key: str, t: torch.Tensor, buffe
         m.register_buffer(leaf, t.clone())
     else:
         m.register_parameter(leaf, torch.nn.Parameter(t.clone()))
-
-
-# ---- a trainable part: where its tensors sit in the checkpoint and how they are packed -------------------------------------
-class Part(NamedTuple):
-    stems: Tuple[str, ...]  # per layer in packed order: stem + its leaves are its parameters, stem + "bn.running_*" its statistics
-    tail: Tuple[str, ...]   # the parameters packed after the layers
-    floats: int             # of the packed buffer
-    pack: Callable          # (layers, tail tensors) -> packed buffer; a layer: (its conv leaves.., scale, shift)
-    unpack: Callable        # packed buffer -> (layers, tail tensors)
-    leaves: Optional[Tuple[Tuple[str, ...], ...]] = None  # per layer, ending in bn.weight, bn.bias; None: LEAVES for every layer
-
-    def layer_leaves(self):
-        return self.leaves if self.leaves is not None else (LEAVES,) * len(self.stems)
-
-
-def encoder_part(preset: str) -> Part:
-    """The 16 layers of the dense encoder under ``PRESETS[preset]``'s prefix."""
-    stems = tuple(PRESETS[preset][0] + stem for stem, _ci, _co, _sep, _stride in layer_plan(False))
-    return Part(stems, (), packed_floats(False), lambda layers, _tail: pack_encoder_buffer(layers),
-                lambda buf: (unpack_encoder_buffer(buf), ()))
-
-
-def sep_encoder_part(preset: str) -> Part:
-    """The 16 layers of the separable encoder under ``PRESETS[preset]``'s prefix: eleven separable layers, five dense downs."""
-    plan = layer_plan(True)
-    stems = tuple(PRESETS[preset][0] + stem for stem, _ci, _co, _sep, _stride in plan)
-    leaves = tuple(SEP_LEAVES if sep else LEAVES for _stem, _ci, _co, sep, _stride in plan)
-    return Part(stems, (), packed_floats(True), lambda layers, _tail: pack_sep_encoder_buffer(layers),
-                lambda buf: (unpack_sep_encoder_buffer(buf), ()), leaves)
-
-
-def decoder_part(preset: str) -> Part:
-    """The 5 up levels of the decoder and the 1x1 classifier under ``DECODER_KEYS[preset]``'s prefixes."""
-    prefix, classifier = DECODER_KEYS[preset]
-    stems = tuple(f"{prefix}{j}.up." for j, _ci, _co in decoder_plan())
-
-    def unpack(buf):
-        levels, cls_w, cls_b = unpack_decoder_buffer(buf)
-        return levels, (cls_w, cls_b)
-
-    return Part(stems, (classifier + "weight", classifier + "bias"), decoder_packed_floats(),
-                lambda levels, tail: pack_decoder_buffer(levels, *tail), unpack)
 
 
 # ---- the module and its autograd function ------------------------------------------------------------------------------------

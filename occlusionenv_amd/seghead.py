@@ -7,16 +7,16 @@ predicted occlusion map (N,1,S,S), bitwise ``enc.segment(obs)`` while the parame
 ``occ_segment_train_forward``; backward runs ``occ_segment_backward`` and maps the packed gradient back to the parameters.
 ``obs`` gets no gradient and the encoder stays frozen.  Any torch optimizer works on ``head.parameters()``.
 
-The parameters sit under the reference's state-dict keys (``encoder.DECODER_KEYS``), so ``head.state_dict()`` drops back into
+The parameters sit under the reference's state-dict keys (``netlayout.DECODER_KEYS``), so ``head.state_dict()`` drops back into
 the checkpoint it came from and ``enc.with_decoder(head.state_dict())`` is the fine-tuned network for inference.
 
 Deviation from pretrainer.py, which trains in train mode: the decoder's BatchNorm keeps its running statistics (buffers
 here); only its affine parameters train.  A training call is one chunk (``N <= enc.max_chunk``), and the kept activations
 belong to the latest forward: a backward of an earlier forward raises.
 
-The host path (fold, packed layout, parameters under the checkpoint's keys, workspace, the autograd function) is
-``nettrain.TrainableNet``'s, shared with ``enctrain`` and ``fullnet``; here are the guards, the native symbols, the outputs
-and the view of the kept activations.
+The host path (parameters under the checkpoint's keys, workspace, the autograd function) is ``nettrain.TrainableNet``'s,
+shared with ``enctrain`` and ``fullnet``, the fold and the packed layout are ``netlayout``'s; here are the guards, the native
+symbols, the outputs and the view of the kept activations.
 """
 from __future__ import annotations
 
@@ -27,8 +27,9 @@ import torch
 from . import _native as nat
 from .encoder import CH, LEVELS, FrozenEncoder
 from .nettrain import TrainableNet, align256, decoder_part
-# importable here as before: the decoder's packed layout, and the pure functions that moved to nettrain
-from .nettrain import bn_param_grads, fold_bn_vectors, pack_decoder_buffer, register_under_key, unpack_decoder_buffer  # noqa: F401
+# importable here as before: the decoder's packed layout and the folds (netlayout), and what moved to nettrain
+from .netlayout import bn_param_grads, fold_bn_vectors, pack_decoder_buffer, unpack_decoder_buffer  # noqa: F401
+from .nettrain import register_under_key  # noqa: F401
 
 
 class SegmentationHead(TrainableNet):

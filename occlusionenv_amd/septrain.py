@@ -19,7 +19,7 @@ from __future__ import annotations
 from .encoder import FrozenEncoder
 from .enctrain import PooledFeatureNet
 from .nettrain import sep_encoder_part
-from .nettrain import pack_sep_encoder_buffer, unpack_sep_encoder_buffer  # noqa: F401  (the packed layout, importable here)
+from .netlayout import pack_sep_encoder_buffer, unpack_sep_encoder_buffer  # noqa: F401  (the packed layout, importable here)
 
 
 class TrainableSeparableEncoder(PooledFeatureNet):
